@@ -6,17 +6,23 @@ states + frozen-teacher forward + replay cross-entropy + (L-1)-layer per-modalit
 global-norm clip + AdamW (accumulate 1, replay on every step: SURVEY.md section 8d "primary").  Nothing is skipped or
 cached inside the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--model 410m] [--batch 32] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--model 410m] [--batch 32] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 ``python bench.py --gpus N`` without a launcher starts the N ranks itself (a torch.distributed.run child, before anything touches
 the GPU) and fails if the node has fewer than N GPUs or fewer than N ranks join -- it never reports a 1-GPU number for N > 1.
 
-The JSON line carries, beside the contract's keys: ``roofline`` (dominant kernel = the bf16 MFMA GEMM: algorithmic flops / the
-kernel's own execution time inside the step, measured live with start/stop events on the launches -- the quantity rocprofv3
---kernel-trace reports, see profiles/), ``kernels`` (the same for attention and for every HBM-bound kernel against 8 TB/s),
-``secondary`` (the reference's blended schedule: bs 16 x accumulate 4, 3 plain-CE + 1 MAFED micro-batch per optimiser step,
-scripts/run_seed42.sh:51-70) and ``cpu_baseline``.
+A plain run sets up, warms up, times the K steps and prints the headline line (``ms_per_step`` = one timed step).
+``--dump-outputs DIR`` then writes what the last timed step computed as float32 / float64 ``DIR/<name>.npy``: ``loss``,
+``grad_norm``, ``lr`` and a fixed seeded sample of the updated parameters (``params_sample``); the inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
+
+``--full`` adds the measurements beside the headline, each a key of the JSON line: ``roofline`` (dominant kernel = the bf16
+MFMA GEMM: algorithmic flops / the kernel's own execution time inside the step, measured live with start/stop events on the
+launches -- the quantity rocprofv3 --kernel-trace reports, see profiles/), ``kernels`` (the same for attention and for every
+HBM-bound kernel against 8 TB/s), ``ddp_forecast``, ``teacher_cache``, ``secondary`` (the reference's blended schedule: bs 16 x
+accumulate 4, 3 plain-CE + 1 MAFED micro-batch per optimiser step, scripts/run_seed42.sh:51-70), ``image_input`` and
+``cpu_baseline``; the ``--no-*`` options leave single ones out.
 """
 import argparse
 import json
@@ -177,6 +183,33 @@ def dump_profile(directory, name, kp, rank):
             fp.write(f"{tag},{work:.6g},{st:.4f},{ms * 1e3:.3f}\n")
 
 
+DUMP_PARAMS_SAMPLE = 1 << 22   # parameters written by --dump-outputs: 4M fp32 = 16 MB
+
+
+def dump_outputs(directory, rec, trainer, model):
+    """What the last timed step handed its caller -> ``directory/<name>.npy`` (float32 / float64): the step record's loss, clip
+    norm and learning rate, and the parameters the step left behind, as a fixed seeded sample (the whole vector is 1.6 GB at
+    410M)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    trainer.join()   # the pipelined AdamW of the last step has landed in the parameters
+    torch.cuda.synchronize()
+    flat = model.flat_params
+    if flat.numel() <= DUMP_PARAMS_SAMPLE:
+        sample = flat
+    else:
+        idx = torch.randint(0, flat.numel(), (DUMP_PARAMS_SAMPLE,), generator=torch.Generator().manual_seed(4242)).sort().values
+        sample = flat[idx.to(flat.device)]
+    arrays = {"params_sample": sample}
+    for key in ("loss", "grad_norm", "lr"):
+        if key in rec:
+            v = rec[key]
+            arrays[key] = v.detach() if torch.is_tensor(v) else torch.tensor(v, dtype=torch.float64)
+    for name, t in arrays.items():
+        t = t.cpu()
+        np.save(os.path.join(directory, name + ".npy"), t.numpy() if t.dtype in (torch.float32, torch.float64) else t.float().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -187,10 +220,14 @@ def main():
     ap.add_argument("--img-tokens", type=int, default=256)
     ap.add_argument("--txt-tokens", type=int, default=32)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--full", action="store_true", help="after the headline also measure rooflines, ddp_forecast, teacher_cache, secondary, "
+                    "image_input and cpu_baseline (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed (loss, grad_norm, lr, a "
+                    "seeded sample of the updated parameters) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-profile", action="store_true", help="skip the per-kernel roofline steps after the timed region")
     ap.add_argument("--dump-profile", default=None, metavar="DIR", help="write the per-launch records behind `roofline` / `kernels` as CSV (tag, "
-                    "algorithmic work, start ms, duration us) for the timed configuration and for the single-stream repeat")
+                    "algorithmic work, start ms, duration us) for the timed configuration and for the single-stream repeat (with --full)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the blended-schedule measurement (3 CE + 1 MAFED micro-batches)")
     ap.add_argument("--no-teacher-cache-leg", action="store_true", help="skip the teacher-cache measurement (frozen-teacher states of the whole "
                     "replay memory resident in HBM: 108 GB at 410M / 4000 samples)")
@@ -364,13 +401,15 @@ def main():
     log(f"timed region: {args.steps} steps in {dt * 1e3:.1f} ms (host enqueue wall {t_host * 1e3:.1f} ms, CPU {c_host * 1e3:.1f} ms; "
         f"hipMalloc calls inside {a_timed1[0] - a_timed0[0]}), loss {loss:.5f}")
     assert loss == loss, "NaN loss in the timed region"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rec, tr, student)
 
     # live rooflines: N_PROF more steps of the SAME configuration (same streams / overlap) with every hot kernel launched
     # between a start/stop event pair: per-kernel execution time, as rocprofv3 --kernel-trace would report it.  Not part of
     # `value`.  Every rank takes these steps (they contain the gradient collectives); rank 0 reports.
     N_PROF = 3
     prof_step, prof_alone = None, None
-    if not args.no_kernel_profile:
+    if args.full and not args.no_kernel_profile:
         with KernelProfile() as kp:
             for i in range(N_PROF):
                 tr.step(task_batch, args.warmup + args.steps + i)
@@ -397,7 +436,7 @@ def main():
     # section 5: 2.7 ms with all seven xGMI links busy, 18.6 ms for one ring) x the two ways the backward beside it can run: the persistent
     # kernels in ticketed order, or every GEMM of that backward on the 128 x 128 kernels (MAFED_EPI_NO_PERSISTENT, round 3's choice).
     ddp_forecast = None
-    if world == 1 and not args.no_ddp_forecast:
+    if args.full and world == 1 and not args.no_ddp_forecast:
         from mafed_amd.dist import EmulatedReducer
         tr.join()
         rows = []
@@ -436,7 +475,7 @@ def main():
     # (FeatureDistillation.build_teacher_cache: fp32 [layers, samples, S, h], filled once per task by the same kernels), a replay step
     # gathers its 32 samples' rows instead of running the teacher forward
     teacher_cache = None
-    if not args.no_teacher_cache_leg:
+    if args.full and not args.no_teacher_cache_leg:
         tr.join()
         need = (cfg.num_hidden_layers - 1) * len(mem) * (P + T) * cfg.hidden_size * 4
         free, _tot = torch.cuda.mem_get_info(dev)
@@ -473,7 +512,7 @@ def main():
     # secondary metric: the reference's blended schedule -- bs 16 x accumulate 4, replay_interval 4: per optimiser
     # step three plain-CE micro-batches on task data and one MAFED micro-batch on memory data (scripts/run_seed42.sh:51-70)
     secondary = None
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         tr.join()
         B2 = 16
         mem2 = HBMReplayBuffer(B2, dev, seed=2236 + rank)
@@ -518,7 +557,7 @@ def main():
     # third leg: the same all-distill step fed with IMAGES (pixel_values [B,3,224,224] -> native frozen CLIP-ViT-L/14 tower -> step), the
     # data path of upstream's training loop; the tower runs once per step (upstream: twice, distillation.py:91,222).  Random tower weights.
     image_leg = None
-    if not args.no_image_leg and cfg.vision_hidden_size == 1024 and P == 256:
+    if args.full and not args.no_image_leg and cfg.vision_hidden_size == 1024 and P == 256:
         from mafed_amd.vision import ClipVisionConfig, ClipVisionTower
         tr.join()
         student.zero_grad()
@@ -684,7 +723,7 @@ def main():
             out["teacher_cache"] = teacher_cache
         if ddp_forecast:
             out["ddp_forecast"] = ddp_forecast
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.model, P, T)
             except Exception as e:  # the CPU leg must never take the GPU number down with it

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Run ON THE GPU BOX (via gpurun) from the repo root: regenerates the judged artifacts under gpurun_out/profiles_new/
-#   bench_line.json            the default bench.py line (roofline from live HIP events, cpu_baseline)
+#   bench_line.json            the bench.py --full line (roofline from live HIP events, cpu_baseline)
 #   bench_kernel_stats.csv     rocprofv3 --kernel-trace --stats summary of the same command (without the CPU leg)
 #   bench_kernel_by_shape.csv  per (kernel, grid) launch statistics from the same trace
 #   timeline.txt               tools/trace_timeline.py on the same trace (overlap depth, per-queue mix, idle gaps)
@@ -10,7 +10,7 @@ set -e
 OUT=gpurun_out/profiles_new
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-if [ "$SKIP_BENCH" != "1" ]; then timeout -k 10 500 python3 bench.py --dump-profile $OUT 2> $OUT/bench_stderr.log | tail -1 > $OUT/bench_line.json; fi
+if [ "$SKIP_BENCH" != "1" ]; then timeout -k 10 500 python3 bench.py --full --dump-profile $OUT 2> $OUT/bench_stderr.log | tail -1 > $OUT/bench_line.json; fi
 rm -rf gpurun_out/prof_kt
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_kt -- python3 bench.py --no-cpu-baseline --no-kernel-profile --no-secondary --no-image-leg --no-teacher-cache-leg --no-ddp-forecast > /dev/null 2>&1
 ks=$(find gpurun_out/prof_kt -name "*kernel_stats.csv" | head -1)
