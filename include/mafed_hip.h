@@ -264,6 +264,41 @@ int mafed_ewc_penalty_fwd(const float* p, const float* p_old, const float* fishe
 int mafed_ewc_penalty_bwd(const float* p, const float* p_old, const float* fisher, int64_t n, float lambda,
                           const float* coef_dev, float* grad, void* stream);
 
+/* ---- representation-drift analysis: per-layer, per-modality linear CKA (mafed/analysis/) --------------------------
+ * Modality pooling of one forward's hidden states (mafed/analysis/get_average_CKA_per_layer.py:107-118): for sample b and
+ * layer l (hidden_host[l] = hidden_states[l + 1], fp32 [B, S, h], S = P + T)
+ *   out[0, l, rows[b], :] = mean of hidden[b, 0:P, :]                          (image)
+ *   out[1, l, rows[b], :] = mean of hidden[b, S - txt_len : S, :]              (text, txt_len = sum_t attention_mask[b, t])
+ * out fp32 [2, L, n, h]; rows int64 [B] or NULL (row b; a row outside [0, n) drops the sample); txt_len == 0 gives NaN, as the reference's mean of an empty slice.
+ * fp64 sums in a fixed order.  L <= 64; hidden_host is a HOST array of L device pointers. */
+int mafed_cka_pool(const float* const* hidden_host, int L, int B, int S, int P, int h, const int64_t* attention_mask, int T,
+                   const int64_t* rows, int64_t n, float* out, void* stream);
+
+/* Column means and centred row norms of G feature sets X_g [n, h] (row stride ldx, set g at X + g * set_stride), fp64:
+ *   mean[g, c] = sum_r X_g[r, c] / n            row_sqnorm[g, r] = sum_c (X_g[r, c] - mean[g, c])^2   (row_sqnorm may be NULL)
+ * Replaces: the centring of feature_space_linear_cka (mafed/analysis/cka.py:133-134) and its debiased estimator's
+ * sum_squared_rows (cka.py:144-147).  Deterministic (fixed-order fp64 reductions). */
+size_t mafed_cka_stats_workspace_bytes(int64_t G, int64_t n, int64_t h);
+int mafed_cka_stats(const float* X, int64_t G, int64_t n, int64_t h, int64_t ldx, int64_t set_stride, double* mean,
+                    double* row_sqnorm, void* workspace, size_t workspace_bytes, void* stream);
+
+/* One product of mafed_cka_hsic: X [n, hx] (row stride ldx) and Y [n, hy] (row stride ldy), fp32, with their fp64 column
+ * means (mafed_cka_stats).  A product whose X, mean_x, hx and ldx equal Y, mean_y, hy and ldy is a self term. */
+typedef struct mafed_cka_product {
+  const float* X; const double* mean_x; int64_t ldx; int64_t hx;
+  const float* Y; const double* mean_y; int64_t ldy; int64_t hy;
+  int64_t n;
+} mafed_cka_product;
+
+/* Batched centred cross-Gram Frobenius norm, out[p] = ||(X_p - 1 mean_x^T)^T (Y_p - 1 mean_y^T)||_F^2 (fp64 [count]).
+ * Replaces: np.linalg.norm(features_x.T.dot(features_y)) ** 2 and the two self-similarity norms of
+ * feature_space_linear_cka (mafed/analysis/cka.py:136-138).  fp32-input MFMA on operands centred in fp64, the MFMA
+ * accumulators flushed into second-level fp32 ones every 4096 rows, C never stored, fp64 squares; results are bitwise the
+ * same for every batch composition.
+ * n, hx, hy < 2^31.  workspace: mafed_cka_hsic_workspace_bytes(products, count) bytes (host-side query). */
+size_t mafed_cka_hsic_workspace_bytes(const mafed_cka_product* products, int count);
+int mafed_cka_hsic(const mafed_cka_product* products, int count, double* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- embedding + concat (mafed/model/vl_pythia.py:282-283) ---------------------------------------------------
  * h0[b, :P] = image[b] ; h0[b, P:] = embed_in[input_ids[b]]  -> fp32 [B,P+T,h].  image in img_dtype [B,P,h]. */
 int mafed_embed_concat_fwd(const void* image, mafed_dtype img_dtype, const float* embed_in, const int64_t* input_ids,

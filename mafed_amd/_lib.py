@@ -50,6 +50,11 @@ SIGNATURES = {
     "mafed_ewc_workspace_bytes": (_z, [_l]),
     "mafed_ewc_penalty_fwd": (_i, [_p, _p, _p, _l, _f, _f, _p, _p, _z, _p]),
     "mafed_ewc_penalty_bwd": (_i, [_p, _p, _p, _l, _f, _p, _p, _p]),
+    "mafed_cka_pool": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _l, _p, _p]),
+    "mafed_cka_stats_workspace_bytes": (_z, [_l, _l, _l]),
+    "mafed_cka_stats": (_i, [_p, _l, _l, _l, _l, _l, _p, _p, _p, _z, _p]),
+    "mafed_cka_hsic_workspace_bytes": (_z, [_p, _i]),
+    "mafed_cka_hsic": (_i, [_p, _i, _p, _p, _z, _p]),
     "mafed_colsum_workspace_bytes": (_z, [_l, _l]),
     "mafed_colsum": (_i, [_p, _i, _l, _l, _l, _p, _p, _z, _p]),
     "mafed_layernorm_fwd": (_i, [_p, _l, _i, _f, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
@@ -108,6 +113,11 @@ class GemmProblem(C.Structure):
     """``mafed_gemm_problem`` of include/mafed_hip.h (one entry of a grouped launch)."""
     _fields_ = [("M", _l), ("N", _l), ("K", _l), ("A", _p), ("lda", _l), ("B", _p), ("ldb", _l), ("C", _p), ("ldc", _l),
                 ("bias", _p), ("epilogue", _i), ("aux", _p), ("res1", _p), ("res2", _p), ("beta", _f), ("colsum", _p), ("sumsq", _p)]
+
+
+class CkaProduct(C.Structure):
+    """``mafed_cka_product`` of include/mafed_hip.h (one product of a batched HSIC launch)."""
+    _fields_ = [("X", _p), ("mean_x", _p), ("ldx", _l), ("hx", _l), ("Y", _p), ("mean_y", _p), ("ldy", _l), ("hy", _l), ("n", _l)]
 
 
 _lib: Optional[C.CDLL] = None

@@ -456,6 +456,26 @@ class VLPythiaForCausalLM(nn.Module):
                                   attention_mask.to(dev, torch.int64).contiguous(), None, True, train=False, n_hidden=n_hidden)
         return tuple(st["hidden"])
 
+    @torch.no_grad()
+    def modality_features(self, input_ids, attention_mask, pixel_values=None, patch_embeddings=None, out: Optional[torch.Tensor] = None,
+                          rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Per-sample mean image and mean text hidden state of every layer 1..L (mafed/analysis/get_average_CKA_per_layer.py:107-118):
+        one inference forward without the LM head, then one pooling launch.  out fp32 [2 (image, text), L, n, h] (allocated with
+        n = B if None); sample b lands in row rows[b] (default b).  The text mean is over the LAST sum(attention_mask[b]) positions,
+        the reference's literal rule (the same rows as the mask's under left padding); an empty text gives NaN."""
+        feats = patch_embeddings if patch_embeddings is not None else self.get_patch_embeddings(pixel_values)
+        cfg, dev = self.config, self.flat_params.device
+        input_ids = input_ids.to(dev, torch.int64).contiguous()
+        attention_mask = attention_mask.to(dev, torch.int64).contiguous()
+        B = input_ids.shape[0]
+        if out is None:
+            out = torch.empty((2, cfg.num_hidden_layers, B, cfg.hidden_size), dtype=torch.float32, device=dev)
+        if rows is not None:
+            rows = rows.to(dev, torch.int64).contiguous()
+        st = self._engine_forward(feats.to(dev).contiguous(), input_ids, attention_mask, None, True, train=False, skip_head=True)
+        ops.cka_pool(st["hidden"][1:], attention_mask, cfg.num_vision_tokens, out, rows)
+        return out
+
     # ---- greedy decode (SURVEY.md section 8f-3) -----------------------------------------------------------------------
     @torch.no_grad()
     def generate(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
@@ -614,7 +634,7 @@ class VLPythiaForCausalLM(nn.Module):
     # ---- engine ------------------------------------------------------------------------------------------------------
     def _engine_forward(self, feats, input_ids, attention_mask, labels, want_hidden, train, n_hidden: Optional[int] = None,
                         keep_qkv: bool = False, qkv_out: Optional[Sequence[torch.Tensor]] = None, label_rows_hint: Optional[int] = None,
-                        last_only: bool = False):
+                        last_only: bool = False, skip_head: bool = False):
         if not self.flat_params.is_cuda:
             raise RuntimeError("mafed_amd runs on the GPU only (no CPU fallback); move the model with .cuda()")
         pe, main_st = self._param_events, torch.cuda.current_stream()
@@ -690,6 +710,12 @@ class VLPythiaForCausalLM(nn.Module):
             lnl, _, _, _ = ops.layernorm_fwd(xl, self._p("gpt_neox.final_layer_norm.weight"), self._p("gpt_neox.final_layer_norm.bias"),
                                              None, None, cfg.layer_norm_eps, cd, save_stats=False)
             sv["logits"] = ops.gemm(lnl, w("embed_out.weight"), False, True).view(B, 1, cfg.vocab_size)
+            return sv
+        if skip_head:
+            # representation analysis: hidden_states[L] (the fp32 final-LN state) is the last thing anyone reads; no LM head, no loss
+            full, _, _, _ = ops.layernorm_fwd(x, self._p("gpt_neox.final_layer_norm.weight"), self._p("gpt_neox.final_layer_norm.bias"),
+                                              None, None, cfg.layer_norm_eps, torch.float32, save_stats=False)
+            hidden.append(full.view(B, S, h))
             return sv
         # final LN (fp32 hidden state L only when asked for) + LM head on the T text positions (vl_pythia.py:89,310)
         xt = x.view(B, S, h)[:, P:, :].reshape(B * T, h)

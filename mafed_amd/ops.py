@@ -11,6 +11,7 @@ import torch
 
 from mafed_amd import _lib
 import contextlib
+import ctypes as C
 import threading
 
 from mafed_amd._lib import BF16, EPI_GELU, EPI_GELU_BWD, EPI_NO_PERSISTENT, EPI_NONE, EPI_QUICK_GELU, EPI_RES1_BF16, EPI_TICKETED, F32, check  # noqa: F401
@@ -570,6 +571,59 @@ def ewc_penalty_bwd_(p: torch.Tensor, p_old: torch.Tensor, fisher: torch.Tensor,
     assert grad.dtype == torch.float32 and grad.shape == p.shape and coef.dtype == torch.float32
     check(_lib.load().mafed_ewc_penalty_bwd(_ptr(p), _ptr(p_old), _ptr(fisher), p.numel(), float(lam), _ptr(coef), _ptr(grad), _stream()),
           "mafed_ewc_penalty_bwd")
+
+
+def cka_pool(hidden: Sequence[torch.Tensor], attention_mask: torch.Tensor, P: int, out: torch.Tensor, rows: Optional[torch.Tensor] = None) -> None:
+    """out[0, l, rows[b]] = mean of hidden[l][b, :P]; out[1, l, rows[b]] = mean of the last sum(attention_mask[b]) rows of hidden[l][b]
+    (fp32 hidden states [B, S, h], text mask [B, T], out fp32 [2, L, n, h])."""
+    L = len(hidden)
+    B, S, h = hidden[0].shape
+    T = attention_mask.shape[1]
+    assert all(x.shape == (B, S, h) and x.dtype == torch.float32 and x.is_contiguous() for x in hidden)
+    assert attention_mask.dtype == torch.int64 and attention_mask.shape == (B, T) and attention_mask.is_contiguous()
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.dim() == 4 and out.shape[0] == 2 and out.shape[1] == L and out.shape[3] == h
+    if rows is not None:
+        assert rows.dtype == torch.int64 and rows.shape == (B,) and rows.is_contiguous()
+    ptrs = (C.c_void_p * L)(*[_ptr(x) for x in hidden])
+    check(_lib.load().mafed_cka_pool(ptrs, L, B, S, int(P), h, _ptr(attention_mask), T, _ptr(rows), out.shape[2], _ptr(out), _stream()),
+          "mafed_cka_pool")
+
+
+def cka_stats(X: torch.Tensor, row_norms: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """fp64 column means [G, h] and centred squared row norms [G, n] of G fp32 feature sets X [G, n, h] (or one set [n, h])."""
+    assert X.dtype == torch.float32 and X.dim() in (2, 3) and X.stride(-1) == 1
+    X3 = X if X.dim() == 3 else X.unsqueeze(0)
+    G, n, h = X3.shape
+    lib = _lib.load()
+    mean = torch.empty((G, h), dtype=torch.float64, device=X.device)
+    rsq = torch.empty((G, n), dtype=torch.float64, device=X.device) if row_norms else None
+    ws = workspace(X.device).get(lib.mafed_cka_stats_workspace_bytes(G, n, h))
+    check(lib.mafed_cka_stats(_ptr(X3), G, n, h, X3.stride(1), X3.stride(0), _ptr(mean), _ptr(rsq), _ptr(ws), ws.numel(), _stream()),
+          "mafed_cka_stats")
+    return mean, rsq
+
+
+def cka_hsic(products: Sequence[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[p] = ||(X - 1 mean_x^T)^T (Y - 1 mean_y^T)||_F^2 for every (X [n, hx], mean_x [hx], Y [n, hy], mean_y [hy]) in ``products``,
+    fp64 [len(products)]; passing the same tensors as X and Y makes a self term (upper-triangle tiles only)."""
+    descs = (_lib.CkaProduct * max(1, len(products)))()
+    dev = None
+    for i, (X, mx, Y, my) in enumerate(products):
+        assert X.dtype == torch.float32 and Y.dtype == torch.float32 and X.dim() == 2 and Y.dim() == 2 and X.shape[0] == Y.shape[0]
+        assert X.stride(1) == 1 and Y.stride(1) == 1
+        assert mx.dtype == torch.float64 and my.dtype == torch.float64 and mx.shape == (X.shape[1],) and my.shape == (Y.shape[1],)
+        assert mx.is_contiguous() and my.is_contiguous()
+        descs[i] = _lib.CkaProduct(_ptr(X), _ptr(mx), X.stride(0), X.shape[1], _ptr(Y), _ptr(my), Y.stride(0), Y.shape[1], X.shape[0])
+        dev = X.device
+    if out is None:
+        out = torch.empty(len(products), dtype=torch.float64, device=dev)
+    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == len(products)
+    if not products:
+        return out
+    lib = _lib.load()
+    ws = workspace(dev).get(lib.mafed_cka_hsic_workspace_bytes(descs, len(products)))
+    check(lib.mafed_cka_hsic(descs, len(products), _ptr(out), _ptr(ws), ws.numel(), _stream()), "mafed_cka_hsic")
+    return out
 
 
 def gradnorm_clip(g: torch.Tensor, max_norm: float, out2: Optional[torch.Tensor] = None) -> torch.Tensor:
