@@ -390,6 +390,17 @@ int mafed_adamw_step_partial_zero(float* p, float* g, float* m, float* v, int64_
                                   float eps, float weight_decay, int step, const float* clip_scale_dev, float grad_mul, void* p_bf16,
                                   int64_t zero_n, void* stream);
 
+/* torch.optim.Adam (coupled L2) on a flat segment, torch 2.x single-tensor rule: g' = g*gs + wd*p; m = b1*m + (1-b1)*g';
+ * v = b2*v + (1-b2)*g'^2; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps) -- eps AFTER the bias correction, decay in the
+ * gradient (unlike mafed_adamw_step).  gs = grad_mul * clip_dev[1]; a negative clip scale skips the step (p, m, v untouched).
+ * lr_dev / step / p_bf16 as in mafed_adamw_step; zero_n as in mafed_adamw_step_partial_zero (0 = g kept, n = all of g zeroed).  The betas
+ * are double (torch's and mafed_optim_advance's): 1 - beta is formed in double, and step > 0 gives the device advance's corrections. */
+int mafed_adam_step(float* p, float* g, float* m, float* v, int64_t n, const float* lr_dev, double beta1, double beta2, float eps,
+                    float weight_decay, int step, const float* clip_dev, float grad_mul, void* p_bf16, int64_t zero_n, void* stream);
+/* torch.optim.Adamax, same conventions: g' and m as in mafed_adam_step; u = max(b2*u, |g'| + eps); p -= lr/(1-b1^t) * m / u. */
+int mafed_adamax_step(float* p, float* g, float* m, float* u, int64_t n, const float* lr_dev, double beta1, double beta2, float eps,
+                      float weight_decay, int step, const float* clip_dev, float grad_mul, void* p_bf16, int64_t zero_n, void* stream);
+
 /* Device-resident schedule (mafed/optim/sched.py:34-48 + the bias corrections of adamw.py:94-97): state_dev[0] = number of
  * optimiser steps taken so far; increments it to t and writes hyper3_dev = {base_lr * lambda(t-1), 1-b1^t, sqrt(1-b2^t)}
  * (double precision inside) for mafed_adamw_step(step = 0).  total_steps <= 0 means a constant learning rate. */

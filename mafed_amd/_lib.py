@@ -86,6 +86,8 @@ SIGNATURES = {
     "mafed_adamw_step": (_i, [_p, _p, _p, _p, _l, _p, _f, _f, _f, _f, _i, _p, _f, _p, _p]),
     "mafed_adamw_step_zero_grad": (_i, [_p, _p, _p, _p, _l, _p, _f, _f, _f, _f, _i, _p, _f, _p, _p]),
     "mafed_adamw_step_partial_zero": (_i, [_p, _p, _p, _p, _l, _p, _f, _f, _f, _f, _i, _p, _f, _p, _l, _p]),
+    "mafed_adam_step": (_i, [_p, _p, _p, _p, _l, _p, _d, _d, _f, _f, _i, _p, _f, _p, _l, _p]),
+    "mafed_adamax_step": (_i, [_p, _p, _p, _p, _l, _p, _d, _d, _f, _f, _i, _p, _f, _p, _l, _p]),
     "mafed_distill_combine": (_i, [_p, _i, _p, _i, _f, _p, _p, _p, _p, _p, _p]),
     "mafed_optim_advance": (_i, [_p, _d, _l, _l, _d, _d, _p, _p]),
     "mafed_optim_advance_guarded": (_i, [_p, _d, _l, _l, _d, _d, _p, _p, _p]),

@@ -1,5 +1,6 @@
 // Flat-buffer optimiser kernels: global gradient L2 norm + clip scale (Lightning gradient_clip_val,
-// mafed/train.py:288) and HF-style AdamW (mafed/optim/adamw.py:86-111).  HBM-bound streaming, 16-byte accesses.
+// mafed/train.py:288), HF-style AdamW (mafed/optim/adamw.py:86-111) and torch.optim.Adam / Adamax (the other two choices of
+// configure_optimizers, vqa_cont_learner.py:71-128).  HBM-bound streaming, 16-byte accesses.
 #include "common.h"
 
 namespace mafed {
@@ -127,6 +128,92 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
     if (SHADOW) p_bf16[i] = f32_to_bf16(x);
     if (ZERO_G && i < zero_n) g[i] = 0.f;
   }
+}
+
+// torch.optim.Adam / Adamax single-tensor rules (the reference's optim = "adam" / "adamax"): coupled L2 decay enters the gradient,
+// eps is added after the bias correction.  One element; p, m and the second state s (v or u) in place.
+struct AdamL2Rule {
+  float beta1, beta2, omb1, omb2, eps, wd, step_size, inv_bc2_sqrt;   // omb = 1 - beta (rounded from double), step_size = lr / (1-b1^t),
+                                                                      // inv_bc2_sqrt = 1 / sqrt(1-b2^t)
+  __device__ __forceinline__ void operator()(float& p, float gk, float& m, float& s) const {
+    const float gd = gk + wd * p;
+    m = m * beta1 + omb1 * gd;
+    s = s * beta2 + omb2 * gd * gd;
+    p = p - step_size * (m / (sqrtf(s) * inv_bc2_sqrt + eps));
+  }
+};
+struct AdamaxRule {
+  float beta1, beta2, omb1, omb2, eps, wd, step_size, inv_bc2_sqrt;   // (omb2, inv_bc2_sqrt unused: the infinity norm is not corrected)
+  __device__ __forceinline__ void operator()(float& p, float gk, float& m, float& s) const {
+    const float gd = gk + wd * p;
+    m = m * beta1 + omb1 * gd;
+    s = fmaxf(s * beta2, fabsf(gd) + eps);
+    p = p - step_size * (m / s);
+  }
+};
+
+// The streaming pass of the rules above, shaped as adamw_kernel: 16-byte accesses, grid-stride loop, scalar tail for n % 4, the
+// device clip scale (negative = skipped step: p, m, s untouched, g still zeroed), the bf16 shadow write and g[0 .. zero_n) zeroed.
+template <class Rule, bool SHADOW, bool ZERO_G>
+__device__ __forceinline__ void adam_family_pass(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ s,
+                                                 int64_t n, const float* __restrict__ lr_dev, float beta1, float beta2, float omb1, float omb2,
+                                                 float eps, float wd, float bc1, float bc2_sqrt, const float* __restrict__ clip_dev, float grad_mul,
+                                                 bf16_t* __restrict__ p_bf16, int64_t zero_n) {
+  const int64_t zero4 = zero_n / 4;
+  const float lr = lr_dev[0];
+  if (bc1 <= 0.f) {  // {lr, 1-b1^t, sqrt(1-b2^t)} of this step in device memory (mafed_optim_advance)
+    bc1 = lr_dev[1];
+    bc2_sqrt = lr_dev[2];
+  }
+  const float clip = clip_dev ? clip_dev[1] : 1.0f;
+  const bool skip = clip < 0.f;
+  const float gs = grad_mul * clip;
+  const Rule rule{beta1, beta2, omb1, omb2, eps, wd, lr / bc1, 1.0f / bc2_sqrt};
+  const int64_t n4 = n / 4;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  if (skip) {
+    if (ZERO_G) {
+      for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4 && i < zero4; i += stride) store4(g + i * 4, make_float4(0.f, 0.f, 0.f, 0.f));
+      if (blockIdx.x == 0 && threadIdx.x < (n - n4 * 4) && n4 * 4 + threadIdx.x < zero_n) g[n4 * 4 + threadIdx.x] = 0.f;
+    }
+    return;
+  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    float4 pp = load4(p + i * 4), gg = load4(g + i * 4), mm = load4(m + i * 4), ss = load4(s + i * 4);
+    float* pa = &pp.x; float* ga = &gg.x; float* ma = &mm.x; float* sa = &ss.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) rule(pa[k], ga[k] * gs, ma[k], sa[k]);
+    store4(p + i * 4, pp); store4(m + i * 4, mm); store4(s + i * 4, ss);
+    if (SHADOW) store4(p_bf16 + i * 4, pp);
+    if (ZERO_G && i < zero4) store4(g + i * 4, make_float4(0.f, 0.f, 0.f, 0.f));
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n - n4 * 4)) {
+    const int64_t i = n4 * 4 + threadIdx.x;
+    float x = p[i], mk = m[i], sk = s[i];
+    rule(x, g[i] * gs, mk, sk);
+    p[i] = x; m[i] = mk; s[i] = sk;
+    if (SHADOW) p_bf16[i] = f32_to_bf16(x);
+    if (ZERO_G && i < zero_n) g[i] = 0.f;
+  }
+}
+
+// two kernels of their own (not one templated on the rule) so that traces and the in-library profile tell them apart
+template <bool SHADOW, bool ZERO_G>
+__global__ __launch_bounds__(256) void adam_l2_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                      float* __restrict__ v, int64_t n, const float* __restrict__ lr_dev, float beta1,
+                                                      float beta2, float omb1, float omb2, float eps, float wd, float bc1, float bc2_sqrt,
+                                                      const float* __restrict__ clip_dev, float grad_mul, bf16_t* __restrict__ p_bf16,
+                                                      int64_t zero_n) {
+  adam_family_pass<AdamL2Rule, SHADOW, ZERO_G>(p, g, m, v, n, lr_dev, beta1, beta2, omb1, omb2, eps, wd, bc1, bc2_sqrt, clip_dev, grad_mul, p_bf16, zero_n);
+}
+
+template <bool SHADOW, bool ZERO_G>
+__global__ __launch_bounds__(256) void adamax_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                     float* __restrict__ u, int64_t n, const float* __restrict__ lr_dev, float beta1,
+                                                     float beta2, float omb1, float omb2, float eps, float wd, float bc1, float bc2_sqrt,
+                                                     const float* __restrict__ clip_dev, float grad_mul, bf16_t* __restrict__ p_bf16,
+                                                     int64_t zero_n) {
+  adam_family_pass<AdamaxRule, SHADOW, ZERO_G>(p, g, m, u, n, lr_dev, beta1, beta2, omb1, omb2, eps, wd, bc1, bc2_sqrt, clip_dev, grad_mul, p_bf16, zero_n);
 }
 
 // One thread: advance the optimiser step counter and publish this step's scalars {lr, 1-b1^t, sqrt(1-b2^t)} in double
@@ -320,4 +407,57 @@ extern "C" int mafed_adamw_step_partial_zero(float* p, float* g, float* m, float
                                              float eps, float weight_decay, int step, const float* clip_dev, float grad_mul, void* p_bf16,
                                              int64_t zero_n, void* stream) {
   return adamw_impl(p, g, m, v, n, lr_dev, beta1, beta2, eps, weight_decay, step, clip_dev, grad_mul, p_bf16, zero_n, stream);
+}
+
+enum AdamRule { RULE_ADAM_L2 = 0, RULE_ADAMAX = 1 };
+
+static int adam_family_impl(AdamRule rule, const char* name, float* p, float* g, float* m, float* s, int64_t n, const float* lr_dev,
+                            double beta1, double beta2, float eps, float weight_decay, int step, const float* clip_dev, float grad_mul,
+                            void* p_bf16, int64_t zero_n, void* stream) {
+  MAFED_CHECK_ARG(p && g && m && s && lr_dev && n >= 0 && step >= 0, "%s: bad arguments", name);
+  MAFED_CHECK_ARG(zero_n >= 0 && zero_n <= n && (zero_n == n || zero_n % 4 == 0), "%s: zero_n must be 0 .. n and a multiple of 4 (or n)", name);
+  MAFED_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)s) & 15) == 0, "%s: buffers must be 16-byte aligned", name);
+  MAFED_CHECK_ARG(!p_bf16 || ((uintptr_t)p_bf16 & 7) == 0, "%s: p_bf16 must be 8-byte aligned", name);
+  MAFED_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.f && weight_decay >= 0.f,
+                  "%s: betas must be in [0, 1), eps and weight_decay >= 0", name);
+  if (n == 0) return MAFED_OK;
+  // the betas come in double, as torch's Python floats and mafed_optim_advance's: 1 - beta is formed before the rounding to fp32 (from
+  // fp32 betas, 1 - 0.999f is 1.3e-5 off).  step > 0: bias corrections in double on the host, the same numbers as the device advance's;
+  // step == 0: the kernel reads {lr, 1-b1^t, sqrt(1-b2^t)} from lr_dev[0..2]
+  const double bc1 = step > 0 ? 1.0 - pow(beta1, (double)step) : 0.0;
+  const double bc2 = step > 0 ? 1.0 - pow(beta2, (double)step) : 0.0;
+  hipStream_t st = as_stream(stream);
+  int64_t nb = cdiv(n / 4 + 1, 256);
+  if (nb > 4096) nb = 4096;
+  const double bytes = (double)n * (28.0 + (p_bf16 ? 2.0 : 0.0)) + (double)zero_n * 4.0;   // as adamw_impl
+  const bool zero_g = zero_n > 0;
+#define MAFED_ADAM_FAMILY(KERNEL, SH, ZG)                                                                                                \
+  launch(K_ADAMW, bytes, KERNEL<SH, ZG>, dim3((unsigned)nb), dim3(256), 0, st, p, g, m, s, n, lr_dev, (float)beta1, (float)beta2,          \
+         (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, (float)bc1, (float)sqrt(bc2), clip_dev, grad_mul, (bf16_t*)p_bf16, zero_n)
+#define MAFED_ADAM_FAMILY_ALL(KERNEL)                              \
+  if (p_bf16 && zero_g) MAFED_ADAM_FAMILY(KERNEL, true, true);     \
+  else if (p_bf16) MAFED_ADAM_FAMILY(KERNEL, true, false);         \
+  else if (zero_g) MAFED_ADAM_FAMILY(KERNEL, false, true);         \
+  else MAFED_ADAM_FAMILY(KERNEL, false, false)
+  if (rule == RULE_ADAM_L2) {
+    MAFED_ADAM_FAMILY_ALL(adam_l2_kernel);
+  } else {
+    MAFED_ADAM_FAMILY_ALL(adamax_kernel);
+  }
+#undef MAFED_ADAM_FAMILY_ALL
+#undef MAFED_ADAM_FAMILY
+  MAFED_CHECK_LAUNCH(name);
+  return MAFED_OK;
+}
+
+extern "C" int mafed_adam_step(float* p, float* g, float* m, float* v, int64_t n, const float* lr_dev, double beta1, double beta2, float eps,
+                               float weight_decay, int step, const float* clip_dev, float grad_mul, void* p_bf16, int64_t zero_n, void* stream) {
+  return adam_family_impl(RULE_ADAM_L2, "adam_step", p, g, m, v, n, lr_dev, beta1, beta2, eps, weight_decay, step, clip_dev, grad_mul, p_bf16,
+                          zero_n, stream);
+}
+
+extern "C" int mafed_adamax_step(float* p, float* g, float* m, float* u, int64_t n, const float* lr_dev, double beta1, double beta2, float eps,
+                                 float weight_decay, int step, const float* clip_dev, float grad_mul, void* p_bf16, int64_t zero_n, void* stream) {
+  return adam_family_impl(RULE_ADAMAX, "adamax_step", p, g, m, u, n, lr_dev, beta1, beta2, eps, weight_decay, step, clip_dev, grad_mul, p_bf16,
+                          zero_n, stream);
 }

@@ -704,6 +704,15 @@ def adamw_step_(p, g, m, v, lr_dev, beta1, beta2, eps, weight_decay, step, clip=
              int(step), _ptr(clip), float(grad_mul), _ptr(p_bf16), _stream()), "mafed_adamw_step")
 
 
+def adam_family_step_(rule: str, p, g, m, s, lr_dev, beta1, beta2, eps, weight_decay, step, clip=None, grad_mul=1.0, p_bf16=None,
+                      zero_n: int = 0) -> None:
+    """torch.optim.Adam (``rule="adam"``, ``s`` = exp_avg_sq) or Adamax (``rule="adamax"``, ``s`` = exp_inf) on one flat segment, same
+    conventions as ``adamw_step_``; ``zero_n``: the first ``zero_n`` elements of ``g`` are zeroed in the same pass (0 = none, numel = all)."""
+    fn = {"adam": "mafed_adam_step", "adamax": "mafed_adamax_step"}[rule]
+    check(getattr(_lib.load(), fn)(_ptr(p), _ptr(g), _ptr(m), _ptr(s), p.numel(), _ptr(lr_dev), float(beta1), float(beta2), eps, weight_decay, int(step),
+                                   _ptr(clip), float(grad_mul), _ptr(p_bf16), int(zero_n), _stream()), fn)
+
+
 def optim_advance_(state: torch.Tensor, base_lr: float, warmup: int, total: int, beta1: float, beta2: float, hyper: torch.Tensor,
                    clip: Optional[torch.Tensor] = None) -> None:
     """``clip`` = the {norm, scale} pair of this step's clip: a skipped step (scale < 0: non-finite norm) does not advance the counter."""

@@ -5,6 +5,9 @@ mafed/model/vqa_cont_learner.py:58-128) on the model's flat parameter / gradient
 decoupled decay applied after the update with the scheduled lr) as ONE kernel launch per weight-decay segment, with the
 global-norm clip scale (Lightning ``gradient_clip_val``, mafed/train.py:288) read from device memory -- the step never
 synchronises with the host.  The bf16 shadow weights used by the MFMA GEMMs are written by the same kernel.
+
+``FlatAdam`` / ``FlatAdamax`` = torch.optim.Adam / Adamax (the reference's other two ``optim`` choices, vqa_cont_learner.py:
+71-128) on the same buffers: everything but the per-segment update (``_segment_step``) is FlatAdamW's.
 """
 from __future__ import annotations
 
@@ -35,6 +38,9 @@ class FlatAdamW:
     names without ``bias`` are decayed (LayerNorm weights included), names with ``bias`` are not.
     (The ``vqa_output`` lr_mul groups of configure_optimizers are empty for VLPythia.)"""
 
+    OPTIM = "adamw"
+    STATE = ("exp_avg", "exp_avg_sq")   # names of the two per-parameter state buffers (torch's)
+
     def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-6, weight_decay: float = 0.0,
                  correct_bias: bool = True):
         if lr < 0.0:
@@ -51,8 +57,8 @@ class FlatAdamW:
         self.base_lr = lr
         self.betas, self.eps, self.weight_decay = tuple(betas), eps, weight_decay
         dev = model.flat_params.device
-        self.exp_avg = torch.zeros_like(model.flat_params)
-        self.exp_avg_sq = torch.zeros_like(model.flat_params)
+        for name in self.STATE:
+            setattr(self, name, torch.zeros_like(model.flat_params))
         # {lr, 1-b1^t, sqrt(1-b2^t)} of the current step and the step counter live on the DEVICE (mafed_optim_advance):
         # the optimiser kernels carry no per-step host constants, so a whole step replays from a hipGraph
         self.lr_dev = torch.tensor([lr, 1.0, 1.0], dtype=torch.float32, device=dev)
@@ -214,26 +220,30 @@ class FlatAdamW:
             lo, hi = grp["range"]
             if hi <= lo:
                 continue
-            shadow = m.flat_shadow[lo:hi] if m.flat_shadow is not None else None
-            ops.adamw_step_(m.flat_params[lo:hi], m.flat_grads[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], self.lr_dev,
-                            self.betas[0], self.betas[1], self.eps, grp["weight_decay"], 0, clip, grad_mul, shadow, zero_grad=zero_grads)
+            self._segment_step(lo, hi, grp["weight_decay"], clip, grad_mul, zero_grad=zero_grads)
         self._clip_pending = False
         if m.flat_shadow is not None:
             m._shadow_dirty = False
+
+    def _segment_step(self, lo: int, hi: int, wd: float, clip, grad_mul: float, zero_grad: bool, zero_n: Optional[int] = None) -> None:
+        """The update rule on flat range [lo, hi) with weight decay ``wd``: one launch, the bf16 shadow written and (``zero_grad``) the
+        gradient zeroed in the same pass -- all of it, or only its first ``zero_n`` elements."""
+        m = self.model
+        shadow = m.flat_shadow[lo:hi] if m.flat_shadow is not None else None
+        ops.adamw_step_(m.flat_params[lo:hi], m.flat_grads[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], self.lr_dev,
+                        self.betas[0], self.betas[1], self.eps, wd, 0, clip, grad_mul, shadow, zero_grad=zero_grad, zero_n=zero_n)
 
     def _apply_chunks(self, clip, grad_mul: float, skip_matrix_zero: bool = True, events: Optional[dict] = None, stream=None):
         """One AdamW launch per chunk of ``_chunks()`` on the current stream, the gradient zeroed in the same pass; a layer chunk zeroes only
         its LayerNorm-weight part when ``skip_matrix_zero`` (mafed_adamw_step_partial_zero)."""
         m = self.model
         for key, lo, hi, wd in self._chunks():
-            shadow = m.flat_shadow[lo:hi] if m.flat_shadow is not None else None
             zn = None
             if skip_matrix_zero and isinstance(key, tuple) and key[0] == "layer":
                 mlo, mhi = m.layer_matrix_range(key[1])
                 assert lo <= mlo and mhi == hi, "layer chunk = [LayerNorm weights | weight matrices]"
                 zn = mlo - lo
-            ops.adamw_step_(m.flat_params[lo:hi], m.flat_grads[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], self.lr_dev,
-                            self.betas[0], self.betas[1], self.eps, wd, 0, clip, grad_mul, shadow, zero_grad=True, zero_n=zn)
+            self._segment_step(lo, hi, wd, clip, grad_mul, zero_grad=True, zero_n=zn)
             if events is not None:
                 events[key] = stream.record_event()
         if skip_matrix_zero:
@@ -268,9 +278,7 @@ class FlatAdamW:
                 self._apply_chunks(clip, grad_mul, skip_matrix_zero=skip_matrix_zero, events=events, stream=stream)
             else:
                 for key, lo, hi, wd in self._chunks():
-                    shadow = m.flat_shadow[lo:hi] if m.flat_shadow is not None else None
-                    ops.adamw_step_(m.flat_params[lo:hi], m.flat_grads[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], self.lr_dev,
-                                    self.betas[0], self.betas[1], self.eps, wd, 0, clip, grad_mul, shadow, zero_grad=False)
+                    self._segment_step(lo, hi, wd, clip, grad_mul, zero_grad=False)
                     events[key] = stream.record_event()
         self._clip_pending = False
         if m.flat_shadow is not None:
@@ -278,14 +286,61 @@ class FlatAdamW:
         return events
 
     def state_dict(self):
-        return {"exp_avg": self.exp_avg, "exp_avg_sq": self.exp_avg_sq, "step": self.step_count, "sched": self._sched}
+        sd = {name: getattr(self, name) for name in self.STATE}
+        sd.update({"optim": self.OPTIM, "step": self.step_count, "sched": self._sched})
+        return sd
 
     def load_state_dict(self, sd):
-        self.exp_avg.copy_(sd["exp_avg"])
-        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        # (a dict without "optim" predates the other rules: it is AdamW's)
+        other = sd.get("optim", "adamw")
+        if other != self.OPTIM or any(name not in sd for name in self.STATE):
+            raise ValueError("%s cannot load the state of optimiser %r (keys %s)" % (type(self).__name__, other, sorted(sd)))
+        for name in self.STATE:
+            getattr(self, name).copy_(sd[name])
         self.step_count = int(sd["step"])
         self.state_dev.fill_(self.step_count)
         self._sched = tuple(sd.get("sched", self._sched))
+
+
+class _FlatTorchAdam(FlatAdamW):
+    """torch.optim.Adam-family rules on FlatAdamW's machinery (segments, device schedule, clip, chunked / pipelined passes): only the
+    per-segment update differs -- one mafed_adam_step / mafed_adamax_step launch."""
+
+    _RULE = ""
+
+    def __init__(self, model, lr: float, betas, eps: float, weight_decay: float):
+        if not 0.0 <= weight_decay:
+            raise ValueError("Invalid weight_decay value: {}".format(weight_decay))
+        super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+
+    def _segment_step(self, lo: int, hi: int, wd: float, clip, grad_mul: float, zero_grad: bool, zero_n: Optional[int] = None) -> None:
+        m = self.model
+        shadow = m.flat_shadow[lo:hi] if m.flat_shadow is not None else None
+        zn = 0 if not zero_grad else (hi - lo if zero_n is None else min(int(zero_n), hi - lo))
+        ops.adam_family_step_(self._RULE, m.flat_params[lo:hi], m.flat_grads[lo:hi], self.exp_avg[lo:hi], getattr(self, self.STATE[1])[lo:hi],
+                              self.lr_dev, self.betas[0], self.betas[1], self.eps, wd, 0, clip, grad_mul, shadow, zero_n=zn)
+
+
+class FlatAdam(_FlatTorchAdam):
+    """torch.optim.Adam (torch 2.x single-tensor rule; config.optim = "adam") over the two weight-decay segments: the decay is
+    coupled (L2, added to the gradient) and eps comes after the bias correction.  Defaults are torch's."""
+
+    OPTIM = _RULE = "adam"
+    STATE = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, model, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0):
+        super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+
+
+class FlatAdamax(_FlatTorchAdam):
+    """torch.optim.Adamax (config.optim = "adamax"): g' and m as for Adam, u = max(b2*u, |g'| + eps) in ``exp_inf``,
+    p -= lr/(1-b1^t) * m/u.  Defaults are torch's."""
+
+    OPTIM = _RULE = "adamax"
+    STATE = ("exp_avg", "exp_inf")
+
+    def __init__(self, model, lr: float = 2e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0):
+        super().__init__(model, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
 
 
 class LinearWarmupSchedule:

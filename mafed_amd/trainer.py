@@ -17,7 +17,10 @@ from typing import Any, Dict, Optional
 import torch
 
 from mafed_amd.dist import GradReducer
-from mafed_amd.optim import FlatAdamW, compute_warmup, get_linear_schedule_with_warmup
+from mafed_amd.optim import FlatAdam, FlatAdamax, FlatAdamW, compute_warmup, get_linear_schedule_with_warmup
+
+# config.optim -> optimiser (configure_optimizers, vqa_cont_learner.py:104-112)
+_OPTIMIZERS = {"adamw": FlatAdamW, "adam": FlatAdam, "adamax": FlatAdamax}
 
 
 import os as _os
@@ -39,10 +42,13 @@ class Trainer:
         self.replay_interval = int(getattr(cfg, "replay_interval", 4))
         self.grad_norm = float(getattr(cfg, "grad_norm", 2.0))
         optim_name = getattr(cfg, "optim", "adamw")
-        if optim_name != "adamw":
-            raise ValueError("invalid optimizer")  # vqa_cont_learner.py:111-112; only the scripts' AdamW is on the path
-        self.optimizer = FlatAdamW(model, lr=float(getattr(cfg, "learning_rate", 5e-5)), betas=tuple(getattr(cfg, "betas", (0.9, 0.98))),
-                                   weight_decay=float(getattr(cfg, "weight_decay", 0.01)))
+        optim_cls = _OPTIMIZERS.get(optim_name)
+        if optim_cls is None:
+            raise ValueError("invalid optimizer")  # vqa_cont_learner.py:111-112
+        # (eps only when configured: configure_optimizers passes none, so each rule runs with its own default)
+        eps = {"eps": float(cfg.eps)} if getattr(cfg, "eps", None) is not None else {}
+        self.optimizer = optim_cls(model, lr=float(getattr(cfg, "learning_rate", 5e-5)), betas=tuple(getattr(cfg, "betas", (0.9, 0.98))),
+                                   weight_decay=float(getattr(cfg, "weight_decay", 0.01)), **eps)
         total, warm = compute_warmup(n_batches_per_epoch, self.accumulate, float(getattr(cfg, "warmup_perc", 0.1)),
                                      getattr(cfg, "warmup_steps", None))
         total = int(getattr(cfg, "total_steps", total))
