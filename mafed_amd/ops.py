@@ -337,7 +337,7 @@ def decode_supported(M: int, h: int, n1: int) -> bool:
 
 
 def decode_ln_qkv_fc1(x: torch.Tensor, ln1_w, ln1_b, ln2_w, ln2_b, eps: float, wqkv: torch.Tensor, bqkv: torch.Tensor,
-                      qkv_row: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, a_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      qkv_row: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor) -> torch.Tensor:
     """Decode step, first launch of a layer: ``qkv_row[m] = LN1(x[m]) @ wqkv^T + bqkv`` (a strided [M, 3h] view: the cache row of this
     step) and ``a = gelu(LN2(x[m]) @ w1^T + b1)`` -> a [M, n1] bf16.  x fp32 [M, h]; weights bf16 [N, h]."""
     M, h = x.shape
@@ -345,8 +345,7 @@ def decode_ln_qkv_fc1(x: torch.Tensor, ln1_w, ln1_b, ln2_w, ln2_b, eps: float, w
     assert x.dtype == torch.float32 and x.is_contiguous() and wqkv.dtype == torch.bfloat16 and w1.dtype == torch.bfloat16
     assert wqkv.shape == (3 * h, h) and w1.shape[1] == h and wqkv.is_contiguous() and w1.is_contiguous()
     assert qkv_row.shape == (M, 3 * h) and qkv_row.dtype == torch.bfloat16 and qkv_row.stride(1) == 1
-    if a_out is None:
-        a_out = torch.empty((M, n1), dtype=torch.bfloat16, device=x.device)
+    a_out = torch.empty((M, n1), dtype=torch.bfloat16, device=x.device)
     check(_lib.load().mafed_decode_ln_qkv_fc1(_ptr(x), M, h, float(eps), _ptr(ln1_w), _ptr(ln1_b), _ptr(ln2_w), _ptr(ln2_b), _ptr(wqkv),
                                               _ptr(bqkv), _ptr(qkv_row), qkv_row.stride(0), _ptr(w1), _ptr(b1), n1, _ptr(a_out), _stream()),
           "mafed_decode_ln_qkv_fc1")
@@ -386,72 +385,6 @@ def decode_out(x: torch.Tensor, ao: torch.Tensor, act: torch.Tensor, wd: torch.T
     check(_lib.load().mafed_decode_out(_ptr(x), _ptr(out), M, h, n1, _ptr(ao), _ptr(act), _ptr(wd), _ptr(bd), _ptr(w2), _ptr(b2),
                                        _ptr(workspace), workspace.numel(), _stream()), "mafed_decode_out")
     return out
-
-
-class DecodeFlow:
-    """Buffers and the per-layer pointer table of the one-launch decode step (``mafed_decode_flow_step``) for one K/V cache."""
-
-    def __init__(self, layer_ptrs: Sequence[Sequence[torch.Tensor]], M: int, h: int, n1: int, H: int, D: int, V: int, device):
-        lib = _lib.load()
-        self.L = len(layer_ptrs) - 1
-        self.M, self.h, self.n1, self.H, self.D, self.V = M, h, n1, H, D, V
-        tab = [[0 if t is None else _ptr(t) for t in rec] for rec in layer_ptrs]
-        assert all(len(r) == 14 for r in tab)
-        self._keep = layer_ptrs                                   # the table holds raw addresses: keep the tensors alive
-        self.table = torch.tensor(tab, dtype=torch.int64).to(device)
-        z = lambda *s, dt=torch.bfloat16: torch.zeros(*s, dtype=dt, device=device)
-        self.x = z(32, h, dt=torch.float32)
-        self.ln1, self.ln2, self.ao, self.act = z(32, h), z(32, h), z(32, h), z(32, n1)
-        self.ws = torch.zeros(int(lib.mafed_decode_flow_workspace_bytes(h, n1)), dtype=torch.uint8, device=device)
-        self.flags = torch.zeros(int(lib.mafed_decode_flow_flag_bytes(self.L)) // 4, dtype=torch.int32, device=device)
-        self.logits = z(M, V)
-
-    def step(self, S0: int, cap: int, t: int, rot: int, P: int, cos, sin, attention_mask: torch.Tensor, eps: float) -> torch.Tensor:
-        """x (rows < M filled by the caller) -> logits [M, V] bf16 (a static buffer: consume before the next step)."""
-        self.flags.zero_()
-        check(_lib.load().mafed_decode_flow_step(_ptr(self.table), self.L, self.M, self.h, self.n1, self.H, self.D, S0, cap, t, rot, P,
-                                                 attention_mask.shape[1], self.V, float(eps), _ptr(self.x), _ptr(self.ln1), _ptr(self.ln2),
-                                                 _ptr(self.act), _ptr(self.ao), _ptr(self.ws), self.ws.numel(), _ptr(self.flags),
-                                                 self.flags.numel() * 4, _ptr(cos), _ptr(sin), _ptr(attention_mask), _ptr(self.logits), _stream()),
-              "mafed_decode_flow_step")
-        return self.logits
-
-    def timed_out(self) -> bool:
-        """Host check (synchronises): did a hand-over of the last step time out?"""
-        return bool(int(self.flags[-1].item()) != 0)
-
-
-class DecodeAttnOut:
-    """Second launch of every decode layer (``mafed_decode_attn_out``): pointer table, scratch rows and one counter slot per (layer, step)."""
-
-    def __init__(self, layer_ptrs: Sequence[Sequence[torch.Tensor]], M: int, h: int, n1: int, H: int, D: int, cap: int, device):
-        lib = _lib.load()
-        self.L, self.M, self.h, self.n1, self.H, self.D, self.cap = len(layer_ptrs), M, h, n1, H, D, cap
-        tab = [[0 if t is None else _ptr(t) for t in rec] for rec in layer_ptrs]
-        assert all(len(r) == 14 for r in tab)
-        self._keep = layer_ptrs                                   # raw addresses in the table: keep the tensors alive
-        self.table = torch.tensor(tab, dtype=torch.int64).to(device)
-        self.act = torch.zeros(32, n1, dtype=torch.bfloat16, device=device)      # first launch writes rows < M
-        self.ao = torch.zeros(32, h, dtype=torch.bfloat16, device=device)
-        self.ws = torch.zeros(int(lib.mafed_decode_flow_workspace_bytes(h, n1)), dtype=torch.uint8, device=device)
-        self.flags = torch.zeros(cap, self.L, 256, dtype=torch.int32, device=device)
-
-    def begin_step(self, t: int) -> None:
-        self.flags[t].zero_()     # the step's counter slots (a launch leaves them non-zero)
-
-    def run(self, i: int, t: int, x: torch.Tensor, S0: int, rot: int, P: int, cos, sin, attention_mask: torch.Tensor) -> None:
-        assert x.dtype == torch.float32 and x.is_contiguous() and x.shape == (self.M, self.h)
-        check(_lib.load().mafed_decode_attn_out(self.table.data_ptr() + i * 14 * 8, self.M, self.h, self.n1, self.H, self.D, S0, self.cap, t, rot, P,
-                                                attention_mask.shape[1], _ptr(x), _ptr(self.act), _ptr(self.ao), _ptr(self.ws), self.ws.numel(),
-                                                self.flags[t, i].data_ptr(), _ptr(cos), _ptr(sin), _ptr(attention_mask), _stream()),
-              "mafed_decode_attn_out")
-
-    def timed_out(self) -> bool:
-        return bool(int(self.flags[:, :, 255].abs().sum().item()) != 0)
-
-
-def decode_flow_supported(M: int, h: int, n1: int, H: int, D: int, V: int, nk: int) -> bool:
-    return bool(_lib.load().mafed_decode_flow_supported(int(M), int(h), int(n1), int(H), int(D), int(V), int(nk)))
 
 
 def embed_concat_fwd(image: torch.Tensor, embed_in: torch.Tensor, input_ids: torch.Tensor, B: int, P: int, T: int) -> torch.Tensor:

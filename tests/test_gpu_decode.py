@@ -302,118 +302,3 @@ def test_decode_ln_linear_equals_layernorm_then_head(M, h, N):
     bias = (0.1 * torch.randn(N, generator=g)).to(DEV)
     got_b = ops.decode_ln_linear(x, lw, lb, 1e-5, w, bias=bias)
     close(got_b.float(), got.float() + bias, 1e-2, "bias operand")
-
-
-# ---- the decode step as ONE launch (csrc/decode_flow.hip) ---------------------------------------------------------------------------
-def _flow_model(layers=3, P=64, seed=21):
-    from mafed_amd import VLPythiaConfig, VLPythiaForCausalLM
-    cfg = VLPythiaConfig(hidden_size=1024, num_hidden_layers=layers, num_attention_heads=16, intermediate_size=4096, num_vision_tokens=P)
-    return cfg, VLPythiaForCausalLM(cfg, compute_dtype=torch.bfloat16, device="cuda", seed=seed)
-
-
-@pytest.mark.timeout(300)
-@pytest.mark.parametrize("B,T,P", [(32, 12, 64), (5, 9, 40), (17, 32, 256)])
-def test_decode_flow_step_equals_the_three_launch_layers(B, T, P):
-    """One launch per step against the three-launch layers on the same cache state: logits of three consecutive steps, the rows the steps
-    append to every layer's K/V cache, no hand-over time-out, and the same bits when the step is repeated on a restored cache."""
-    from mafed_amd.model import _DecodeCache
-    cfg, model = _flow_model(P=P)
-    g = torch.Generator().manual_seed(B)
-    ids = torch.randint(1, cfg.vocab_size, (B, T), generator=g).to(DEV)
-    am = torch.ones(B, T, dtype=torch.int64)
-    if B > 1:
-        am[1, : T // 3] = 0
-        am[B - 1, : T // 2] = 0
-    am = am.to(DEV)
-    feats = torch.randn(B, P, cfg.vision_hidden_size, generator=g).to(torch.bfloat16).to(DEV)
-    NEW = 4
-
-    def caches():
-        st = model._engine_forward(feats, ids, am, None, False, train=False, keep_qkv=True)
-        pre = [l["qkv"] for l in st["layers"]]
-        model.flow_decode = True
-        c_flow = _DecodeCache(model, [p.clone() for p in pre], B, st["S"], NEW, am)
-        model.flow_decode = False
-        c_ref = _DecodeCache(model, [p.clone() for p in pre], B, st["S"], NEW, am)
-        model.flow_decode = True
-        return c_flow, c_ref
-
-    c_flow, c_ref = caches()
-    assert c_flow.flow is not None and c_ref.flow is None and c_ref.fused
-    tok = ids[:, -1].contiguous()
-    for t in range(3):
-        lf = model._engine_decode_step(tok, t, c_flow).float().clone()
-        assert not c_flow.flow.timed_out(), f"step {t}: a hand-over timed out"
-        lr = model._engine_decode_step(tok, t, c_ref).float()
-        close(lf, lr, 2e-2, f"step {t}: logits, one launch vs three per layer")
-        for i in range(cfg.num_hidden_layers):
-            close(c_flow.new[i][:, t, :].float(), c_ref.new[i][:, t, :].float(), 2e-2, f"step {t}, layer {i}: appended cache row")
-        assert torch.equal(lf.argmax(-1), lr.argmax(-1)) or float((lf.argmax(-1) == lr.argmax(-1)).float().mean()) > 0.9
-        tok = lr.argmax(-1)
-    # bit-identical from run to run (fixed summation orders, no float atomics): redo step 2 on both
-    again = model._engine_decode_step(tok * 0 + ids[:, 0], 2, c_flow).float().clone()
-    again2 = model._engine_decode_step(tok * 0 + ids[:, 0], 2, c_flow).float()
-    assert torch.equal(again, again2)
-
-
-@pytest.mark.timeout(300)
-def test_generate_410m_one_launch_decode_tracks_the_three_launch_layers():
-    """Full 24-layer stack, B = 8: generate() through the one-launch step (eager and replayed from the hipGraph) against the three-launch
-    layers."""
-    from mafed_amd import VLPythiaConfig, VLPythiaForCausalLM
-    cfg = VLPythiaConfig.preset("410m", num_vision_tokens=64)
-    model = VLPythiaForCausalLM(cfg, compute_dtype=torch.bfloat16, device="cuda", seed=11)
-    g = torch.Generator().manual_seed(5)
-    B, T = 8, 12
-    ids = torch.randint(1, cfg.vocab_size, (B, T), generator=g).to(DEV)
-    am = torch.ones(B, T, dtype=torch.int64)
-    am[1, :3] = 0
-    am = am.to(DEV)
-    feats = torch.randn(B, 64, cfg.vision_hidden_size, generator=g).to(torch.bfloat16).to(DEV)
-    kw = dict(input_ids=ids, attention_mask=am, patch_embeddings=feats, max_new_tokens=4, eos_token_id=None, use_cache=True)
-    model.flow_decode = True
-    out_f, st_f = model.generate(return_step_logits=True, **kw)
-    out_g = model.generate(use_graph=True, **kw)
-    model.flow_decode = False
-    out_s, st_s = model.generate(return_step_logits=True, **kw)
-    assert torch.equal(out_f, out_g), "graph replay and eager launches of the one-launch step pick the same tokens"
-    close(st_f[0], st_s[0], 1e-6, "prefill logits")
-    if torch.equal(out_f[:, T], out_s[:, T]):
-        close(st_f[1], st_s[1], 3e-2, "first cached step: one launch vs three per layer")
-
-
-@pytest.mark.timeout(300)
-@pytest.mark.parametrize("B,T,P", [(32, 12, 64), (5, 9, 40), (17, 32, 256)])
-def test_decode_two_launch_layers_equal_the_three_launch_layers(B, T, P):
-    """Attention + dense + fc2 + residuals as one grid behind the strip launch (mafed_decode_attn_out) against the three-launch layers on
-    the same cache state: logits of three steps, appended cache rows, no time-out, same bits when a step is repeated."""
-    from mafed_amd.model import _DecodeCache
-    cfg, model = _flow_model(P=P)
-    g = torch.Generator().manual_seed(B + 1)
-    ids = torch.randint(1, cfg.vocab_size, (B, T), generator=g).to(DEV)
-    am = torch.ones(B, T, dtype=torch.int64)
-    if B > 1:
-        am[1, : T // 3] = 0
-        am[B - 1, : T // 2] = 0
-    am = am.to(DEV)
-    feats = torch.randn(B, P, cfg.vision_hidden_size, generator=g).to(torch.bfloat16).to(DEV)
-    st = model._engine_forward(feats, ids, am, None, False, train=False, keep_qkv=True)
-    pre = [l["qkv"] for l in st["layers"]]
-    model.flow_decode, model.pair_decode = False, True
-    c_pair = _DecodeCache(model, [p.clone() for p in pre], B, st["S"], 4, am)
-    model.pair_decode = False
-    c_ref = _DecodeCache(model, [p.clone() for p in pre], B, st["S"], 4, am)
-    model.pair_decode = True
-    assert c_pair.pair is not None and c_ref.pair is None and c_ref.fused and c_ref.flow is None
-    tok = ids[:, -1].contiguous()
-    for t in range(3):
-        lp = model._engine_decode_step(tok, t, c_pair).float().clone()
-        assert not c_pair.pair.timed_out(), f"step {t}: a hand-over timed out"
-        lr = model._engine_decode_step(tok, t, c_ref).float()
-        close(lp, lr, 2e-2, f"step {t}: logits, two launches vs three per layer")
-        for i in range(cfg.num_hidden_layers):
-            close(c_pair.new[i][:, t, :].float(), c_ref.new[i][:, t, :].float(), 2e-2, f"step {t}, layer {i}: appended cache row")
-        tok = lr.argmax(-1)
-    again = model._engine_decode_step(ids[:, 0].contiguous(), 2, c_pair).float().clone()
-    again2 = model._engine_decode_step(ids[:, 0].contiguous(), 2, c_pair).float()
-    assert torch.equal(again, again2)

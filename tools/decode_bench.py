@@ -33,11 +33,9 @@ def run(use_cache, reps=5, use_graph=False):
 
 t_u, o_u = run(False)
 legs = {}
-for name, fused, flow, pair in (("six launches per layer", False, False, False),
-                                ("one launch per step (opt-in)", True, True, False), ("two launches per layer (opt-in)", True, False, True),
-                                ("three launches per layer", True, False, False)):
+for name, fused in (("six launches per layer", False), ("three launches per layer", True)):
     model._decode_graphs = {}
-    model.fused_decode, model.flow_decode, model.pair_decode = fused, flow, pair
+    model.fused_decode = fused
     t_eager, o_eager = run(True)
     t_graph, o_graph = run(True, use_graph=True)
     assert torch.equal(o_eager, o_graph), f"{name}: graph replay and eager launches must produce the same tokens"
@@ -86,11 +84,10 @@ def step_ms(fused: bool):
     return best, cache.fused
 
 
-for name, fused, flow, pair in (("three launches per layer", True, False, False), ("two launches per layer, opt-in", True, False, True),
-                                ("one launch per step, opt-in", True, True, False), ("six launches per layer", False, False, False)):
-    model.fused_decode, model.flow_decode, model.pair_decode = fused, flow, pair
+for name, fused in (("three launches per layer", True), ("six launches per layer", False)):
+    model.fused_decode = fused
     ms, was_fused = step_ms(fused)
     tot = wbytes + kv_bytes
     print(f"decode step ({name}): {ms:.3f} ms; weights {wbytes / 1e9:.2f} GB + K/V {kv_bytes / 1e9:.2f} GB "
           f"per step -> {tot / ms / 1e9:.2f} TB/s ({tot / ms / 1e9 / 8.0 * 100:.1f} % of 8 TB/s; weights alone {wbytes / ms / 1e9 / 8.0 * 100:.1f} %)")
-model.fused_decode, model.flow_decode, model.pair_decode = True, False, False
+model.fused_decode = True

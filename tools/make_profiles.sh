@@ -5,7 +5,7 @@
 #   bench_kernel_by_shape.csv  per (kernel, grid) launch statistics from the same trace
 #   timeline.txt               tools/trace_timeline.py on the same trace (overlap depth, per-queue mix, idle gaps)
 #   pmc_traffic.json           fabric-side bytes per GEMM launch, per shape, from FETCH_SIZE / WRITE_SIZE (separate --pmc passes)
-#   decode.txt, decode_kernel_stats.csv, decode_pmc.json, decode_flow_trace.txt   the validation decode (skip with SKIP_DECODE=1)
+#   decode.txt, decode_kernel_stats.csv, decode_pmc.json   the validation decode (skip with SKIP_DECODE=1)
 set -e
 OUT=gpurun_out/profiles_new
 mkdir -p $OUT
@@ -91,5 +91,4 @@ if [ "$SKIP_DECODE" != "1" ]; then
     echo; timeout -k 10 120 python3 tools/decode_ab_trace.py 2>/dev/null; echo; timeout -k 10 120 python3 tools/decode_out_trace.py 2>/dev/null; } > $OUT/decode.txt
   bash tools/decode_profile.sh gpurun_out/decode_prof > /dev/null 2>&1 && cp gpurun_out/decode_prof/decode_kernel_stats.csv $OUT/decode_kernel_stats.csv
   bash tools/decode_pmc.sh gpurun_out/decode_pmc > /dev/null 2>&1 && cp gpurun_out/decode_pmc/decode_pmc.json $OUT/decode_pmc.json
-  { timeout -k 10 120 python3 tools/decode_flow_trace.py 2>/dev/null; echo; timeout -k 10 120 python3 tools/decode_pair_trace.py 2>/dev/null; } > $OUT/decode_flow_trace.txt
 fi
