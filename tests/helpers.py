@@ -3,6 +3,7 @@ import os
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from oracle import vlpythia_ref as R
 
@@ -120,3 +121,175 @@ def clip_setup(name):
     sd = R.init_weights(cfg, seed=seed + 2, bias_std=0.02, ln_jitter=0.05)
     batch = R.make_batch(cfg, t["B"], lm["T"], seed=seed + 3, pad=True, n_answer=3)
     return cc, csd, pixels, cfg, sd, batch, g
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# scale-aware comparison and the fp64 distillation-only oracle (MAFED feature-distillation parity)
+# ---------------------------------------------------------------------------------------------------------------
+def _f64(x):
+    if isinstance(x, torch.Tensor):
+        return x.detach().cpu().double().numpy()
+    return np.asarray(x, np.float64)
+
+
+def rel_err(a, ref, scale=None):
+    """max|a - ref| / S with S = max|ref| (or max|scale| when given: a cancellation residue such as the column sum of a
+    weight gradient is judged against the tensor it was summed from).  A zero reference scale gives 0 when ``a`` is exactly
+    zero as well and inf otherwise."""
+    a, ref = _f64(a), _f64(ref)
+    assert a.shape == ref.shape, (a.shape, ref.shape)
+    if not a.size:
+        return 0.0
+    s = float(np.abs(_f64(ref if scale is None else scale)).max())
+    err = float(np.abs(a - ref).max())
+    if s == 0.0:
+        return 0.0 if err == 0.0 else float("inf")
+    return err / s
+
+
+def assert_rel_close(a, ref, rtol, what="", scale=None, atol0=0.0):
+    """err <= rtol * max|ref| (per tensor; ``scale`` as in rel_err).  A reference that is exactly zero must come out within
+    ``atol0`` (default: exactly zero).  Returns the measured relative error."""
+    a64, ref64 = _f64(a), _f64(ref)
+    assert a64.shape == ref64.shape, (what, a64.shape, ref64.shape)
+    s = float(np.abs(_f64(ref if scale is None else scale)).max()) if ref64.size else 0.0
+    err = float(np.abs(a64 - ref64).max()) if a64.size else 0.0
+    if s == 0.0:
+        print(f"[rel] {what}: zero reference, max|got| {err:.3e} (atol {atol0:.1e})")
+        assert err <= atol0, f"{what}: reference is exactly zero, got max |{err:.3e}| > {atol0:.1e}"
+        return 0.0
+    r = err / s
+    print(f"[rel] {what}: rel err {r:.3e} (bound {rtol:.1e})")
+    assert r <= rtol, f"{what}: max err {err:.3e} = {r:.3e} x max|ref| {s:.3g} > rtol {rtol:.1e}"
+    return r
+
+
+# Bounds of the distillation parity checks (tests/test_gpu_model.py, tests/test_gpu_kernels.py), each measured on an MI355X and
+# guarded on the CPU by tests/test_distill_guard.py: a mutated fp64 oracle (distillation_coeff x 1.01, lang/vision weights swapped,
+# one layer coefficient dropped, the first valid text token classed as pad) must fail every check it applies to.
+# (measured worst case on gfx950 in brackets)
+DISTILL_RTOL = 2e-5           # fp32 native distillation-only step vs fp64 oracle: loss, per-layer lang/vision losses, every gradient [3.5e-6]
+DISTILL_RTOL_INJECT = 1e-3    # native grad(replay + 10x distillation) - grad(replay only) vs 10x the fp64 distillation-only gradient
+#                               [3.5e-3 at 1x: the fp32 rounding of the CE gradient, 1e3 times larger, sets the floor; 10x lifts the term above it]
+DISTILL_RTOL_BF16 = 5e-2      # bf16 step at production width vs fp64 oracle (loss and gradients) [1.3e-2]
+KERNEL_RTOL = 2e-5            # distill_fwd / distill_bwd / distill_combine vs fp64 [6.2e-6]
+LN_INJECT_RTOL = 1e-4         # LayerNorm-backward injection dx(with) - dx(without) vs fp64 [1.1e-5]
+GUARD_MARGIN = 3.0            # each mutation must exceed its bound by this factor
+
+
+def distill_variant_cases():
+    """(config, variant) pairs of G3_VARIANTS that distil at least one layer (cumulative needs L >= 3)."""
+    return [(n, v) for n in ("t64", "m64", "t128", "t256") for v in G3_VARIANTS
+            if not (G3_VARIANTS[v]["layer_strategy"] == "cumulative" and TINY[n]["L"] < 3)]
+
+
+def distill_only_fp64(cfg, sd, tsd, batch, spec):
+    """fp64 oracle of the distillation term alone (replay_coeff = 0): {"loss", "modality" [nl, 2] or None, "grads" {name: tensor}}.
+    Parameters that the distillation term does not reach get an exact zero gradient."""
+    import dataclasses
+    spec = dataclasses.replace(spec, replay_coeff=0.0)
+    params = {k: v.double().clone().requires_grad_(True) for k, v in sd.items()}
+    tp = {k: v.double() for k, v in tsd.items()}
+    b64 = dict(batch)
+    b64["patch_embeddings"] = batch["patch_embeddings"].double()
+    loss, _, per_layer = R.mafed_replay_loss(params, tp, b64, cfg, spec, task_id=1)
+    loss.backward()
+    layers = sorted(per_layer)
+    modality = None if spec.cls else torch.stack([torch.stack([per_layer[l]["lang"], per_layer[l]["vision"]]) for l in layers]).detach()
+    grads = {k: (p.grad.detach().clone() if p.grad is not None else torch.zeros_like(p.detach())) for k, p in params.items()}
+    return {"loss": float(loss.detach()), "modality": modality, "grads": grads}
+
+
+def distill_parity_errors(got, ref):
+    """{quantity: relative error (rel_err)} of ``got`` (layout of distill_only_fp64) against ``ref``: the loss, each layer's lang
+    and vision loss, every parameter gradient tensor."""
+    errs = {"loss": rel_err(got["loss"], ref["loss"])}
+    if ref["modality"] is not None and got.get("modality") is not None:
+        m, rm = _f64(got["modality"]).reshape(-1, 2), _f64(ref["modality"])
+        assert m.shape == rm.shape, (m.shape, rm.shape)
+        for l in range(rm.shape[0]):
+            for j, mod in enumerate(("lang", "vision")):
+                errs[f"layer {l} {mod} loss"] = rel_err(m[l, j], rm[l, j])
+    for k in ref["grads"]:
+        errs[f"grad {k}"] = rel_err(got["grads"][k], ref["grads"][k])
+    return errs
+
+
+def check_distill_parity(got, ref, rtol, what=""):
+    """Every quantity of distill_parity_errors within rtol (exact zeros where the reference is exactly zero).  Returns the largest."""
+    errs = distill_parity_errors(got, ref)
+    worst = max(errs, key=errs.get)
+    print(f"[rel] {what}: worst {worst} {errs[worst]:.3e} (bound {rtol:.1e}); loss {errs['loss']:.3e}")
+    bad = {k: v for k, v in errs.items() if not v <= rtol}
+    assert not bad, f"{what}: relative errors above {rtol:.1e}: " + ", ".join(f"{k} {v:.3e}" for k, v in bad.items())
+    return errs[worst]
+
+
+PROD_DISTILL = dict(h=1024, H=16, L=3, V=512, P=256, T=32, B=4, Dv=64)
+
+
+def prod_case(seed=77):
+    """(cfg, student / teacher weights, batch, spec, fp64 distillation-only oracle) of the production-width distillation check.
+    Left padding from make_batch; sample 3 has all of its text padded.  Equal modality weights, discounted layers (gamma 0.9)."""
+    t = PROD_DISTILL
+    cfg = R.RefConfig(vocab_size=t["V"], hidden_size=t["h"], num_hidden_layers=t["L"], num_attention_heads=t["H"],
+                      intermediate_size=4 * t["h"], vision_hidden_size=t["Dv"], num_vision_tokens=t["P"])
+    sd = R.init_weights(cfg, seed=seed, bias_std=0.02, ln_jitter=0.05)
+    tsd = R.perturb(sd, seed=seed + 1, std=5e-3)
+    batch = R.make_batch(cfg, t["B"], t["T"], seed=seed + 2, pad=True, n_answer=3)
+    batch["attention_mask"][3] = 0
+    batch["input_ids"][3] = 0
+    batch["labels"][3] = -100
+    spec = R.DistillSpec(distillation_coeff=1.5, replay_coeff=0.0, modality="equal", layer_strategy="discounted", gamma=0.9)
+    return dict(cfg=cfg, sd=sd, tsd=tsd, batch=batch, spec=spec, ref=distill_only_fp64(cfg, sd, tsd, batch, spec))
+
+
+# fp64 restatements of the distillation kernels (tests/test_gpu_kernels.py; mutated by tests/test_distill_guard.py)
+def distill_rows_fp64(s, t, attention_mask, P, coef, cosine):
+    """mafed_distill_fwd / mafed_distill_bwd in float64 from the oracle's masks: (sums [lang_sum, vision_sum, n_lang, n_vision],
+    ds = d(coef[0] * lang_sum + coef[1] * vision_sum) / ds)."""
+    B, S, h = s.shape
+    lang, img = R.modality_masks(attention_mask, P)
+    lang, img = lang.reshape(-1).double(), img.reshape(-1).double()
+    a, b = s.reshape(-1, h).double().requires_grad_(True), t.reshape(-1, h).double()
+    if cosine:
+        d = F.cosine_embedding_loss(a, b, torch.ones(a.shape[0], dtype=torch.float64), reduction="none")
+    else:
+        d = ((a - b) ** 2).sum(-1) / h
+    ls, vs = (d * lang).sum(), (d * img).sum()
+    c = [float(x) for x in coef]
+    (c[0] * ls + c[1] * vs).backward()
+    sums = torch.stack([ls.detach(), vs.detach(), lang.sum(), img.sum()])
+    return sums, a.grad.view(B, S, h)
+
+
+def ln_injection_fp64(x, t, attention_mask, S, P, scales, inj_mul):
+    """The distillation gradient the LayerNorm backward adds to dx (mafed_layernorm_bwd, teacher != NULL), float64:
+    inj_mul > 0: inj_mul * scale[class] * (x - t); inj_mul < 0: |inj_mul| * scale[class] * d/dx (1 - cos(x, t))."""
+    rows, h = x.shape
+    lang, img = R.modality_masks(attention_mask, P)
+    w = abs(inj_mul) * (float(scales[0]) * lang.reshape(-1).double() + float(scales[1]) * img.reshape(-1).double())
+    xd, td = x.double().requires_grad_(True), t.double()
+    if inj_mul < 0:
+        d = F.cosine_embedding_loss(xd, td, torch.ones(rows, dtype=torch.float64), reduction="none")
+    else:
+        d = 0.5 * ((xd - td) ** 2).sum(-1)
+    (w * d).sum().backward()
+    return xd.grad
+
+
+def distill_combine_fp64(sums, layer_coeff, mode, lang_weight=0.5, lang_vec=None):
+    """mafed_distill_combine in float64: (loss, per_layer [nl], modality [nl, 2], inject [nl, 4])."""
+    s = sums.double()
+    c = layer_coeff.double()
+    lang, vis = s[:, 0] / s[:, 2], s[:, 1] / s[:, 3]
+    if mode == 0:
+        lw = (s[0, 2] / (s[0, 2] + s[0, 3])).expand_as(lang)
+    elif mode == 1:
+        lw = torch.full_like(lang, float(lang_weight))
+    else:
+        lw = lang_vec.double()
+    vw = 1.0 - lw
+    per_layer = lw * lang + vw * vis
+    inject = torch.stack([c * lw / s[:, 2], c * vw / s[:, 3], torch.zeros_like(c), torch.zeros_like(c)], dim=1)
+    return (c * per_layer).sum(), per_layer, torch.stack([lang, vis], dim=1), inject

@@ -8,6 +8,8 @@ import torch
 import torch.nn.functional as F
 
 from oracle import vlpythia_ref as R
+from tests.helpers import (KERNEL_RTOL, LN_INJECT_RTOL, assert_rel_close, distill_combine_fp64, distill_rows_fp64,
+                           ln_injection_fp64)
 
 pytestmark = pytest.mark.gpu
 
@@ -477,10 +479,13 @@ def test_distill(cosine):
     out = ops.distill_fwd(D(s), D(t), D(am), P, cosine)
     assert_close(out[0] / out[2], ll, 1e-5, "lang")
     assert_close(out[1] / out[3], vl, 1e-5, "vision")
+    assert_rel_close(out[0] / out[2], ll, KERNEL_RTOL, "lang")
+    assert_rel_close(out[1] / out[3], vl, KERNEL_RTOL, "vision")
     assert float(out[2]) == float(lang.sum()) and float(out[3]) == float(img.sum())
     coef = torch.tensor([0.3 / float(lang.sum()), 1.1 / float(img.sum())], device=DEV)
     ds = ops.distill_bwd(D(s), D(t), D(am), P, coef, cosine)
     assert_close(ds, sd.grad, 1e-5, "ds")
+    assert_rel_close(ds, sd.grad, KERNEL_RTOL, "ds")
     base = torch.ones(B, S, h, device=DEV)
     ops.distill_bwd(D(s), D(t), D(am), P, coef, cosine, out=base, accumulate=True)
     assert_close(base, sd.grad + 1.0, 1e-5, "ds accumulate")
@@ -492,6 +497,124 @@ def test_distill(cosine):
     assert_close(o.reshape(()), ref, 1e-5, "cls")
     dsc = ops.distill_cls_bwd(D(s), D(t), torch.tensor([1.0 / B], device=DEV))
     assert_close(dsc, sd2.grad, 1e-5, "cls grad")
+
+
+def _padded_mask(B, T, g):
+    """Left padding of random length; sample 0 keeps all of its text, sample B // 2 has all of it padded."""
+    am = torch.ones(B, T, dtype=torch.int64)
+    for b in range(1, B):
+        am[b, : int(torch.randint(0, T, (1,), generator=g))] = 0
+    am[B // 2] = 0
+    return am
+
+
+@pytest.mark.parametrize("cosine", [False, True])
+@pytest.mark.parametrize("h", [768, 1024, 2048])
+def test_distill_production_rows(h, cosine):
+    """B 32 x S 288 = 9216 rows: more than the 1024-block cap of distill_fwd (grid stride), 1-2 trips of row_stats' 1024-column
+    step, a sample with all text padded; sums and ds against fp64, relative to their own scale."""
+    ops = _ops()
+    g = torch.Generator().manual_seed(h + int(cosine))
+    B, P, T = 32, 256, 32
+    S = P + T
+    s = torch.randn(B, S, h, generator=g)
+    t = s + 0.05 * torch.randn(B, S, h, generator=g)
+    am = _padded_mask(B, T, g)
+    lang, img = R.modality_masks(am, P)
+    nl, nv = float(lang.sum()), float(img.sum())
+    coef = torch.tensor([0.75 * 0.5 / nl, 0.75 * 0.5 / nv])
+    ref_sums, ref_ds = distill_rows_fp64(s, t, am, P, coef, cosine)
+    D = lambda v: v.to(DEV)
+    out = ops.distill_fwd(D(s), D(t), D(am), P, cosine).cpu()
+    assert float(out[2]) == nl and float(out[3]) == nv
+    assert_rel_close(out[0], ref_sums[0], KERNEL_RTOL, "lang sum")
+    assert_rel_close(out[1], ref_sums[1], KERNEL_RTOL, "vision sum")
+    ds = ops.distill_bwd(D(s), D(t), D(am), P, D(coef), cosine).cpu()
+    assert_rel_close(ds, ref_ds, KERNEL_RTOL, "ds")
+    assert float(ds[B // 2, P:].abs().max()) == 0.0  # padded text rows: exact zeros
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("nl", [3, 70])
+def test_distill_combine(mode, nl):
+    """The one launch that turns the per-layer sums into the loss, per-layer and per-modality values and the injection coefficients
+    (nl = 70 strides layers over the wave's lanes), against an fp64 restatement."""
+    ops = _ops()
+    g = torch.Generator().manual_seed(3 * nl + mode)
+    n_lang, n_vis = 731.0, 8192.0
+    sums = torch.stack([torch.rand(nl, generator=g) * 3 + 0.1, torch.rand(nl, generator=g) * 5 + 0.1,
+                        torch.full((nl,), n_lang), torch.full((nl,), n_vis)], dim=1).contiguous()
+    coeff = torch.rand(nl, generator=g) + 0.05
+    vec = torch.rand(nl, generator=g)
+    D = lambda v: v.to(DEV)
+    loss, per_layer, modality, inject = ops.distill_combine(D(sums), D(coeff), mode, 0.3, D(vec) if mode == 2 else None)
+    rl, rp, rm, ri = distill_combine_fp64(sums, coeff, mode, 0.3, vec)
+    assert_rel_close(loss.reshape(()), rl, KERNEL_RTOL, "loss")
+    assert_rel_close(per_layer, rp, KERNEL_RTOL, "per-layer")
+    assert_rel_close(modality[:, 0], rm[:, 0], KERNEL_RTOL, "lang")
+    assert_rel_close(modality[:, 1], rm[:, 1], KERNEL_RTOL, "vision")
+    assert_rel_close(inject[:, 0], ri[:, 0], KERNEL_RTOL, "lang injection coefficient")
+    assert_rel_close(inject[:, 1], ri[:, 1], KERNEL_RTOL, "vision injection coefficient")
+    assert_rel_close(inject[:, 2:], ri[:, 2:], KERNEL_RTOL, "unused injection slots")
+
+
+@pytest.mark.parametrize("cosine", [False, True])
+@pytest.mark.parametrize("h", [768, 1024, 2048])
+def test_layernorm_bwd_step_configuration(h, cosine):
+    """The LayerNorm backward as the training step runs it: bf16 dY into both LayerNorms, the residual gradient, the bf16 copy of
+    dx, DXSUM, and the distillation injection (MSE at inj_mul = 2/h, cosine at inj_mul < 0), at 9216 rows, split into
+    layernorm_bwd_rows + layernorm_bwd_params.  The injection is checked as dx(with) - dx(without) against fp64, relative to its
+    own size; the split form must give the one-launch form's bits."""
+    ops = _ops()
+    g = torch.Generator().manual_seed(2 * h + int(cosine))
+    B, P, T = 32, 256, 32
+    S = P + T
+    rows = B * S
+    x = torch.randn(rows, h, generator=g) * 1.5 + 0.2
+    t = x + 0.05 * torch.randn(rows, h, generator=g)
+    w1, w2 = 1 + 0.1 * torch.randn(h, generator=g), 1 + 0.1 * torch.randn(h, generator=g)
+    b1, b2 = 0.1 * torch.randn(h, generator=g), 0.1 * torch.randn(h, generator=g)
+    dy1 = (0.02 * torch.randn(rows, h, generator=g)).to(torch.bfloat16)
+    dy2 = (0.02 * torch.randn(rows, h, generator=g)).to(torch.bfloat16)
+    dres = 0.02 * torch.randn(rows, h, generator=g)
+    am = _padded_mask(B, T, g)
+    inj_mul = -1.0 if cosine else 2.0 / h
+    # injection a few 1e-3 of dx (the cosine gradient of t = x + small noise is nearly orthogonal to x and much smaller per unit scale)
+    scales = torch.tensor([0.7, 0.4]) * (0.3 * math.sqrt(h) if cosine else 2e-3 * h)
+    D = lambda v: v.to(DEV)
+    _, _, mean, rstd = ops.layernorm_fwd(D(x), D(w1), D(b1), D(w2), D(b2), 1e-5, torch.float32)
+    inj_kw = dict(teacher=D(t), attention_mask=D(am), S=S, P=P, inj_scale=D(scales), inj_mul=inj_mul)
+
+    def split(**kw):
+        dx, dx_lp, ws = ops.layernorm_bwd_rows(D(dy1), D(dy2), D(x), mean, rstd, D(w1), D(w2), D(dres), want_lp=True, want_dxsum=True, **kw)
+        grads = [torch.zeros(h, device=DEV) for _ in range(6)]
+        ops.layernorm_bwd_params(ws, rows, h, *grads)
+        return dx, dx_lp, grads
+
+    dx, dx_lp, grads = split(**inj_kw)
+    dx0, _, _ = split()
+    one = [torch.zeros(h, device=DEV) for _ in range(6)]
+    dx1, dx1_lp = ops.layernorm_bwd(D(dy1), D(dy2), D(x), mean, rstd, D(w1), D(w2), D(dres), *one[:4], want_lp=True,
+                                    dxsum_a=one[4], dxsum_b=one[5], **inj_kw)
+    assert torch.equal(dx, dx1) and torch.equal(dx_lp, dx1_lp), "rows + params != one launch (dx)"
+    for a, b in zip(grads, one):
+        assert torch.equal(a, b), "rows + params != one launch (parameter / dxsum gradients)"
+    assert torch.equal(dx_lp, dx.to(torch.bfloat16))
+    # fp64 reference: both LayerNorms + residual, then the injection on top
+    xd = x.double().requires_grad_(True)
+    w1d, b1d, w2d, b2d = (v.double().requires_grad_(True) for v in (w1, b1, w2, b2))
+    tot = ((F.layer_norm(xd, (h,), w1d, b1d, 1e-5) * dy1.double()).sum() + (F.layer_norm(xd, (h,), w2d, b2d, 1e-5) * dy2.double()).sum()
+           + (xd * dres.double()).sum())
+    tot.backward()
+    inj = ln_injection_fp64(x, t, am, S, P, scales, inj_mul)
+    ref_dx = xd.grad + inj
+    print(f"injection / dx: {float(inj.abs().max() / xd.grad.abs().max()):.2e}")
+    assert_rel_close(dx.cpu() - dx0.cpu(), inj, LN_INJECT_RTOL, "injection dx(with) - dx(without)")
+    assert float((dx - dx0).view(B, S, h)[B // 2, P:].abs().max()) == 0.0  # padded text rows: no injection
+    assert_rel_close(dx, ref_dx, 1e-5, "dx")
+    for got, ref, what in zip(grads, (w1d.grad, b1d.grad, w2d.grad, b2d.grad, ref_dx.sum(0), ref_dx.sum(0)),
+                              ("dw1", "db1", "dw2", "db2", "dxsum_a", "dxsum_b")):
+        assert_rel_close(got, ref, 1e-5, what)
 
 
 def test_optimizer_kernels_against_reference_fixture():

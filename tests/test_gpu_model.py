@@ -7,7 +7,8 @@ import pytest
 import torch
 
 from oracle import vlpythia_ref as R
-from tests.helpers import G3_VARIANTS, TINY, g3_spec, golden_setup, load_golden, tiny_cfg
+from tests.helpers import (DISTILL_RTOL, DISTILL_RTOL_BF16, DISTILL_RTOL_INJECT, G3_VARIANTS, TINY, check_distill_parity,
+                           distill_only_fp64, distill_variant_cases, g3_spec, golden_setup, load_golden, prod_case, tiny_cfg)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -82,8 +83,11 @@ def test_forward_backward_vs_reference_golden(name):
 
 
 def make_fd(cfg, vname, g, teacher_model, batch, B):
+    return make_fd_spec(cfg, g3_spec(vname, cfg, g), teacher_model, B)
+
+
+def make_fd_spec(cfg, spec, teacher_model, B):
     from mafed_amd import FeatureDistillation
-    spec = g3_spec(vname, cfg, g)
     opts = types.SimpleNamespace(tasks=["a", "b", "c"], batch_size=B, seed=42, pin_mem=False, accumulate_grad_batches=1)
     fd = FeatureDistillation(memory_size=100, opts=opts, model_type="vlpythia", num_hidden_layers=cfg.num_hidden_layers - 1,
                              distillation_coeff=spec.distillation_coeff, replay_coeff=spec.replay_coeff,
@@ -156,6 +160,90 @@ def test_mafed_fused_and_generic_distillation_paths(fused, replay_coeff, vname, 
     names, norms = grad_norms(model, cfg)
     refn = np.array([float(params[k].grad.norm()) if params[k].grad is not None else 0.0 for k in names])
     close(norms, refn, TOL, "grad norms")
+
+
+_FP64_DISTILL = {}
+
+
+def fp64_distill(name, vname):
+    """fp64 distillation-only oracle of a golden (config, variant), computed once and shared by both distillation paths."""
+    if (name, vname) not in _FP64_DISTILL:
+        cfg, sd, tsd, batch, g = golden_setup(name)
+        _FP64_DISTILL[(name, vname)] = distill_only_fp64(cfg, sd, tsd, batch, g3_spec(vname, cfg, g))
+    return _FP64_DISTILL[(name, vname)]
+
+
+def run_native_replay(model, fd, batch, cfg, replay_coeff, distillation_coeff):
+    """One FeatureDistillation.replay + backward -> {"loss", "modality", "grads"} in the layout of distill_only_fp64."""
+    fd.replay_coeff, fd.distillation_coeff = replay_coeff, distillation_coeff
+    fd.last_modality_losses = None
+    fd.mem_dataloader = [to_dev(batch)]
+    model.zero_grad()
+    loss, _ = fd.replay(model)
+    loss.backward()
+    mod = fd.last_modality_losses
+    names = [k for k, _ in R.param_shapes(cfg)]
+    return {"loss": float(loss), "modality": None if mod is None else mod.detach().double().cpu(),
+            "grads": {k: model._g(k).detach().double().cpu() for k in names}}
+
+
+INJECT_BOOST = 10.0  # distillation_coeff multiplier of the combined-loss check (tests/helpers.py: DISTILL_RTOL_INJECT)
+
+
+def check_injection(full, ce, ref, rtol, what):
+    """grad(replay + INJECT_BOOST x distillation) - grad(replay only), on the same batch, against INJECT_BOOST x the fp64
+    distillation-only gradient, relative to that gradient's own scale: the injection while the CE gradient shares the backward.
+    (At 1x the fp32 rounding of the CE gradient, about 1e3 times larger than the distillation gradient, leaves residues of 3.5e-3
+    of it; the term is linear in its coefficient.  The loss is not differenced for the same reason: the distillation-only run
+    checks it.)"""
+    diff = {"loss": INJECT_BOOST * ref["loss"], "modality": full["modality"],
+            "grads": {k: full["grads"][k] - ce["grads"][k] for k in full["grads"]}}
+    boosted = {"loss": INJECT_BOOST * ref["loss"], "modality": ref["modality"], "grads": {k: INJECT_BOOST * v for k, v in ref["grads"].items()}}
+    return check_distill_parity(diff, boosted, rtol, what)
+
+
+@pytest.mark.parametrize("fused", [True, False])
+@pytest.mark.parametrize("name,vname", distill_variant_cases())
+def test_mafed_distillation_only_vs_fp64_oracle(name, vname, fused):
+    """The distillation term alone (replay_coeff = 0) against the oracle in float64, every quantity relative to its own scale:
+    the loss, each layer's lang / vision loss and every parameter gradient tensor (exact zeros where the term does not reach).
+    Then the injection inside the combined step: grad at replay_coeff 0.7 minus grad with distillation_coeff 0 (check_injection)."""
+    cfg, sd, tsd, batch, g = golden_setup(name)
+    ref = fp64_distill(name, vname)
+    model, teacher = build_model(cfg, sd), build_model(cfg, tsd)
+    fd, spec = make_fd(cfg, vname, g, teacher, batch, batch["input_ids"].shape[0])
+    fd.fused_distill = fused
+    what = f"{name}/{vname}/{'fused' if fused else 'generic'}"
+    got = run_native_replay(model, fd, batch, cfg, 0.0, spec.distillation_coeff)
+    check_distill_parity(got, ref, DISTILL_RTOL, what)
+    full = run_native_replay(model, fd, batch, cfg, 0.7, INJECT_BOOST * spec.distillation_coeff)
+    ce = run_native_replay(model, fd, batch, cfg, 0.7, 0.0)
+    check_injection(full, ce, ref, DISTILL_RTOL_INJECT, what + " (with CE)")
+
+
+_PROD = {}
+
+
+def prod_setup():
+    """Production-width distillation case: h 1024, 16 heads, 3 layers, 256 image + 32 text tokens, B 4 with left padding and one
+    sample whose text is all padding (shared by the fp32 and bf16 checks and tests/test_distill_guard.py)."""
+    if not _PROD:
+        _PROD.update(prod_case())
+    return _PROD
+
+
+@pytest.mark.parametrize("mode", ["fused", "generic", "bf16"])
+def test_distillation_production_width_vs_fp64_oracle(mode):
+    """NV = 4 LayerNorm rows, S = 288 attention and the real injection size: the fp32 distillation-only step (both paths) at
+    DISTILL_RTOL, the bf16 step at the measured DISTILL_RTOL_BF16, against the fp64 oracle."""
+    p = prod_setup()
+    cfg, batch, spec = p["cfg"], p["batch"], p["spec"]
+    dt = torch.bfloat16 if mode == "bf16" else torch.float32
+    model, teacher = build_model(cfg, p["sd"], dt), build_model(cfg, p["tsd"], dt)
+    fd, _ = make_fd_spec(cfg, spec, teacher, batch["input_ids"].shape[0])
+    fd.fused_distill = mode != "generic"
+    got = run_native_replay(model, fd, batch, cfg, 0.0, spec.distillation_coeff)
+    check_distill_parity(got, p["ref"], DISTILL_RTOL_BF16 if mode == "bf16" else DISTILL_RTOL, f"prod/{mode}")
 
 
 def test_layer_strategy_errors_match_reference():
