@@ -216,6 +216,38 @@ int mafed_decode_set_trace(void* buf);
 int mafed_attn_decode_set_trace(void* buf);   /* the same for mafed_attn_decode_prerot's all-rows-in-flight kernel: 8 int64 per (batch, head) */
 int mafed_decode_out(const float* x, float* x_out, int M, int h, int n1, const void* ao, const void* act, const void* wd,
                      const float* bd, const void* w2, const float* b2, void* workspace, size_t workspace_bytes, void* stream);
+/* M > 64 (up to 256 rows: B = 32 samples x 8 beams): mafed_decode_ln_qkv_fc1 and mafed_decode_out run the rows in blocks of 64, each
+ * block exactly as a call with those 64 rows (the same kernels and bits; decode_out's workspace is the 64-row one, re-used in order).
+ * mafed_decode_ln_linear stays at M <= 64. */
+
+/* ---- beam search over a shared-prefix KV cache (model.generate(num_beams=k), HF GenerationMixin._beam_search semantics) ---------
+ * Per sample: one prefill; per layer the prefix [B,S0,H,3,D] (pre-rotated keys) shared by the sample's k beams and the generated rows
+ * [B*k,cap,H,3,D] (slot r writes its row t at [r, t]); an int32 ancestry table anc [B*k,cap] names the slot holding row j of beam r's
+ * history.  A reorder rewrites anc only (anc'[r,j] = anc[parent(r),j] for j < t, anc'[r,t] = r): no K/V is copied.  k <= 8.
+ *
+ * mafed_beam_candidates: logits [B*kin, V] (row stride ldl, fp32 or bf16) and running scores [B*kin] -> per sample the top 2k of
+ * log_softmax(logits[row]) + score[row] over its kin rows x V tokens, best first: out_score [B,2k] fp32, out_token [B,2k] int64,
+ * out_parent [B,2k] int32 (row within the sample).  Order: score descending; equal scores go to the lower flat index row * V + token. */
+int mafed_beam_candidates(const void* logits, mafed_dtype dtype, int64_t ldl, const float* score, int B, int kin, int V, int k,
+                          float* out_score, int64_t* out_token, int* out_parent, void* stream);
+/* One beam-search step's bookkeeping, one workgroup per sample (HF 5.x _beam_search with one eos id, eos < 0: none): candidates among
+ * the first k ranks that emit eos (or every one at step == cap - 1) join the finished set with score / (step + 1)^length_penalty, the
+ * k best finished hypotheses are kept best first; the first k candidates that did not finish continue (run_score, next_token, the
+ * rows of anc / hist rewritten); early_stopping 0 / 1 / 2 = False / True / "never" with HF's stop heuristic, after which a sample is
+ * `done` (its set is final; its beams feed pad).  The *_in / *_out pairs are distinct buffers (ping-pong between steps).  fin_tok
+ * [B,k,cap] int64 holds the hypotheses' generated tokens padded with `pad`, fin_score [B,k] (-1e9 = empty), fin_len [B,k] (0 = empty). */
+int mafed_beam_update(const float* cand_score, const int64_t* cand_token, const int* cand_parent, int B, int k, int step, int cap,
+                      int eos, int pad, int early_stopping, float length_penalty, float* run_score, const int* anc_in, int* anc_out,
+                      const int64_t* hist_in, int64_t* hist_out, const int64_t* fin_tok_in, int64_t* fin_tok_out,
+                      const float* fin_score_in, float* fin_score_out, const int* fin_len_in, int* fin_len_out, int* done,
+                      int64_t* next_token, void* stream);
+/* Decode attention of the k beams of every sample over the layout above: one workgroup per (sample, head) serves the k query rows
+ * (row t of each beam slot, position S0 + t), reads the sample's prefix K/V once for all of them, rows j < t through anc and row t
+ * from the beam's own slot (its key rotated, used and written back rotated, as mafed_attn_decode_prerot does).  attention_mask
+ * [B,T] per sample.  rot % 16 == 0, D in {64, 128, 256}.  out [B*k, H*D]. */
+int mafed_attn_decode_beam(const void* qkv_prefix, int S0, void* qkv_new, int cap, int t, mafed_dtype dtype, int B, int k,
+                           const int* anc, int H, int D, int rot, const float* rot_cos, const float* rot_sin,
+                           const int64_t* attention_mask, int T, void* out, void* stream);
 
 /* ---- online EWC penalty (mafed/methods/ewc.py:105-127) -------------------------------------
  * The reference's compute_regularization over named_parameters(), on the flat fp32 buffers:

@@ -759,7 +759,9 @@ static int num_cus() {
 using namespace mafed;
 
 // h % 256 == 0 (eight waves x whole 32-deep k-steps), n1 % 32 == 0, M <= 64 with ceil(M / 16) * h / 256 <= 16 (the x slab lives in registers)
+// M in 65 .. 256 (beam search: B x k rows): served in blocks of 64 rows by the 64-row kernels
 extern "C" int mafed_decode_supported(int M, int h, int n1) {
+  if (M > 64 && M <= 256) return mafed_decode_supported(64, h, n1);
   if (M < 1 || M > 64 || h % 256 != 0 || n1 % 32 != 0 || h > 4096) return 0;
   const int mt = (M + 15) / 16, ks = h / 256;
   if (!(ks == 1 || ks == 2 || ks == 3 || ks == 4 || ks == 8)) return 0;
@@ -812,6 +814,14 @@ extern "C" int mafed_decode_ln_qkv_fc1(const float* x, int M, int h, float eps, 
   MAFED_CHECK_ARG(mafed_decode_supported(M, h, n1), "decode_ln_qkv_fc1: unsupported shape M=%d h=%d n1=%d", M, h, n1);
   MAFED_CHECK_ARG(x && ln1_w && ln1_b && ln2_w && ln2_b && wqkv && bqkv && qkv_out && w1 && b1 && a_out, "decode_ln_qkv_fc1: null operand");
   MAFED_CHECK_ARG(qkv_ld >= 3 * (int64_t)h && qkv_ld % 4 == 0, "decode_ln_qkv_fc1: qkv_ld");
+  if (M > 64) {   // blocks of 64 rows, each exactly the 64-row call
+    for (int m0 = 0; m0 < M; m0 += 64) {
+      const int rc = mafed_decode_ln_qkv_fc1(x + (int64_t)m0 * h, M - m0 < 64 ? M - m0 : 64, h, eps, ln1_w, ln1_b, ln2_w, ln2_b, wqkv, bqkv,
+                                             (bf16_t*)qkv_out + (int64_t)m0 * qkv_ld, qkv_ld, w1, b1, n1, (bf16_t*)a_out + (int64_t)m0 * n1, stream);
+      if (rc) return rc;
+    }
+    return MAFED_OK;
+  }
   DecodeAArgs a{x, M, h, eps, ln1_w, ln1_b, ln2_w, ln2_b, (const bf16_t*)wqkv, bqkv, (bf16_t*)qkv_out, qkv_ld, (const bf16_t*)w1, b1, (bf16_t*)a_out, 3 * h, n1, g_decode_trace};
   const int mt = (M + 15) / 16, ks = h / 256;
   const size_t lds = (size_t)(16 * mt + 32) * (size_t)(h + 8) * 2;
@@ -839,7 +849,7 @@ extern "C" int mafed_decode_ln_qkv_fc1(const float* x, int M, int h, float eps, 
 // out[m, 0:N] = LN(x[m]) . w^T (+ bias): the final LayerNorm folded into the LM head's product (bf16 out, row stride ldo)
 extern "C" int mafed_decode_ln_linear(const float* x, int M, int h, float eps, const float* ln_w, const float* ln_b, const void* w, const float* bias,
                                       int64_t N, void* out, int64_t ldo, void* stream) {
-  MAFED_CHECK_ARG(mafed_decode_supported(M, h, 32) && N % 32 == 0 && N >= 32 && N <= (int64_t)1 << 30, "decode_ln_linear: unsupported shape M=%d h=%d N=%lld",
+  MAFED_CHECK_ARG(M <= 64 && mafed_decode_supported(M, h, 32) && N % 32 == 0 && N >= 32 && N <= (int64_t)1 << 30, "decode_ln_linear: unsupported shape M=%d h=%d N=%lld",
                   M, h, (long long)N);
   MAFED_CHECK_ARG(x && ln_w && ln_b && w && out && ldo >= N && ldo % 4 == 0, "decode_ln_linear: operands");
   DecodeAArgs a{x, M, h, eps, ln_w, ln_b, ln_w, ln_b, (const bf16_t*)w, bias, (bf16_t*)out, ldo, (const bf16_t*)w, bias, (bf16_t*)out, (int)N, 0, nullptr};
@@ -884,6 +894,7 @@ extern "C" int mafed_decode_set_trace(void* buf) { g_decode_trace = (long long*)
 
 extern "C" size_t mafed_decode_out_workspace_bytes(int M, int h) {
   // [P <= 16][ceil(M / 16) * 16][h] fp32 partial tiles + h / 32 counters (zero-initialised once by the caller; the kernel re-arms them)
+  if (M > 64) M = 64;   // (more rows: blocks of 64 in order, one workspace)
   return (size_t)16 * (size_t)(((M + 15) / 16) * 16) * (size_t)h * sizeof(float) + (size_t)(h / 32) * sizeof(unsigned);
 }
 
@@ -892,6 +903,18 @@ extern "C" int mafed_decode_out(const float* x, float* x_out, int M, int h, int 
   MAFED_CHECK_ARG(mafed_decode_supported(M, h, n1), "decode_out: unsupported shape M=%d h=%d n1=%d", M, h, n1);
   MAFED_CHECK_ARG(x && x_out && ao && act && wd && bd && w2 && b2 && workspace, "decode_out: null operand");
   MAFED_CHECK_ARG(workspace_bytes >= mafed_decode_out_workspace_bytes(M, h), "decode_out: workspace too small");
+  if (M > 64) {   // blocks of 64 rows in stream order, each exactly the call with its rows (the counters are re-armed by every launch)
+    for (int m0 = 0; m0 < M; m0 += 64) {
+      const int64_t o = (int64_t)m0 * h;
+      const int mc = M - m0 < 64 ? M - m0 : 64;
+      // a shorter last block sees the workspace shifted so that its counters are the 64-row layout's (zero), not partial tiles
+      const size_t shift = mafed_decode_out_workspace_bytes(64, h) - mafed_decode_out_workspace_bytes(mc, h);
+      const int rc = mafed_decode_out(x + o, x_out + o, mc, h, n1, (const bf16_t*)ao + o, (const bf16_t*)act + (int64_t)m0 * n1,
+                                      wd, bd, w2, b2, (char*)workspace + shift, workspace_bytes - shift, stream);
+      if (rc) return rc;
+    }
+    return MAFED_OK;
+  }
   const int mt = (M + 15) / 16, groups = h / 32, ktot = (h + n1) / 32;
   int P = (num_cus() + groups / 2) / groups;
   if (P < 1) P = 1;

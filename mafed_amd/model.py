@@ -89,6 +89,14 @@ class CausalLMOutput:
         return tuple(v for v in (self.loss, self.logits, self.hidden_states) if v is not None)[i]
 
 
+@dataclass
+class BeamSearchOutput:
+    """``generate(..., return_dict_in_generate=True)``: the fields of transformers' GenerateBeamDecoderOnlyOutput that are produced."""
+
+    sequences: torch.Tensor
+    sequences_scores: Optional[torch.Tensor] = None
+
+
 # parameter holders: modules without a forward; the tree only exists so that state-dict names match the reference
 class _Affine(nn.Module):
     def __init__(self, w: nn.Parameter, b: Optional[nn.Parameter]):
@@ -199,6 +207,7 @@ class VLPythiaForCausalLM(nn.Module):
         # 256 CUs without split-K (one layer's products alone leave a third to seven eighths of the chip idle); 0 = one launch each
         self.dw_group_layers = 2
         self.sparse_lm_head = True          # batches that carry ``max_label_rows`` get the row-sparse LM head in training
+        self.beam_trace: Optional[List[Any]] = None   # a list: generate(num_beams > 1) appends every step's candidate lists to it
         self.defer_ln_param_reduce = True   # LayerNorm parameter-gradient reduction on a side stream (needs overlap_param_grads)
         self.reset_parameters(seed)
         self.register_load_state_dict_post_hook(lambda m, ik: setattr(m, "_shadow_dirty", True))
@@ -481,7 +490,8 @@ class VLPythiaForCausalLM(nn.Module):
     def generate(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
                  patch_embeddings: Optional[torch.Tensor] = None, max_new_tokens: int = 10, use_cache: bool = True,
                  pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = 0, do_sample: bool = False,
-                 return_step_logits: bool = False, use_graph: bool = False, **kwargs):
+                 return_step_logits: bool = False, use_graph: bool = False, num_beams: int = 1, length_penalty: float = 1.0,
+                 early_stopping: Any = False, num_return_sequences: int = 1, return_dict_in_generate: bool = False, **kwargs):
         """Greedy search with the call signature the reference validation uses (mafed/model/vqa_cont_learner.py:260-267,
         mafed/utils/eval_utils.py:170-177: ``generate(input_ids=, attention_mask=, pixel_values=, max_new_tokens=10,
         use_cache=False, pad_token_id=eos)``) and HF ``greedy_search`` semantics (transformers 4.37.1): next token = argmax of
@@ -493,11 +503,36 @@ class VLPythiaForCausalLM(nn.Module):
         again for every token.  ``use_cache=True`` (default here) runs the prefix once, keeps each layer's fused-QKV output as
         the K/V cache and then moves ONE row per sample through the stack per token (``mafed_attn_decode``); both produce the
         same tokens.  Returns [B, T + n_generated] like HF; with ``return_step_logits`` also the fp32 last-position logits of
-        every step [n, B, V]."""
-        if do_sample or kwargs.get("num_beams", 1) != 1:
-            raise NotImplementedError("only greedy search is on the validation path")
+        every step [n, B, V].
+
+        ``num_beams = k > 1``: beam search with HF ``GenerationMixin._beam_search`` semantics (transformers 5.x; ``length_penalty``,
+        ``early_stopping`` True / False / "never", ``num_return_sequences`` <= k <= 8) -> [B * num_return_sequences, T + n], rows padded
+        with ``pad_token_id`` up to the longest returned hypothesis; ``return_dict_in_generate`` adds the length-normalised
+        ``sequences_scores`` (a beam-search option: the greedy path returns its tensor as before).  ``use_cache=False`` recomputes the B * k beams' full sequences every step; ``use_cache=True`` prefills
+        each sample once and decodes its k beams over the shared prefix (``_beam_search``).  Not implemented: sampling (beam-sample
+        included), graph capture of the beam loop, diverse / constrained beam search."""
+        if do_sample:
+            raise NotImplementedError("sampling (do_sample=True, beam-sample included) is not implemented: greedy or beam search only")
+        if kwargs.get("num_beam_groups") not in (None, 1) or kwargs.get("constraints") is not None or kwargs.get("force_words_ids") is not None:
+            raise NotImplementedError("diverse / constrained beam search (num_beam_groups, constraints, force_words_ids) is not implemented")
+        if not isinstance(num_beams, int) or num_beams < 1 or num_beams > 8:
+            raise ValueError(f"num_beams must be an int in 1 .. 8, got {num_beams!r}")
+        if num_return_sequences < 1 or num_return_sequences > num_beams:
+            raise ValueError(f"num_return_sequences ({num_return_sequences}) must be in 1 .. num_beams ({num_beams})")
         if input_ids is None or (pixel_values is None and patch_embeddings is None):
             raise ValueError("generate needs input_ids and pixel_values / patch_embeddings")
+        if num_beams > 1:
+            if use_graph:
+                raise NotImplementedError("use_graph=True (hipGraph capture) is not implemented for beam search")
+            if return_step_logits:
+                raise NotImplementedError("return_step_logits is a greedy-search option")
+            if max_new_tokens < 1:
+                raise ValueError(f"beam search needs max_new_tokens >= 1, got {max_new_tokens}")
+            if early_stopping not in (False, True, "never"):
+                raise ValueError(f"early_stopping must be True, False or 'never', got {early_stopping!r}")
+            return self._beam_search(input_ids, attention_mask, pixel_values, patch_embeddings, num_beams, max_new_tokens, use_cache,
+                                     pad_token_id, eos_token_id, float(length_penalty), early_stopping, num_return_sequences,
+                                     return_dict_in_generate)
         dev = self.flat_params.device
         feats = (patch_embeddings if patch_embeddings is not None else self.get_patch_embeddings(pixel_values)).to(dev).contiguous()
         ids = input_ids.to(dev, torch.int64).contiguous()
@@ -563,6 +598,79 @@ class VLPythiaForCausalLM(nn.Module):
             return out, torch.stack(step_logits, dim=0)
         return out
 
+    def _beam_search(self, input_ids, attention_mask, pixel_values, patch_embeddings, k: int, max_new: int, use_cache: bool, pad_token_id,
+                     eos_token_id, length_penalty: float, early_stopping, nrs: int, return_dict: bool):
+        """Beam search (generate(num_beams=k)); every decision on the device (csrc/beam.hip), one host synchronisation at the end.
+        Per step: mafed_beam_candidates (top 2k of log_softmax + running score per sample) and mafed_beam_update (finished set,
+        continuing beams, early stopping, ancestry / history rewrite).  The loop runs to max_new_tokens like the greedy path: a sample
+        whose result is final stops changing (HF leaves the loop once every sample is such), and the output is cut at the end."""
+        cfg, dev = self.config, self.flat_params.device
+        feats = (patch_embeddings if patch_embeddings is not None else self.get_patch_embeddings(pixel_values)).to(dev).contiguous()
+        ids = input_ids.to(dev, torch.int64).contiguous()
+        am = (attention_mask if attention_mask is not None else torch.ones_like(input_ids)).to(dev, torch.int64).contiguous()
+        if eos_token_id is not None and pad_token_id is None:
+            pad_token_id = eos_token_id
+        eos = -1 if eos_token_id is None else int(eos_token_id)
+        pad = 0 if pad_token_id is None else int(pad_token_id)
+        early = {False: 0, True: 1, "never": 2}[early_stopping]
+        B, T = ids.shape
+        BK, cap = B * k, max_new
+        i32, i64, f32 = torch.int32, torch.int64, torch.float32
+        cand = (torch.empty((B, 2 * k), dtype=f32, device=dev), torch.empty((B, 2 * k), dtype=i64, device=dev),
+                torch.empty((B, 2 * k), dtype=i32, device=dev))
+        run_score = torch.zeros(BK, dtype=f32, device=dev)
+        anc = [torch.zeros((BK, cap), dtype=i32, device=dev) for _ in range(2)]
+        hist = [torch.zeros((BK, cap), dtype=i64, device=dev) for _ in range(2)]
+        fin_tok = [torch.full((B, k, cap), pad, dtype=i64, device=dev) for _ in range(2)]
+        fin_score = [torch.full((B, k), -1e9, dtype=f32, device=dev) for _ in range(2)]
+        fin_len = [torch.zeros((B, k), dtype=i32, device=dev) for _ in range(2)]
+        done = torch.zeros(B, dtype=i32, device=dev)
+        next_tok = torch.zeros(BK, dtype=i64, device=dev)
+        cur = 0
+
+        def beam_step(logits, score, n):
+            nonlocal cur
+            ops.beam_candidates(logits, score, B, k, out=cand)
+            if self.beam_trace is not None:   # tests / tools: every step's candidate lists (score, token, parent), copied
+                self.beam_trace.append(tuple(c.clone() for c in cand))
+            o = 1 - cur
+            ops.beam_update(cand, B, k, n, cap, eos, pad, early, length_penalty, run_score, (anc[cur], anc[o]), (hist[cur], hist[o]),
+                            (fin_tok[cur], fin_tok[o]), (fin_score[cur], fin_score[o]), (fin_len[cur], fin_len[o]), done, next_tok)
+            cur = o
+
+        if not use_cache:
+            # the reference's literal recompute: the B * k beams' full sequences through the stack every step (HF expands every
+            # sample k times; beams 1 .. k-1 start at -1e9, so the first step's candidates all come from beam 0)
+            feats_k, ids_k, am_k = feats.repeat_interleave(k, 0), ids.repeat_interleave(k, 0), am.repeat_interleave(k, 0)
+            score0 = torch.full((B, k), -1e9, dtype=f32, device=dev)
+            score0[:, 0] = 0.0
+            score0 = score0.view(BK)
+            for n in range(max_new):
+                cur_ids = torch.cat([ids_k, hist[cur][:, :n]], dim=1)
+                cur_am = torch.cat([am_k, torch.ones((BK, n), dtype=i64, device=dev)], dim=1)
+                st = self._engine_forward(feats_k, cur_ids, cur_am, None, False, train=False)
+                beam_step(st["logits"][:, -1, :], score0 if n == 0 else run_score, n)
+        else:
+            # one prefill per sample: its last-position logits are the first step's (only beam 0 is live there), its K/V the prefix
+            # that the sample's k beams share
+            S_ = cfg.num_vision_tokens + T
+            store = torch.empty((cfg.num_hidden_layers, B * S_, 3 * cfg.num_attention_heads * cfg.head_dim), dtype=self.compute_dtype, device=dev)
+            st = self._engine_forward(feats, ids, am, None, False, train=False, qkv_out=list(store.unbind(0)), last_only=True)
+            cache = _DecodeCache(self, list(store.unbind(0)), B, st["S"], max_new, am, fused=getattr(self, "fused_decode", True),
+                                 prefix_storage=store, beams=k)
+            if not cache.prerot:
+                raise NotImplementedError("the cached beam search needs the pre-rotated cache (rotary dims % 16 == 0, head size 64 / 128 / 256)")
+            beam_step(st["logits"][:, -1, :], torch.zeros(B, dtype=f32, device=dev), 0)
+            for t in range(max_new - 1):
+                cache.anc = anc[cur]
+                beam_step(self._engine_decode_step(next_tok, t, cache), run_score, t + 1)
+        lens = fin_len[cur][:, :nrs]
+        n_keep = int(lens.max())   # the one host synchronisation
+        seqs = torch.cat([ids.repeat_interleave(nrs, 0), fin_tok[cur][:, :nrs, :n_keep].reshape(B * nrs, n_keep)], dim=1)
+        if return_dict:
+            return BeamSearchOutput(sequences=seqs, sequences_scores=fin_score[cur][:, :nrs].reshape(B * nrs).clone())
+        return seqs
+
     def _engine_decode_step(self, tokens: torch.Tensor, t: int, cache: "_DecodeCache") -> torch.Tensor:
         """One token per sample through the stack: ``tokens`` [B] sit at position S0 + t; returns the logits [B, V]."""
         cfg, cd = self.config, self.compute_dtype
@@ -581,10 +689,12 @@ class VLPythiaForCausalLM(nn.Module):
                                           cfg.layer_norm_eps, w(pre + "attention.query_key_value.weight"),
                                           self._p(pre + "attention.query_key_value.bias"), cache.new[i][:, t, :],
                                           w(pre + "mlp.dense_h_to_4h.weight"), self._p(pre + "mlp.dense_h_to_4h.bias"))
-                ao = ops.attn_decode(cache.prefix[i], S0, cache.new[i], t, B, H, D, rot, cos, sin, cache.attention_mask, prerot=True)
+                ao = (ops.attn_decode(cache.prefix[i], S0, cache.new[i], t, B, H, D, rot, cos, sin, cache.attention_mask, prerot=True)
+                      if cache.anc is None else
+                      ops.attn_decode_beam(cache.prefix[i], S0, cache.new[i], t, B, cache.beams, cache.anc, H, D, rot, cos, sin, cache.attention_mask))
                 x = ops.decode_out(x, ao, a, w(pre + "attention.dense.weight"), self._p(pre + "attention.dense.bias"),
                                    w(pre + "mlp.dense_4h_to_h.weight"), self._p(pre + "mlp.dense_4h_to_h.bias"), cache.workspace, out=x)
-            if B <= 32 and h == 1024 and cfg.vocab_size % 32 == 0 and cfg.vocab_size >= 16384:
+            if B * cache.beams <= 32 and h == 1024 and cfg.vocab_size % 32 == 0 and cfg.vocab_size >= 16384:
                 # final LayerNorm + LM head as one persistent launch (decode_head_kernel: rows normalised once per CU, the vocabulary's
                 # weight strips streamed through LDS): 24 us against 48 for LayerNorm + the skinny product at V = 50k
                 return ops.decode_ln_linear(x, self._p("gpt_neox.final_layer_norm.weight"), self._p("gpt_neox.final_layer_norm.bias"),
@@ -601,7 +711,9 @@ class VLPythiaForCausalLM(nn.Module):
             # the new token's q | k | v row goes straight into the cache (row t of the per-layer [B, cap, 3*H*D] tensor)
             ops.gemm(ln1, w(pre + "attention.query_key_value.weight"), False, True, bias=self._p(pre + "attention.query_key_value.bias"),
                      out=cache.new[i][:, t, :])
-            ao = ops.attn_decode(cache.prefix[i], S0, cache.new[i], t, B, H, D, rot, cos, sin, cache.attention_mask, prerot=cache.prerot)
+            ao = (ops.attn_decode(cache.prefix[i], S0, cache.new[i], t, B, H, D, rot, cos, sin, cache.attention_mask, prerot=cache.prerot)
+                  if cache.anc is None else
+                  ops.attn_decode_beam(cache.prefix[i], S0, cache.new[i], t, B, cache.beams, cache.anc, H, D, rot, cos, sin, cache.attention_mask))
             attn = ops.gemm(ao, w(pre + "attention.dense.weight"), False, True, bias=self._p(pre + "attention.dense.bias"), out_dtype=cd)
             a = ops.gemm(ln2, w(pre + "mlp.dense_h_to_4h.weight"), False, True, bias=self._p(pre + "mlp.dense_h_to_4h.bias"), epilogue=EPI_GELU)
             x = ops.gemm(a, w(pre + "mlp.dense_4h_to_h.weight"), False, True, bias=self._p(pre + "mlp.dense_4h_to_h.bias"),
@@ -1038,19 +1150,25 @@ class _DecodeCache:
     transpose, k un-rotated) and a [B, cap, 3*H*D] tensor that receives one row per generated token."""
 
     def __init__(self, model, prefix, B: int, S0: int, cap: int, attention_mask: torch.Tensor, prerotate: bool = True, fused: bool = True,
-                 prefix_storage: Optional[torch.Tensor] = None):
+                 prefix_storage: Optional[torch.Tensor] = None, beams: int = 1):
         self.prefix, self.B, self.S0, self.cap, self.attention_mask = prefix, B, S0, max(1, cap), attention_mask
         self.prefix_storage = prefix_storage   # [L, B*S0, 3h] holding every entry of `prefix` (then one rotation launch serves all layers)
+        # beam search: the prefix stays one per sample, the generated rows are one per beam slot ([B*beams, cap, 3h]); `anc` (int32
+        # [B*beams, cap], set by the caller before each step) names the slot holding each row of a beam's history
+        self.beams, self.anc = beams, None
+        rows = B * beams
         cfg = model.config
         n = 3 * cfg.num_attention_heads * cfg.head_dim
-        self.new = [torch.zeros((B, self.cap, n), dtype=prefix[0].dtype, device=prefix[0].device) for _ in prefix]
+        self.new = [torch.zeros((rows, self.cap, n), dtype=prefix[0].dtype, device=prefix[0].device) for _ in prefix]
         # Pre-rotated cache (round 4): once the prefill's attention has read the un-rotated keys, rotate them in place -- every decode step
         # then loads k and v only (mafed_attn_decode_prerot).  Needs rot % 16 == 0 and an MFMA head size (every VLPythia preset).
         self.prerot = bool(prerotate) and cfg.rotary_ndims % 16 == 0 and cfg.head_dim in (64, 128, 256)
         self._model = model
         # fused decode layer (csrc/decode.hip): bf16 mode over the pre-rotated cache, shapes per mafed_decode_supported
-        self.fused = bool(fused) and self.prerot and prefix[0].dtype == torch.bfloat16 and ops.decode_supported(B, cfg.hidden_size, cfg.intermediate_size)
-        self.workspace = ops.decode_out_workspace(B, cfg.hidden_size, prefix[0].device) if self.fused else None
+        # (more than 64 rows -- 64-row blocks of the fused kernels -- only for beam search: a greedy batch of B > 64 keeps the six launches)
+        self.fused = (bool(fused) and self.prerot and prefix[0].dtype == torch.bfloat16 and (rows <= 64 or beams > 1)
+                      and ops.decode_supported(rows, cfg.hidden_size, cfg.intermediate_size))
+        self.workspace = ops.decode_out_workspace(rows, cfg.hidden_size, prefix[0].device) if self.fused else None
         if self.prerot:
             self.rotate_prefix()
 

@@ -320,6 +320,48 @@ def attn_decode(qkv_prefix: torch.Tensor, S0: int, qkv_new: torch.Tensor, t: int
     return out
 
 
+def attn_decode_beam(qkv_prefix: torch.Tensor, S0: int, qkv_new: torch.Tensor, t: int, B: int, k: int, anc: torch.Tensor, H: int, D: int,
+                     rot: int, cos, sin, attention_mask: torch.Tensor) -> torch.Tensor:
+    """Decode attention of the k beams of B samples (mafed_attn_decode_beam): queries = row t of every slot of ``qkv_new`` [B*k,cap,3*H*D],
+    keys = the sample's pre-rotated prefix ``qkv_prefix`` [B*S0, 3*H*D] (read once for its k beams), then rows j < t of slot
+    ``anc[r, j]`` and row t of the beam's own slot.  ``anc`` int32 [B*k, cap].  -> [B*k, H*D]"""
+    cap = qkv_new.shape[1]
+    assert qkv_new.dim() == 3 and qkv_new.shape[0] == B * k and qkv_new.is_contiguous() and qkv_prefix.is_contiguous()
+    assert qkv_new.dtype == qkv_prefix.dtype and anc.dtype == torch.int32 and anc.shape == (B * k, cap) and anc.is_contiguous()
+    assert cos.shape[0] >= S0 + t + 1
+    out = torch.empty((B * k, H * D), dtype=qkv_new.dtype, device=qkv_new.device)
+    check(_lib.load().mafed_attn_decode_beam(_ptr(qkv_prefix), S0, _ptr(qkv_new), cap, t, _dt(qkv_new), B, k, _ptr(anc), H, D, rot, _ptr(cos),
+                                             _ptr(sin), _ptr(attention_mask), attention_mask.shape[1], _ptr(out), _stream()), "mafed_attn_decode_beam")
+    return out
+
+
+def beam_candidates(logits: torch.Tensor, score: torch.Tensor, B: int, k: int, out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None):
+    """Per sample, the top 2k of ``log_softmax(logits[row]) + score[row]`` over its kin = rows / B rows (mafed_beam_candidates).
+    logits [B*kin, V] fp32 / bf16 (unit column stride), score fp32 [B*kin] -> (score fp32 [B,2k], token int64 [B,2k], parent int32 [B,2k]),
+    best first; equal scores go to the lower flat index row * V + token."""
+    rows, V = logits.shape
+    assert logits.stride(1) == 1 and rows % B == 0 and score.dtype == torch.float32 and score.numel() == rows and score.is_contiguous()
+    dev = logits.device
+    if out is None:
+        out = (torch.empty((B, 2 * k), dtype=torch.float32, device=dev), torch.empty((B, 2 * k), dtype=torch.int64, device=dev),
+               torch.empty((B, 2 * k), dtype=torch.int32, device=dev))
+    cs, ct, cp = out
+    check(_lib.load().mafed_beam_candidates(_ptr(logits), _dt(logits), logits.stride(0), _ptr(score), B, rows // B, V, k, _ptr(cs), _ptr(ct),
+                                            _ptr(cp), _stream()), "mafed_beam_candidates")
+    return cs, ct, cp
+
+
+def beam_update(cand, B: int, k: int, step: int, cap: int, eos: int, pad: int, early_stopping: int, length_penalty: float, run_score,
+                anc, hist, fin_tok, fin_score, fin_len, done, next_token) -> None:
+    """One step of the beam bookkeeping (mafed_beam_update).  ``anc`` / ``hist`` / ``fin_tok`` / ``fin_score`` / ``fin_len`` are
+    (before, after) pairs of distinct tensors; ``run_score``, ``done`` and ``next_token`` are updated in place."""
+    cs, ct, cp = cand
+    check(_lib.load().mafed_beam_update(_ptr(cs), _ptr(ct), _ptr(cp), B, k, step, cap, int(eos), int(pad), int(early_stopping), float(length_penalty),
+                                        _ptr(run_score), _ptr(anc[0]), _ptr(anc[1]), _ptr(hist[0]), _ptr(hist[1]), _ptr(fin_tok[0]), _ptr(fin_tok[1]),
+                                        _ptr(fin_score[0]), _ptr(fin_score[1]), _ptr(fin_len[0]), _ptr(fin_len[1]), _ptr(done), _ptr(next_token),
+                                        _stream()), "mafed_beam_update")
+
+
 def gemm_grouped_fuses_sumsq(shapes: Sequence[Tuple[int, int, int]], transA: bool, transB: bool) -> bool:
     """Would ``gemm_grouped`` run these (M, N, K) bf16 -> fp32 products as one persistent launch with the squares of C fused into its
     epilogue?  (host-side query, no launch)"""
