@@ -1,0 +1,348 @@
+"""Generation for ``VLPythiaForCausalLM``: greedy and beam search, the KV-cached decode step, its cache and the captured-graph decode.
+``GenerationMixin`` is a base class of the model (mafed_amd/model.py, which this module does not import): it uses the model's engine
+forward, parameter records and rotary tables, and the state ``fused_decode`` / ``beam_trace`` / ``_decode_graphs`` its ``__init__`` declares."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Any, Optional, Tuple
+
+import torch
+
+from mafed_amd import ops
+from mafed_amd._lib import EPI_GELU
+
+
+@dataclass
+class BeamSearchOutput:
+    """``generate(..., return_dict_in_generate=True)``: the fields of transformers' GenerateBeamDecoderOnlyOutput that are produced."""
+
+    sequences: torch.Tensor
+    sequences_scores: Optional[torch.Tensor] = None
+
+
+def _greedy_pick(last_logits: torch.Tensor, unfinished: torch.Tensor, eos_token_id, pad_token_id) -> Tuple[torch.Tensor, torch.Tensor]:
+    """HF ``greedy_search`` token rule: argmax of the last position, finished rows emit ``pad_token_id``; -> (tokens [B], the
+    updated ``unfinished`` flags).  Shared by the eager loop and the captured graph's body."""
+    nxt = last_logits.float().argmax(dim=-1)
+    if eos_token_id is not None:
+        nxt = nxt * unfinished + pad_token_id * (1 - unfinished)
+        unfinished = unfinished * (nxt != eos_token_id).to(torch.int64)
+    return nxt, unfinished
+
+
+class GenerationMixin:
+    """``generate`` and what it runs on, as methods of the model."""
+
+    # ---- greedy decode -----------------------------------------------------------------------
+    @torch.no_grad()
+    def generate(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
+                 patch_embeddings: Optional[torch.Tensor] = None, max_new_tokens: int = 10, use_cache: bool = True,
+                 pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = 0, do_sample: bool = False,
+                 return_step_logits: bool = False, use_graph: bool = False, num_beams: int = 1, length_penalty: float = 1.0,
+                 early_stopping: Any = False, num_return_sequences: int = 1, return_dict_in_generate: bool = False, **kwargs):
+        """Greedy search with the call signature the reference validation uses (mafed/model/vqa_cont_learner.py:260-267,
+        mafed/utils/eval_utils.py:170-177: ``generate(input_ids=, attention_mask=, pixel_values=, max_new_tokens=10,
+        use_cache=False, pad_token_id=eos)``) and HF ``greedy_search`` semantics (transformers 4.37.1): next token = argmax of
+        the last position, finished rows keep emitting ``pad_token_id``, the attention mask grows by ones, generation stops
+        when every row has produced ``eos_token_id`` (GPT-NeoX / Pythia: 0) or after ``max_new_tokens``.  Positions are
+        ``arange`` over [image | text | generated].
+
+        ``use_cache=False`` is the reference's literal behaviour -- the whole 256 + T + t prefix is pushed through the stack
+        again for every token.  ``use_cache=True`` (default here) runs the prefix once, keeps each layer's fused-QKV output as
+        the K/V cache and then moves ONE row per sample through the stack per token (``mafed_attn_decode``); both produce the
+        same tokens.  Returns [B, T + n_generated] like HF; with ``return_step_logits`` also the fp32 last-position logits of
+        every step [n, B, V].
+
+        ``num_beams = k > 1``: beam search with HF ``GenerationMixin._beam_search`` semantics (transformers 5.x; ``length_penalty``,
+        ``early_stopping`` True / False / "never", ``num_return_sequences`` <= k <= 8) -> [B * num_return_sequences, T + n], rows padded
+        with ``pad_token_id`` up to the longest returned hypothesis; ``return_dict_in_generate`` adds the length-normalised
+        ``sequences_scores`` (a beam-search option: the greedy path returns its tensor as before).  ``use_cache=False`` recomputes the B * k beams' full sequences every step; ``use_cache=True`` prefills
+        each sample once and decodes its k beams over the shared prefix (``_beam_search``).  Not implemented: sampling (beam-sample
+        included), graph capture of the beam loop, diverse / constrained beam search."""
+        if do_sample:
+            raise NotImplementedError("sampling (do_sample=True, beam-sample included) is not implemented: greedy or beam search only")
+        if kwargs.get("num_beam_groups") not in (None, 1) or kwargs.get("constraints") is not None or kwargs.get("force_words_ids") is not None:
+            raise NotImplementedError("diverse / constrained beam search (num_beam_groups, constraints, force_words_ids) is not implemented")
+        if not isinstance(num_beams, int) or num_beams < 1 or num_beams > 8:
+            raise ValueError(f"num_beams must be an int in 1 .. 8, got {num_beams!r}")
+        if num_return_sequences < 1 or num_return_sequences > num_beams:
+            raise ValueError(f"num_return_sequences ({num_return_sequences}) must be in 1 .. num_beams ({num_beams})")
+        if input_ids is None or (pixel_values is None and patch_embeddings is None):
+            raise ValueError("generate needs input_ids and pixel_values / patch_embeddings")
+        inputs = (input_ids, attention_mask, pixel_values, patch_embeddings, pad_token_id, eos_token_id)
+        if num_beams > 1:
+            if use_graph:
+                raise NotImplementedError("use_graph=True (hipGraph capture) is not implemented for beam search")
+            if return_step_logits:
+                raise NotImplementedError("return_step_logits is a greedy-search option")
+            if max_new_tokens < 1:
+                raise ValueError(f"beam search needs max_new_tokens >= 1, got {max_new_tokens}")
+            if early_stopping not in (False, True, "never"):
+                raise ValueError(f"early_stopping must be True, False or 'never', got {early_stopping!r}")
+            return self._beam_search(*self._generate_inputs(*inputs), eos_token_id, num_beams, max_new_tokens, use_cache, float(length_penalty),
+                                     early_stopping, num_return_sequences, return_dict_in_generate)
+        feats, ids, am, pad_token_id = self._generate_inputs(*inputs)
+        B, T = ids.shape
+        unfinished = torch.ones(B, dtype=torch.int64, device=ids.device)
+        new_tokens, step_logits = [], []
+
+        def pick(last_logits):
+            nonlocal unfinished
+            nxt, unfinished = _greedy_pick(last_logits, unfinished, eos_token_id, pad_token_id)
+            new_tokens.append(nxt)
+            if return_step_logits:
+                step_logits.append(last_logits.float())
+            return nxt
+
+        if not use_cache:
+            cur_ids, cur_am = ids, am
+            for _ in range(max_new_tokens):
+                st = self._engine_forward(feats, cur_ids, cur_am, None, False, train=False)
+                nxt = pick(st["logits"][:, -1, :])
+                cur_ids = torch.cat([cur_ids, nxt[:, None]], dim=1)
+                cur_am = torch.cat([cur_am, torch.ones_like(nxt)[:, None]], dim=1)
+        elif use_graph and not return_step_logits and max_new_tokens > 1:
+            # opt-in: the nine one-row-per-sample steps (~150 launches of 5-20 us kernels each) captured once per (B, T, max_new)
+            # into a hipGraph whose K/V cache lives at fixed addresses (the prefill's QKV GEMMs write straight into it).  It
+            # takes the host out of the loop; on an idle host it measures the same as eager launches (24.1 vs 24.2 ms at
+            # 410M / B = 32): the steps are bound by the GPU-side cost of that many small kernels.
+            key = (B, T, max_new_tokens, eos_token_id, pad_token_id)
+            gd = self._decode_graphs.get(key)
+            if gd is None:
+                gd = self._decode_graphs[key] = _GraphedDecode(self, B, T, max_new_tokens, eos_token_id, pad_token_id)
+            gen_all = gd.run(feats, ids, am)
+            new_tokens = list(gen_all.unbind(1))
+        else:
+            cache, first_logits = self._prefill(feats, ids, am, max_new_tokens)
+            nxt = pick(first_logits)
+            for t in range(max_new_tokens - 1):
+                nxt = pick(self._engine_decode_step(nxt, t, cache))
+        gen = torch.stack(new_tokens, dim=1)
+        if eos_token_id is not None:
+            # HF leaves the loop as soon as every row has finished: the output is as long as the slowest row needed
+            done = (gen == eos_token_id).to(torch.int64).cumsum(1).clamp_(max=1)       # 1 from the first eos on
+            first = (done.shape[1] - done.sum(1)) + done[:, -1]                        # tokens up to and including the first eos
+            n_keep = int(first.max().clamp_(max=gen.shape[1]))
+            gen = gen[:, :n_keep]
+            step_logits = step_logits[:n_keep]
+        out = torch.cat([ids, gen], dim=1)
+        if return_step_logits:
+            return out, torch.stack(step_logits, dim=0)
+        return out
+
+    def _generate_inputs(self, input_ids, attention_mask, pixel_values, patch_embeddings, pad_token_id, eos_token_id):
+        """-> (vision features, token ids, attention mask) on the model's device and the effective ``pad_token_id``."""
+        dev = self.flat_params.device
+        feats = (patch_embeddings if patch_embeddings is not None else self.get_patch_embeddings(pixel_values)).to(dev).contiguous()
+        ids = input_ids.to(dev, torch.int64).contiguous()
+        am = (attention_mask if attention_mask is not None else torch.ones_like(input_ids)).to(dev, torch.int64).contiguous()
+        if eos_token_id is not None and pad_token_id is None:
+            pad_token_id = eos_token_id  # HF's fallback for open-end generation
+        return feats, ids, am, pad_token_id
+
+    def _prefix_store(self, B: int, T: int) -> torch.Tensor:
+        """[L, B*S0, 3h]: every layer's fused-QKV output lands in one tensor (the K/V cache's prefix): its keys are then rotated by ONE launch."""
+        cfg = self.config
+        S0 = cfg.num_vision_tokens + T
+        return torch.empty((cfg.num_hidden_layers, B * S0, 3 * cfg.num_attention_heads * cfg.head_dim), dtype=self.compute_dtype,
+                           device=self.flat_params.device)
+
+    def _prefill(self, feats, ids, am, cap: int, beams: int = 1) -> Tuple["_DecodeCache", torch.Tensor]:
+        """Run the prompt once, its QKV GEMMs writing straight into a fresh prefix store -> (the decode cache over it, the last
+        position's logits [B, V])."""
+        B, T = ids.shape
+        store = self._prefix_store(B, T)
+        st = self._engine_forward(feats, ids, am, None, False, train=False, qkv_out=list(store.unbind(0)), last_only=True)
+        cache = _DecodeCache(self, list(store.unbind(0)), B, st["S"], cap, am, fused=self.fused_decode, prefix_storage=store, beams=beams)
+        return cache, st["logits"][:, -1, :]
+
+    def _beam_search(self, feats, ids, am, pad_token_id, eos_token_id, k: int, max_new: int, use_cache: bool, length_penalty: float,
+                     early_stopping, nrs: int, return_dict: bool):
+        """Beam search (generate(num_beams=k)); every decision on the device (csrc/beam.hip), one host synchronisation at the end.
+        Per step: mafed_beam_candidates (top 2k of log_softmax + running score per sample) and mafed_beam_update (finished set,
+        continuing beams, early stopping, ancestry / history rewrite).  The loop runs to max_new_tokens like the greedy path: a sample
+        whose result is final stops changing (HF leaves the loop once every sample is such), and the output is cut at the end."""
+        dev = ids.device
+        eos = -1 if eos_token_id is None else int(eos_token_id)
+        pad = 0 if pad_token_id is None else int(pad_token_id)
+        early = {False: 0, True: 1, "never": 2}[early_stopping]
+        B, T = ids.shape
+        BK, cap = B * k, max_new
+        i32, i64, f32 = torch.int32, torch.int64, torch.float32
+        cand = (torch.empty((B, 2 * k), dtype=f32, device=dev), torch.empty((B, 2 * k), dtype=i64, device=dev),
+                torch.empty((B, 2 * k), dtype=i32, device=dev))
+        run_score = torch.zeros(BK, dtype=f32, device=dev)
+        anc = [torch.zeros((BK, cap), dtype=i32, device=dev) for _ in range(2)]
+        hist = [torch.zeros((BK, cap), dtype=i64, device=dev) for _ in range(2)]
+        fin_tok = [torch.full((B, k, cap), pad, dtype=i64, device=dev) for _ in range(2)]
+        fin_score = [torch.full((B, k), -1e9, dtype=f32, device=dev) for _ in range(2)]
+        fin_len = [torch.zeros((B, k), dtype=i32, device=dev) for _ in range(2)]
+        done = torch.zeros(B, dtype=i32, device=dev)
+        next_tok = torch.zeros(BK, dtype=i64, device=dev)
+        cur = 0
+
+        def beam_step(logits, score, n):
+            nonlocal cur
+            ops.beam_candidates(logits, score, B, k, out=cand)
+            if self.beam_trace is not None:   # tests / tools: every step's candidate lists (score, token, parent), copied
+                self.beam_trace.append(tuple(c.clone() for c in cand))
+            o = 1 - cur
+            ops.beam_update(cand, B, k, n, cap, eos, pad, early, length_penalty, run_score, (anc[cur], anc[o]), (hist[cur], hist[o]),
+                            (fin_tok[cur], fin_tok[o]), (fin_score[cur], fin_score[o]), (fin_len[cur], fin_len[o]), done, next_tok)
+            cur = o
+
+        if not use_cache:
+            # the reference's literal recompute: the B * k beams' full sequences through the stack every step (HF expands every
+            # sample k times; beams 1 .. k-1 start at -1e9, so the first step's candidates all come from beam 0)
+            feats_k, ids_k, am_k = feats.repeat_interleave(k, 0), ids.repeat_interleave(k, 0), am.repeat_interleave(k, 0)
+            score0 = torch.full((B, k), -1e9, dtype=f32, device=dev)
+            score0[:, 0] = 0.0
+            score0 = score0.view(BK)
+            for n in range(max_new):
+                cur_ids = torch.cat([ids_k, hist[cur][:, :n]], dim=1)
+                cur_am = torch.cat([am_k, torch.ones((BK, n), dtype=i64, device=dev)], dim=1)
+                st = self._engine_forward(feats_k, cur_ids, cur_am, None, False, train=False)
+                beam_step(st["logits"][:, -1, :], score0 if n == 0 else run_score, n)
+        else:
+            # one prefill per sample: its last-position logits are the first step's (only beam 0 is live there), its K/V the prefix
+            # that the sample's k beams share
+            cache, first_logits = self._prefill(feats, ids, am, max_new, beams=k)
+            if not cache.prerot:
+                raise NotImplementedError("the cached beam search needs the pre-rotated cache (rotary dims % 16 == 0, head size 64 / 128 / 256)")
+            beam_step(first_logits, torch.zeros(B, dtype=f32, device=dev), 0)
+            for t in range(max_new - 1):
+                cache.anc = anc[cur]
+                beam_step(self._engine_decode_step(next_tok, t, cache), run_score, t + 1)
+        lens = fin_len[cur][:, :nrs]
+        n_keep = int(lens.max())   # the one host synchronisation
+        seqs = torch.cat([ids.repeat_interleave(nrs, 0), fin_tok[cur][:, :nrs, :n_keep].reshape(B * nrs, n_keep)], dim=1)
+        if return_dict:
+            return BeamSearchOutput(sequences=seqs, sequences_scores=fin_score[cur][:, :nrs].reshape(B * nrs).clone())
+        return seqs
+
+    def _engine_decode_step(self, tokens: torch.Tensor, t: int, cache: "_DecodeCache") -> torch.Tensor:
+        """One token per sample through the stack: ``tokens`` [B] sit at position S0 + t; returns the logits [B, V]."""
+        cfg, cd = self.config, self.compute_dtype
+        h, H, D, L = cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim, cfg.num_hidden_layers
+        B, S0, rot = cache.B, cache.S0, cfg.rotary_ndims
+        cos, sin = self.rotary_tables(S0 + cache.cap)
+        wts, pars = self._tensors(0), self._tensors(1)   # compute-dtype weights; fp32 LayerNorm parameters, biases and embedding
+        Wo, Po = wts.outer, pars.outer
+        x = Po.embed_in.index_select(0, tokens)  # fp32 residual stream row
+
+        def attend(i):
+            # (greedy: one cache row per sample; beam search: `anc` names the slot holding each row of a beam's history.  A fused cache
+            #  is always pre-rotated, _DecodeCache)
+            if cache.anc is None:
+                return ops.attn_decode(cache.prefix[i], S0, cache.new[i], t, B, H, D, rot, cos, sin, cache.attention_mask, prerot=cache.prerot)
+            return ops.attn_decode_beam(cache.prefix[i], S0, cache.new[i], t, B, cache.beams, cache.anc, H, D, rot, cos, sin, cache.attention_mask)
+
+        for i in range(L):
+            w, p = wts.layers[i], pars.layers[i]
+            if cache.fused:
+                # three launches per layer (csrc/decode.hip): [LN1 | LN2] + QKV + fc1/GELU, attention over the pre-rotated cache, and
+                # dense + fc2 + both residuals as one product over the concatenated K
+                a = ops.decode_ln_qkv_fc1(x, p.ln1_w, p.ln1_b, p.ln2_w, p.ln2_b, cfg.layer_norm_eps, w.qkv_w, p.qkv_b, cache.new[i][:, t, :],
+                                          w.fc1_w, p.fc1_b)
+                x = ops.decode_out(x, attend(i), a, w.dense_w, p.dense_b, w.fc2_w, p.fc2_b, cache.workspace, out=x)
+                continue
+            ln1, ln2, _, _ = ops.layernorm_fwd(x, p.ln1_w, p.ln1_b, p.ln2_w, p.ln2_b, cfg.layer_norm_eps, cd, save_stats=False)
+            # the new token's q | k | v row goes straight into the cache (row t of the per-layer [B, cap, 3*H*D] tensor)
+            ops.gemm(ln1, w.qkv_w, False, True, bias=p.qkv_b, out=cache.new[i][:, t, :])
+            attn = ops.gemm(attend(i), w.dense_w, False, True, bias=p.dense_b, out_dtype=cd)
+            a = ops.gemm(ln2, w.fc1_w, False, True, bias=p.fc1_b, epilogue=EPI_GELU)
+            x = ops.gemm(a, w.fc2_w, False, True, bias=p.fc2_b, out_dtype=torch.float32, res1=attn, res2=x)
+        if cache.fused and B * cache.beams <= 32 and h == 1024 and cfg.vocab_size % 32 == 0 and cfg.vocab_size >= 16384:
+            # final LayerNorm + LM head as one persistent launch (decode_head_kernel: rows normalised once per CU, the vocabulary's
+            # weight strips streamed through LDS): 24 us against 48 for LayerNorm + the skinny product at V = 50k
+            return ops.decode_ln_linear(x, Po.final_ln_w, Po.final_ln_b, cfg.layer_norm_eps, Wo.embed_out)
+        # (other shapes: the one-slab-per-block forms of ops.decode_ln_linear are no faster than the two launches below)
+        lnf, _, _, _ = ops.layernorm_fwd(x, Po.final_ln_w, Po.final_ln_b, None, None, cfg.layer_norm_eps, cd, save_stats=False)
+        return ops.gemm(lnf, Wo.embed_out, False, True)
+
+
+class _DecodeCache:
+    """K/V cache of a greedy decode: per layer the prefill's [B*S0, 3*H*D] fused-QKV output (kept as written -- no split, no
+    transpose, k un-rotated) and a [B, cap, 3*H*D] tensor that receives one row per generated token."""
+
+    def __init__(self, model, prefix, B: int, S0: int, cap: int, attention_mask: torch.Tensor, prerotate: bool = True, fused: bool = True,
+                 prefix_storage: Optional[torch.Tensor] = None, beams: int = 1):
+        self.prefix, self.B, self.S0, self.cap, self.attention_mask = prefix, B, S0, max(1, cap), attention_mask
+        self.prefix_storage = prefix_storage   # [L, B*S0, 3h] holding every entry of `prefix` (then one rotation launch serves all layers)
+        # beam search: the prefix stays one per sample, the generated rows are one per beam slot ([B*beams, cap, 3h]); `anc` (int32
+        # [B*beams, cap], set by the caller before each step) names the slot holding each row of a beam's history
+        self.beams, self.anc = beams, None
+        rows = B * beams
+        cfg = model.config
+        n = 3 * cfg.num_attention_heads * cfg.head_dim
+        self.new = [torch.zeros((rows, self.cap, n), dtype=prefix[0].dtype, device=prefix[0].device) for _ in prefix]
+        # Pre-rotated cache (round 4): once the prefill's attention has read the un-rotated keys, rotate them in place -- every decode step
+        # then loads k and v only (mafed_attn_decode_prerot).  Needs rot % 16 == 0 and an MFMA head size (every VLPythia preset).
+        self.prerot = bool(prerotate) and cfg.rotary_ndims % 16 == 0 and cfg.head_dim in (64, 128, 256)
+        self._model = model
+        # fused decode layer (csrc/decode.hip): bf16 mode over the pre-rotated cache, shapes per mafed_decode_supported
+        # (more than 64 rows -- 64-row blocks of the fused kernels -- only for beam search: a greedy batch of B > 64 keeps the six launches)
+        self.fused = (bool(fused) and self.prerot and prefix[0].dtype == torch.bfloat16 and (rows <= 64 or beams > 1)
+                      and ops.decode_supported(rows, cfg.hidden_size, cfg.intermediate_size))
+        self.workspace = ops.decode_out_workspace(rows, cfg.hidden_size, prefix[0].device) if self.fused else None
+        if self.prerot:
+            self.rotate_prefix()
+
+    def rotate_prefix(self) -> None:
+        """Rotate the prefix keys in place (call once per prefill: the prefix must hold what the QKV GEMMs wrote)."""
+        cfg = self._model.config
+        cos, sin = self._model.rotary_tables(self.S0 + self.cap)
+        whole = self.prefix_storage   # every layer's prefix in ONE tensor: one launch for all
+        if whole is not None:
+            ops.rotate_k_rows_(whole, whole.shape[0] * self.B, self.S0, cfg.num_attention_heads, cfg.head_dim, cfg.rotary_ndims, cos, sin)
+            return
+        for p in self.prefix:
+            ops.rotate_k_rows_(p, self.B, self.S0, cfg.num_attention_heads, cfg.head_dim, cfg.rotary_ndims, cos, sin)
+
+
+class _GraphedDecode:
+    """Greedy decode steps 1 .. max_new-1 for one (B, T, max_new) shape as a single hipGraph.  Static buffers: the per-layer
+    K/V cache (prefix written by the prefill's QKV GEMMs through ``qkv_out``, plus the per-token rows), the prompt mask, the
+    prefill's last-position logits, the ``unfinished`` flags and the generated tokens."""
+
+    def __init__(self, model, B: int, T: int, max_new: int, eos_token_id, pad_token_id):
+        cfg = model.config
+        dev, cd = model.flat_params.device, model.compute_dtype
+        S0 = cfg.num_vision_tokens + T
+        self.model, self.B, self.T, self.S0, self.max_new = model, B, T, S0, max_new
+        store = model._prefix_store(B, T)
+        self.am = torch.ones((B, T), dtype=torch.int64, device=dev)
+        self.first_logits = torch.zeros((B, cfg.vocab_size), dtype=cd if cd != torch.float32 else torch.float32, device=dev)
+        self.tokens = torch.zeros((B, max_new), dtype=torch.int64, device=dev)
+        model.rotary_tables(S0 + max(1, max_new))  # built (host -> device copy) before the capture, not inside it
+        self.cache = _DecodeCache(model, list(store.unbind(0)), B, S0, max_new, self.am, fused=model.fused_decode,
+                                  prefix_storage=store)   # (rotates the still-empty prefix once: harmless)
+
+        def body():
+            unfinished = torch.ones(B, dtype=torch.int64, device=dev)
+            logits = self.first_logits
+            for t in range(max_new):
+                nxt, unfinished = _greedy_pick(logits, unfinished, eos_token_id, pad_token_id)
+                self.tokens[:, t] = nxt
+                if t + 1 < max_new:
+                    logits = model._engine_decode_step(nxt, t, self.cache)
+
+        # one eager pass on a side stream (lazy initialisations must not happen inside the capture), then the capture
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            body()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            body()
+
+    def run(self, feats, ids, am) -> torch.Tensor:
+        m = self.model
+        st = m._engine_forward(feats, ids, am, None, False, train=False, qkv_out=self.cache.prefix, last_only=True)
+        if self.cache.prerot:
+            self.cache.rotate_prefix()   # this prefill's keys, rotated in place for the captured steps
+        self.am.copy_(am)
+        self.first_logits.copy_(st["logits"][:, -1, :])
+        self.graph.replay()
+        return self.tokens.clone()

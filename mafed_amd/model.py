@@ -23,6 +23,7 @@ from __future__ import annotations
 import copy
 import math
 from dataclasses import dataclass, field
+from collections import namedtuple
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import os as _os
@@ -32,6 +33,7 @@ from torch import nn
 
 from mafed_amd import ops
 from mafed_amd._lib import EPI_GELU, EPI_GELU_BWD, EPI_NONE
+from mafed_amd.generation import BeamSearchOutput, GenerationMixin, _DecodeCache, _GraphedDecode  # noqa: F401  (re-exported)
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -89,14 +91,6 @@ class CausalLMOutput:
         return tuple(v for v in (self.loss, self.logits, self.hidden_states) if v is not None)[i]
 
 
-@dataclass
-class BeamSearchOutput:
-    """``generate(..., return_dict_in_generate=True)``: the fields of transformers' GenerateBeamDecoderOnlyOutput that are produced."""
-
-    sequences: torch.Tensor
-    sequences_scores: Optional[torch.Tensor] = None
-
-
 # parameter holders: modules without a forward; the tree only exists so that state-dict names match the reference
 class _Affine(nn.Module):
     def __init__(self, w: nn.Parameter, b: Optional[nn.Parameter]):
@@ -131,17 +125,41 @@ def is_no_decay(name: str) -> bool:
     return any(k in name for k in NO_DECAY_KEYS)
 
 
+# Record field -> state-dict name (behind ``gpt_neox.layers.{i}.`` for a layer's tensors).  In a layer the four (matrix, bias) pairs follow the two
+# LayerNorms in slot order 0 .. 3: the order of ``dw_sumsq`` and of ``layer_matrix_range``.
+LAYER_FIELD_NAMES = {"ln1_w": "input_layernorm.weight", "ln1_b": "input_layernorm.bias",
+                     "ln2_w": "post_attention_layernorm.weight", "ln2_b": "post_attention_layernorm.bias",
+                     "qkv_w": "attention.query_key_value.weight", "qkv_b": "attention.query_key_value.bias",
+                     "dense_w": "attention.dense.weight", "dense_b": "attention.dense.bias",
+                     "fc1_w": "mlp.dense_h_to_4h.weight", "fc1_b": "mlp.dense_h_to_4h.bias",
+                     "fc2_w": "mlp.dense_4h_to_h.weight", "fc2_b": "mlp.dense_4h_to_h.bias"}
+OUTER_FIELD_NAMES = {"proj0_w": "vision_embed_tokens.0.weight", "proj0_b": "vision_embed_tokens.0.bias",
+                     "proj2_w": "vision_embed_tokens.2.weight", "proj2_b": "vision_embed_tokens.2.bias",
+                     "embed_in": "gpt_neox.embed_in.weight", "final_ln_w": "gpt_neox.final_layer_norm.weight",
+                     "final_ln_b": "gpt_neox.final_layer_norm.bias", "embed_out": "embed_out.weight"}
+OuterTensors = namedtuple("OuterTensors", list(OUTER_FIELD_NAMES))   # projector, token embedding, final LayerNorm, LM head
+
+
+class LayerTensors(namedtuple("LayerTensors", list(LAYER_FIELD_NAMES))):
+    """The tensors of one GPT-NeoX layer as views of one flat buffer (weights in compute dtype, fp32 parameters or gradients)."""
+    __slots__ = ()
+
+    def matrix(self, slot: int) -> torch.Tensor:
+        return self[4 + 2 * slot]
+
+    def bias(self, slot: int) -> torch.Tensor:
+        return self[5 + 2 * slot]
+
+
+def layer_tensor_name(i: int, field: str) -> str:
+    return f"gpt_neox.layers.{i}." + LAYER_FIELD_NAMES[field]
+
+
 def _param_specs(cfg: VLPythiaConfig) -> List[Tuple[str, Tuple[int, ...]]]:
     h, ff, V, dv = cfg.hidden_size, cfg.intermediate_size, cfg.vocab_size, cfg.vision_hidden_size
+    layer = LayerTensors((h,), (h,), (h,), (h,), (3 * h, h), (3 * h,), (h, h), (h,), (ff, h), (ff,), (h, ff), (h,))._asdict()
     out: List[Tuple[str, Tuple[int, ...]]] = [("gpt_neox.embed_in.weight", (V, h))]
-    for i in range(cfg.num_hidden_layers):
-        p = f"gpt_neox.layers.{i}."
-        out += [(p + "input_layernorm.weight", (h,)), (p + "input_layernorm.bias", (h,)),
-                (p + "post_attention_layernorm.weight", (h,)), (p + "post_attention_layernorm.bias", (h,)),
-                (p + "attention.query_key_value.weight", (3 * h, h)), (p + "attention.query_key_value.bias", (3 * h,)),
-                (p + "attention.dense.weight", (h, h)), (p + "attention.dense.bias", (h,)),
-                (p + "mlp.dense_h_to_4h.weight", (ff, h)), (p + "mlp.dense_h_to_4h.bias", (ff,)),
-                (p + "mlp.dense_4h_to_h.weight", (h, ff)), (p + "mlp.dense_4h_to_h.bias", (h,))]
+    out += [(layer_tensor_name(i, f), shape) for i in range(cfg.num_hidden_layers) for f, shape in layer.items()]
     out += [("gpt_neox.final_layer_norm.weight", (h,)), ("gpt_neox.final_layer_norm.bias", (h,)),
             ("embed_out.weight", (V, h)),
             ("vision_embed_tokens.0.weight", (h, dv)), ("vision_embed_tokens.0.bias", (h,)),
@@ -149,7 +167,21 @@ def _param_specs(cfg: VLPythiaConfig) -> List[Tuple[str, Tuple[int, ...]]]:
     return out
 
 
-class VLPythiaForCausalLM(nn.Module):
+class BufferViews:
+    """Every tensor of one flat buffer ``src`` as a view: ``layers[i]`` (LayerTensors), ``outer`` (OuterTensors) and ``by_name`` (state-dict
+    name -> the same view objects).  Raises if a record field names a tensor that ``offsets`` does not hold, or the records miss one."""
+    __slots__ = ("src", "layers", "outer", "by_name")
+
+    def __init__(self, src: torch.Tensor, offsets: Dict[str, Tuple[int, int, Tuple[int, ...]]], n_layers: int):
+        self.src = src
+        self.by_name = {name: src[o:o + n].view(shape) for name, (o, n, shape) in offsets.items()}
+        self.layers = [LayerTensors(*(self.by_name[layer_tensor_name(i, f)] for f in LayerTensors._fields)) for i in range(n_layers)]
+        self.outer = OuterTensors(*(self.by_name[name] for name in OUTER_FIELD_NAMES.values()))
+        if len(LayerTensors._fields) * n_layers + len(OuterTensors._fields) != len(offsets):
+            raise KeyError("the parameter records do not cover every tensor of the flat layout")
+
+
+class VLPythiaForCausalLM(GenerationMixin, nn.Module):
     """MI355X-native counterpart of ``VLCLIPGPTNeoXForCausalLM`` for the training hot path."""
 
     def __init__(self, config: VLPythiaConfig, compute_dtype: torch.dtype = torch.bfloat16, device: Any = None,
@@ -200,15 +232,40 @@ class VLPythiaForCausalLM(nn.Module):
         # {"pre" | ("layer", i) | "head": event} left by FlatAdamW.apply_pipelined: the forward waits chunk by chunk
         self._param_events = None
         self._side = None
-        self._view_cache: Dict[Tuple[int, str], torch.Tensor] = {}
+        self._hook_zero_t: Optional[torch.Tensor] = None   # _hook_zero(): a zero scalar on this replica's device, filled once
+        # [weights in compute dtype, fp32 parameters, gradients] as BufferViews: built on first use, dropped by _apply, rebuilt when a flat
+        # buffer object was replaced (_tensors)
+        self._views: List[Optional[BufferViews]] = [None, None, None]
+        self._tensors(1)   # (built here once: a record field that names no tensor of the layout fails at construction, on any machine)
         self.overlap_param_grads = True  # run dW / bias-gradient kernels on side_stream() concurrently with the dX chain
         # bf16: the four weight gradients dW += dY^T.X of `dw_group_layers` consecutive layers are deferred and launched as ONE grouped
         # persistent GEMM (mafed_gemm_grouped) on the main stream: 2 layers = 768 tiles of 128 x 256 = three whole rounds of the
         # 256 CUs without split-K (one layer's products alone leave a third to seven eighths of the chip idle); 0 = one launch each
         self.dw_group_layers = 2
+        self._dw_fuse_cache: Dict[Tuple[int, int], bool] = {}   # _dw_group_fuses_squares: (rows, dw_group_layers) -> the library's answer
         self.sparse_lm_head = True          # batches that carry ``max_label_rows`` get the row-sparse LM head in training
-        self.beam_trace: Optional[List[Any]] = None   # a list: generate(num_beams > 1) appends every step's candidate lists to it
+        # device flag of the last row-sparse training forward (written there; read by callers / tests): 1 = rows were dropped, the loss is NaN
+        self.last_label_overflow: Optional[torch.Tensor] = None
         self.defer_ln_param_reduce = True   # LayerNorm parameter-gradient reduction on a side stream (needs overlap_param_grads)
+        # generation (mafed_amd/generation.py)
+        self.beam_trace: Optional[List[Any]] = None   # a list: generate(num_beams > 1) appends every step's candidate lists to it
+        self.fused_decode = True    # written by callers (tests, tools/decode_bench.py): False = the six-launch decode layer; read when a decode cache is built
+        self._decode_graphs: Dict[Tuple, Any] = {}   # written and read by generate(use_graph=True): (B, T, max_new, eos, pad) -> _GraphedDecode
+        # The hand-over of a backward sweep (_engine_backward_impl) between Trainer, the optimiser and the model.  Before the sweep,
+        # Trainer._device_step sets `contended_backward` and `grad_overwrite` and, with the incremental norm, installs the hook of
+        # FlatAdamW.begin_incremental_norm as `grad_ready_hook` (that call sets `dw_sumsq`; Trainer clears it otherwise).  The sweep counts
+        # itself in `_bw_serial`, zeroes the layers' matrix gradients first if `_dw_stale` and it accumulates, clears `_dw_stale`, records in
+        # `_dw_sumsq_used` whether its weight-gradient GEMMs fill `dw_sumsq`, and leaves `dx_chain_event`.  Afterwards the norm hook takes the
+        # fused squares only if `_dw_sumsq_used == _bw_serial`, FlatAdamW.clip_grad_norm_ takes the hook's partials only if every range
+        # reported under the current `_bw_serial`, Trainer resets `grad_overwrite` and takes `dx_chain_event`, and an optimiser pass that
+        # leaves the matrices un-zeroed sets `_dw_stale`.
+        self.contended_backward: Any = False   # Trainer (bench.py, tests) writes, the sweep reads: False / None, True / "128x128" or "ticketed" GEMM kernels beside collectives
+        self.grad_overwrite = False   # Trainer writes around a window's first backward, the sweep reads: its grouped dW GEMMs write (beta = 0) the matrix gradients
+        self._dw_stale = False        # FlatAdamW._apply_chunks(skip_matrix_zero) sets, the sweep and zero_grad clear: the matrix gradients hold the last window's values
+        self.dw_sumsq: Optional[torch.Tensor] = None   # begin_incremental_norm / Trainer write, the sweep and the norm hook read: fp32 [L, 4, 16] slots of the norm partials
+        self._dw_sumsq_used: Optional[int] = None      # the sweep writes, the norm hook reads: `_bw_serial` of the last sweep if it filled `dw_sumsq`
+        self._bw_serial = 0                            # the sweep increments; the norm hook and clip_grad_norm_ read
+        self.dx_chain_event: Optional[torch.cuda.Event] = None   # the sweep writes (end of its dX chain), Trainer takes it and resets it to None
         self.reset_parameters(seed)
         self.register_load_state_dict_post_hook(lambda m, ik: setattr(m, "_shadow_dirty", True))
 
@@ -226,17 +283,17 @@ class VLPythiaForCausalLM(nn.Module):
         neox.embed_in = _Affine(params["gpt_neox.embed_in.weight"], None)
         layers = nn.ModuleList()
         for i in range(cfg.num_hidden_layers):
-            pre = f"gpt_neox.layers.{i}."
+            t = LayerTensors(*(params[layer_tensor_name(i, f)] for f in LayerTensors._fields))
             lyr = nn.Module()
-            lyr.input_layernorm = _Affine(params[pre + "input_layernorm.weight"], params[pre + "input_layernorm.bias"])
-            lyr.post_attention_layernorm = _Affine(params[pre + "post_attention_layernorm.weight"], params[pre + "post_attention_layernorm.bias"])
+            lyr.input_layernorm = _Affine(t.ln1_w, t.ln1_b)
+            lyr.post_attention_layernorm = _Affine(t.ln2_w, t.ln2_b)
             att = nn.Module()
-            att.query_key_value = _Affine(params[pre + "attention.query_key_value.weight"], params[pre + "attention.query_key_value.bias"])
-            att.dense = _Affine(params[pre + "attention.dense.weight"], params[pre + "attention.dense.bias"])
+            att.query_key_value = _Affine(t.qkv_w, t.qkv_b)
+            att.dense = _Affine(t.dense_w, t.dense_b)
             lyr.attention = att
             mlp = nn.Module()
-            mlp.dense_h_to_4h = _Affine(params[pre + "mlp.dense_h_to_4h.weight"], params[pre + "mlp.dense_h_to_4h.bias"])
-            mlp.dense_4h_to_h = _Affine(params[pre + "mlp.dense_4h_to_h.weight"], params[pre + "mlp.dense_4h_to_h.bias"])
+            mlp.dense_h_to_4h = _Affine(t.fc1_w, t.fc1_b)
+            mlp.dense_4h_to_h = _Affine(t.fc2_w, t.fc2_b)
             lyr.mlp = mlp
             layers.append(lyr)
         neox.layers = layers
@@ -312,7 +369,7 @@ class VLPythiaForCausalLM(nn.Module):
                 p.data = self.flat_params[o:o + n].view(shape)
                 p.grad = self.flat_grads[o:o + n].view(shape)
             self._rot_cache.clear()
-            self._view_cache.clear()
+            self._views = [None, None, None]
             self._side = None
             self._shadow_dirty = True
             enc = self.vision_encoder if not isinstance(self.vision_encoder, _FrozenVision) else getattr(self.vision_encoder, "encoder", None)
@@ -337,7 +394,7 @@ class VLPythiaForCausalLM(nn.Module):
 
     def _hook_zero(self) -> torch.Tensor:
         """A zero scalar of this replica's device, filled once (value of the 0-dim hook outputs / gradients nobody reads)."""
-        z = getattr(self, "_hook_zero_t", None)
+        z = self._hook_zero_t
         if z is None or z.device != self.flat_params.device:
             z = self._hook_zero_t = torch.zeros(1, device=self.flat_params.device)
         return z
@@ -349,25 +406,25 @@ class VLPythiaForCausalLM(nn.Module):
             ops.cast(self.flat_params, torch.bfloat16, out=self.flat_shadow)
         self._shadow_dirty = False
 
-    def _view(self, cache_id: int, src: torch.Tensor, name: str) -> torch.Tensor:
-        """Cached view of one tensor inside a flat buffer (the host path looks these up ~40 times per layer per step)."""
-        key = (cache_id, name)
-        v = self._view_cache.get(key)
-        if v is None or v._base is not src:
-            o, n, shape = self._offsets[name]
-            v = src[o:o + n].view(shape)
-            self._view_cache[key] = v
+    def _tensors(self, which: int) -> BufferViews:
+        """The per-layer / outer records over one flat buffer: 0 = weights in compute dtype (the bf16 shadow, or the parameters in
+        fp32 mode), 1 = fp32 parameters, 2 = gradients.  The engine fetches each once per forward, backward or decode step."""
+        src = (self.flat_shadow if self.compute_dtype == torch.bfloat16 else self.flat_params, self.flat_params, self.flat_grads)[which]
+        v = self._views[which]
+        if v is None or v.src is not src:
+            v = self._views[which] = BufferViews(src, self._offsets, self.config.num_hidden_layers)
         return v
 
+    # by state-dict name, for callers outside the engine (tests, tools)
     def _w(self, name: str) -> torch.Tensor:
         """Weight in compute dtype."""
-        return self._view(0, self.flat_shadow if self.compute_dtype == torch.bfloat16 else self.flat_params, name)
+        return self._tensors(0).by_name[name]
 
     def _p(self, name: str) -> torch.Tensor:
-        return self._view(1, self.flat_params, name)
+        return self._tensors(1).by_name[name]
 
     def _g(self, name: str) -> torch.Tensor:
-        return self._view(2, self.flat_grads, name)
+        return self._tensors(2).by_name[name]
 
     def zero_grad(self, set_to_none: bool = False):  # gradients are views of the flat buffer: always zero in place
         self.flat_grads.zero_()
@@ -376,11 +433,10 @@ class VLPythiaForCausalLM(nn.Module):
     def layer_matrix_range(self, i: int) -> Tuple[int, int]:
         """Flat range of layer i's four weight matrices (query_key_value, dense, dense_h_to_4h, dense_4h_to_h: contiguous, behind the layer's
         two LayerNorm weights in the decayed segment) -- the part of the gradient buffer that the grouped weight-gradient GEMMs write whole."""
-        pre = f"gpt_neox.layers.{i}."
-        lo = self._offsets[pre + "attention.query_key_value.weight"][0]
-        o, n, _ = self._offsets[pre + "mlp.dense_4h_to_h.weight"]
-        names = [pre + "attention.query_key_value.weight", pre + "attention.dense.weight", pre + "mlp.dense_h_to_4h.weight", pre + "mlp.dense_4h_to_h.weight"]
-        assert all(lo <= self._offsets[k][0] < o + n for k in names)
+        grads = self._tensors(2)
+        first = [grads.layers[i].matrix(slot).storage_offset() - grads.src.storage_offset() for slot in range(4)]
+        lo, o, n = first[0], first[3], grads.layers[i].matrix(3).numel()
+        assert all(lo <= k < o + n for k in first)
         return lo, o + (n + 63) // 64 * 64
 
     def _zero_layer_matrices(self, layers) -> None:
@@ -485,243 +541,6 @@ class VLPythiaForCausalLM(nn.Module):
         ops.cka_pool(st["hidden"][1:], attention_mask, cfg.num_vision_tokens, out, rows)
         return out
 
-    # ---- greedy decode -----------------------------------------------------------------------
-    @torch.no_grad()
-    def generate(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
-                 patch_embeddings: Optional[torch.Tensor] = None, max_new_tokens: int = 10, use_cache: bool = True,
-                 pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = 0, do_sample: bool = False,
-                 return_step_logits: bool = False, use_graph: bool = False, num_beams: int = 1, length_penalty: float = 1.0,
-                 early_stopping: Any = False, num_return_sequences: int = 1, return_dict_in_generate: bool = False, **kwargs):
-        """Greedy search with the call signature the reference validation uses (mafed/model/vqa_cont_learner.py:260-267,
-        mafed/utils/eval_utils.py:170-177: ``generate(input_ids=, attention_mask=, pixel_values=, max_new_tokens=10,
-        use_cache=False, pad_token_id=eos)``) and HF ``greedy_search`` semantics (transformers 4.37.1): next token = argmax of
-        the last position, finished rows keep emitting ``pad_token_id``, the attention mask grows by ones, generation stops
-        when every row has produced ``eos_token_id`` (GPT-NeoX / Pythia: 0) or after ``max_new_tokens``.  Positions are
-        ``arange`` over [image | text | generated].
-
-        ``use_cache=False`` is the reference's literal behaviour -- the whole 256 + T + t prefix is pushed through the stack
-        again for every token.  ``use_cache=True`` (default here) runs the prefix once, keeps each layer's fused-QKV output as
-        the K/V cache and then moves ONE row per sample through the stack per token (``mafed_attn_decode``); both produce the
-        same tokens.  Returns [B, T + n_generated] like HF; with ``return_step_logits`` also the fp32 last-position logits of
-        every step [n, B, V].
-
-        ``num_beams = k > 1``: beam search with HF ``GenerationMixin._beam_search`` semantics (transformers 5.x; ``length_penalty``,
-        ``early_stopping`` True / False / "never", ``num_return_sequences`` <= k <= 8) -> [B * num_return_sequences, T + n], rows padded
-        with ``pad_token_id`` up to the longest returned hypothesis; ``return_dict_in_generate`` adds the length-normalised
-        ``sequences_scores`` (a beam-search option: the greedy path returns its tensor as before).  ``use_cache=False`` recomputes the B * k beams' full sequences every step; ``use_cache=True`` prefills
-        each sample once and decodes its k beams over the shared prefix (``_beam_search``).  Not implemented: sampling (beam-sample
-        included), graph capture of the beam loop, diverse / constrained beam search."""
-        if do_sample:
-            raise NotImplementedError("sampling (do_sample=True, beam-sample included) is not implemented: greedy or beam search only")
-        if kwargs.get("num_beam_groups") not in (None, 1) or kwargs.get("constraints") is not None or kwargs.get("force_words_ids") is not None:
-            raise NotImplementedError("diverse / constrained beam search (num_beam_groups, constraints, force_words_ids) is not implemented")
-        if not isinstance(num_beams, int) or num_beams < 1 or num_beams > 8:
-            raise ValueError(f"num_beams must be an int in 1 .. 8, got {num_beams!r}")
-        if num_return_sequences < 1 or num_return_sequences > num_beams:
-            raise ValueError(f"num_return_sequences ({num_return_sequences}) must be in 1 .. num_beams ({num_beams})")
-        if input_ids is None or (pixel_values is None and patch_embeddings is None):
-            raise ValueError("generate needs input_ids and pixel_values / patch_embeddings")
-        if num_beams > 1:
-            if use_graph:
-                raise NotImplementedError("use_graph=True (hipGraph capture) is not implemented for beam search")
-            if return_step_logits:
-                raise NotImplementedError("return_step_logits is a greedy-search option")
-            if max_new_tokens < 1:
-                raise ValueError(f"beam search needs max_new_tokens >= 1, got {max_new_tokens}")
-            if early_stopping not in (False, True, "never"):
-                raise ValueError(f"early_stopping must be True, False or 'never', got {early_stopping!r}")
-            return self._beam_search(input_ids, attention_mask, pixel_values, patch_embeddings, num_beams, max_new_tokens, use_cache,
-                                     pad_token_id, eos_token_id, float(length_penalty), early_stopping, num_return_sequences,
-                                     return_dict_in_generate)
-        dev = self.flat_params.device
-        feats = (patch_embeddings if patch_embeddings is not None else self.get_patch_embeddings(pixel_values)).to(dev).contiguous()
-        ids = input_ids.to(dev, torch.int64).contiguous()
-        am = (attention_mask if attention_mask is not None else torch.ones_like(input_ids)).to(dev, torch.int64).contiguous()
-        if eos_token_id is not None and pad_token_id is None:
-            pad_token_id = eos_token_id  # HF's fallback for open-end generation
-        B, T = ids.shape
-        unfinished = torch.ones(B, dtype=torch.int64, device=dev)
-        new_tokens, step_logits = [], []
-        if not hasattr(self, "_decode_graphs"):
-            self._decode_graphs = {}
-
-        def pick(last_logits):
-            nonlocal unfinished
-            nxt = last_logits.float().argmax(dim=-1)
-            if eos_token_id is not None:
-                nxt = nxt * unfinished + pad_token_id * (1 - unfinished)
-                unfinished = unfinished * (nxt != eos_token_id).to(torch.int64)
-            new_tokens.append(nxt)
-            if return_step_logits:
-                step_logits.append(last_logits.float())
-            return nxt
-
-        if not use_cache:
-            cur_ids, cur_am = ids, am
-            for _ in range(max_new_tokens):
-                st = self._engine_forward(feats, cur_ids, cur_am, None, False, train=False)
-                nxt = pick(st["logits"][:, -1, :])
-                cur_ids = torch.cat([cur_ids, nxt[:, None]], dim=1)
-                cur_am = torch.cat([cur_am, torch.ones_like(nxt)[:, None]], dim=1)
-        elif use_graph and not return_step_logits and max_new_tokens > 1:
-            # opt-in: the nine one-row-per-sample steps (~150 launches of 5-20 us kernels each) captured once per (B, T, max_new)
-            # into a hipGraph whose K/V cache lives at fixed addresses (the prefill's QKV GEMMs write straight into it).  It
-            # takes the host out of the loop; on an idle host it measures the same as eager launches (24.1 vs 24.2 ms at
-            # 410M / B = 32): the steps are bound by the GPU-side cost of that many small kernels.
-            gd = self._decode_graphs.get((B, T, max_new_tokens, eos_token_id, pad_token_id))
-            if gd is None:
-                gd = self._decode_graphs[(B, T, max_new_tokens, eos_token_id, pad_token_id)] = _GraphedDecode(
-                    self, B, T, max_new_tokens, eos_token_id, pad_token_id)
-            gen_all = gd.run(feats, ids, am)
-            new_tokens = list(gen_all.unbind(1))
-        else:
-            # every layer's fused-QKV output lands in one tensor (the K/V cache's prefix): its keys are then rotated by ONE launch
-            cfg_ = self.config
-            S_ = cfg_.num_vision_tokens + T
-            store = torch.empty((cfg_.num_hidden_layers, B * S_, 3 * cfg_.num_attention_heads * cfg_.head_dim), dtype=self.compute_dtype, device=dev)
-            st = self._engine_forward(feats, ids, am, None, False, train=False, qkv_out=list(store.unbind(0)), last_only=True)
-            cache = _DecodeCache(self, list(store.unbind(0)), B, st["S"], max_new_tokens, am, fused=getattr(self, "fused_decode", True),
-                                 prefix_storage=store)
-            nxt = pick(st["logits"][:, -1, :])
-            for t in range(max_new_tokens - 1):
-                nxt = pick(self._engine_decode_step(nxt, t, cache))
-        gen = torch.stack(new_tokens, dim=1)
-        if eos_token_id is not None:
-            # HF leaves the loop as soon as every row has finished: the output is as long as the slowest row needed
-            done = (gen == eos_token_id).to(torch.int64).cumsum(1).clamp_(max=1)       # 1 from the first eos on
-            first = (done.shape[1] - done.sum(1)) + done[:, -1]                        # tokens up to and including the first eos
-            n_keep = int(first.max().clamp_(max=gen.shape[1]))
-            gen = gen[:, :n_keep]
-            step_logits = step_logits[:n_keep]
-        out = torch.cat([ids, gen], dim=1)
-        if return_step_logits:
-            return out, torch.stack(step_logits, dim=0)
-        return out
-
-    def _beam_search(self, input_ids, attention_mask, pixel_values, patch_embeddings, k: int, max_new: int, use_cache: bool, pad_token_id,
-                     eos_token_id, length_penalty: float, early_stopping, nrs: int, return_dict: bool):
-        """Beam search (generate(num_beams=k)); every decision on the device (csrc/beam.hip), one host synchronisation at the end.
-        Per step: mafed_beam_candidates (top 2k of log_softmax + running score per sample) and mafed_beam_update (finished set,
-        continuing beams, early stopping, ancestry / history rewrite).  The loop runs to max_new_tokens like the greedy path: a sample
-        whose result is final stops changing (HF leaves the loop once every sample is such), and the output is cut at the end."""
-        cfg, dev = self.config, self.flat_params.device
-        feats = (patch_embeddings if patch_embeddings is not None else self.get_patch_embeddings(pixel_values)).to(dev).contiguous()
-        ids = input_ids.to(dev, torch.int64).contiguous()
-        am = (attention_mask if attention_mask is not None else torch.ones_like(input_ids)).to(dev, torch.int64).contiguous()
-        if eos_token_id is not None and pad_token_id is None:
-            pad_token_id = eos_token_id
-        eos = -1 if eos_token_id is None else int(eos_token_id)
-        pad = 0 if pad_token_id is None else int(pad_token_id)
-        early = {False: 0, True: 1, "never": 2}[early_stopping]
-        B, T = ids.shape
-        BK, cap = B * k, max_new
-        i32, i64, f32 = torch.int32, torch.int64, torch.float32
-        cand = (torch.empty((B, 2 * k), dtype=f32, device=dev), torch.empty((B, 2 * k), dtype=i64, device=dev),
-                torch.empty((B, 2 * k), dtype=i32, device=dev))
-        run_score = torch.zeros(BK, dtype=f32, device=dev)
-        anc = [torch.zeros((BK, cap), dtype=i32, device=dev) for _ in range(2)]
-        hist = [torch.zeros((BK, cap), dtype=i64, device=dev) for _ in range(2)]
-        fin_tok = [torch.full((B, k, cap), pad, dtype=i64, device=dev) for _ in range(2)]
-        fin_score = [torch.full((B, k), -1e9, dtype=f32, device=dev) for _ in range(2)]
-        fin_len = [torch.zeros((B, k), dtype=i32, device=dev) for _ in range(2)]
-        done = torch.zeros(B, dtype=i32, device=dev)
-        next_tok = torch.zeros(BK, dtype=i64, device=dev)
-        cur = 0
-
-        def beam_step(logits, score, n):
-            nonlocal cur
-            ops.beam_candidates(logits, score, B, k, out=cand)
-            if self.beam_trace is not None:   # tests / tools: every step's candidate lists (score, token, parent), copied
-                self.beam_trace.append(tuple(c.clone() for c in cand))
-            o = 1 - cur
-            ops.beam_update(cand, B, k, n, cap, eos, pad, early, length_penalty, run_score, (anc[cur], anc[o]), (hist[cur], hist[o]),
-                            (fin_tok[cur], fin_tok[o]), (fin_score[cur], fin_score[o]), (fin_len[cur], fin_len[o]), done, next_tok)
-            cur = o
-
-        if not use_cache:
-            # the reference's literal recompute: the B * k beams' full sequences through the stack every step (HF expands every
-            # sample k times; beams 1 .. k-1 start at -1e9, so the first step's candidates all come from beam 0)
-            feats_k, ids_k, am_k = feats.repeat_interleave(k, 0), ids.repeat_interleave(k, 0), am.repeat_interleave(k, 0)
-            score0 = torch.full((B, k), -1e9, dtype=f32, device=dev)
-            score0[:, 0] = 0.0
-            score0 = score0.view(BK)
-            for n in range(max_new):
-                cur_ids = torch.cat([ids_k, hist[cur][:, :n]], dim=1)
-                cur_am = torch.cat([am_k, torch.ones((BK, n), dtype=i64, device=dev)], dim=1)
-                st = self._engine_forward(feats_k, cur_ids, cur_am, None, False, train=False)
-                beam_step(st["logits"][:, -1, :], score0 if n == 0 else run_score, n)
-        else:
-            # one prefill per sample: its last-position logits are the first step's (only beam 0 is live there), its K/V the prefix
-            # that the sample's k beams share
-            S_ = cfg.num_vision_tokens + T
-            store = torch.empty((cfg.num_hidden_layers, B * S_, 3 * cfg.num_attention_heads * cfg.head_dim), dtype=self.compute_dtype, device=dev)
-            st = self._engine_forward(feats, ids, am, None, False, train=False, qkv_out=list(store.unbind(0)), last_only=True)
-            cache = _DecodeCache(self, list(store.unbind(0)), B, st["S"], max_new, am, fused=getattr(self, "fused_decode", True),
-                                 prefix_storage=store, beams=k)
-            if not cache.prerot:
-                raise NotImplementedError("the cached beam search needs the pre-rotated cache (rotary dims % 16 == 0, head size 64 / 128 / 256)")
-            beam_step(st["logits"][:, -1, :], torch.zeros(B, dtype=f32, device=dev), 0)
-            for t in range(max_new - 1):
-                cache.anc = anc[cur]
-                beam_step(self._engine_decode_step(next_tok, t, cache), run_score, t + 1)
-        lens = fin_len[cur][:, :nrs]
-        n_keep = int(lens.max())   # the one host synchronisation
-        seqs = torch.cat([ids.repeat_interleave(nrs, 0), fin_tok[cur][:, :nrs, :n_keep].reshape(B * nrs, n_keep)], dim=1)
-        if return_dict:
-            return BeamSearchOutput(sequences=seqs, sequences_scores=fin_score[cur][:, :nrs].reshape(B * nrs).clone())
-        return seqs
-
-    def _engine_decode_step(self, tokens: torch.Tensor, t: int, cache: "_DecodeCache") -> torch.Tensor:
-        """One token per sample through the stack: ``tokens`` [B] sit at position S0 + t; returns the logits [B, V]."""
-        cfg, cd = self.config, self.compute_dtype
-        h, H, D, L = cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim, cfg.num_hidden_layers
-        B, S0, rot = cache.B, cache.S0, cfg.rotary_ndims
-        cos, sin = self.rotary_tables(S0 + cache.cap)
-        w = self._w
-        x = self._p("gpt_neox.embed_in.weight").index_select(0, tokens)  # fp32 residual stream row
-        if cache.fused:
-            # three launches per layer (csrc/decode.hip): [LN1 | LN2] + QKV + fc1/GELU, attention over the pre-rotated cache, and
-            # dense + fc2 + both residuals as one product over the concatenated K
-            for i in range(L):
-                pre = f"gpt_neox.layers.{i}."
-                a = ops.decode_ln_qkv_fc1(x, self._p(pre + "input_layernorm.weight"), self._p(pre + "input_layernorm.bias"),
-                                          self._p(pre + "post_attention_layernorm.weight"), self._p(pre + "post_attention_layernorm.bias"),
-                                          cfg.layer_norm_eps, w(pre + "attention.query_key_value.weight"),
-                                          self._p(pre + "attention.query_key_value.bias"), cache.new[i][:, t, :],
-                                          w(pre + "mlp.dense_h_to_4h.weight"), self._p(pre + "mlp.dense_h_to_4h.bias"))
-                ao = (ops.attn_decode(cache.prefix[i], S0, cache.new[i], t, B, H, D, rot, cos, sin, cache.attention_mask, prerot=True)
-                      if cache.anc is None else
-                      ops.attn_decode_beam(cache.prefix[i], S0, cache.new[i], t, B, cache.beams, cache.anc, H, D, rot, cos, sin, cache.attention_mask))
-                x = ops.decode_out(x, ao, a, w(pre + "attention.dense.weight"), self._p(pre + "attention.dense.bias"),
-                                   w(pre + "mlp.dense_4h_to_h.weight"), self._p(pre + "mlp.dense_4h_to_h.bias"), cache.workspace, out=x)
-            if B * cache.beams <= 32 and h == 1024 and cfg.vocab_size % 32 == 0 and cfg.vocab_size >= 16384:
-                # final LayerNorm + LM head as one persistent launch (decode_head_kernel: rows normalised once per CU, the vocabulary's
-                # weight strips streamed through LDS): 24 us against 48 for LayerNorm + the skinny product at V = 50k
-                return ops.decode_ln_linear(x, self._p("gpt_neox.final_layer_norm.weight"), self._p("gpt_neox.final_layer_norm.bias"),
-                                            cfg.layer_norm_eps, w("embed_out.weight"))
-            # (other shapes: the one-slab-per-block forms of ops.decode_ln_linear are no faster than the two launches below)
-            lnf, _, _, _ = ops.layernorm_fwd(x, self._p("gpt_neox.final_layer_norm.weight"), self._p("gpt_neox.final_layer_norm.bias"),
-                                             None, None, cfg.layer_norm_eps, cd, save_stats=False)
-            return ops.gemm(lnf, w("embed_out.weight"), False, True)
-        for i in range(L):
-            pre = f"gpt_neox.layers.{i}."
-            ln1, ln2, _, _ = ops.layernorm_fwd(x, self._p(pre + "input_layernorm.weight"), self._p(pre + "input_layernorm.bias"),
-                                               self._p(pre + "post_attention_layernorm.weight"), self._p(pre + "post_attention_layernorm.bias"),
-                                               cfg.layer_norm_eps, cd, save_stats=False)
-            # the new token's q | k | v row goes straight into the cache (row t of the per-layer [B, cap, 3*H*D] tensor)
-            ops.gemm(ln1, w(pre + "attention.query_key_value.weight"), False, True, bias=self._p(pre + "attention.query_key_value.bias"),
-                     out=cache.new[i][:, t, :])
-            ao = (ops.attn_decode(cache.prefix[i], S0, cache.new[i], t, B, H, D, rot, cos, sin, cache.attention_mask, prerot=cache.prerot)
-                  if cache.anc is None else
-                  ops.attn_decode_beam(cache.prefix[i], S0, cache.new[i], t, B, cache.beams, cache.anc, H, D, rot, cos, sin, cache.attention_mask))
-            attn = ops.gemm(ao, w(pre + "attention.dense.weight"), False, True, bias=self._p(pre + "attention.dense.bias"), out_dtype=cd)
-            a = ops.gemm(ln2, w(pre + "mlp.dense_h_to_4h.weight"), False, True, bias=self._p(pre + "mlp.dense_h_to_4h.bias"), epilogue=EPI_GELU)
-            x = ops.gemm(a, w(pre + "mlp.dense_4h_to_h.weight"), False, True, bias=self._p(pre + "mlp.dense_4h_to_h.bias"),
-                         out_dtype=torch.float32, res1=attn, res2=x)
-        lnf, _, _, _ = ops.layernorm_fwd(x, self._p("gpt_neox.final_layer_norm.weight"), self._p("gpt_neox.final_layer_norm.bias"),
-                                         None, None, cfg.layer_norm_eps, cd, save_stats=False)
-        return ops.gemm(lnf, w("embed_out.weight"), False, True)
-
     # ---- engine ------------------------------------------------------------------------------------------------------
     def _engine_forward(self, feats, input_ids, attention_mask, labels, want_hidden, train, n_hidden: Optional[int] = None,
                         keep_qkv: bool = False, qkv_out: Optional[Sequence[torch.Tensor]] = None, label_rows_hint: Optional[int] = None,
@@ -740,7 +559,8 @@ class VLPythiaForCausalLM(nn.Module):
         rows = B * S
         rot = cfg.rotary_ndims
         cos, sin = self.rotary_tables(S)
-        w = self._w
+        wts, pars = self._tensors(0), self._tensors(1)   # compute-dtype weights; fp32 LayerNorm parameters, biases and embedding
+        Wo, Po = wts.outer, pars.outer
         sv: Dict[str, Any] = {"B": B, "T": T, "P": P, "S": S, "input_ids": input_ids, "attention_mask": attention_mask, "labels": labels,
                               "layers": []}
         # projector: Linear -> GELU(erf) -> Linear (vl_pythia.py:226-234,270)
@@ -749,9 +569,9 @@ class VLPythiaForCausalLM(nn.Module):
             f2 = f2.float()
         fc = f2.contiguous() if f2.dtype == cd else ops.cast(f2.contiguous(), cd)
         u0 = torch.empty((B * P, h), dtype=cd, device=fc.device) if train else None
-        a0 = ops.gemm(fc, w("vision_embed_tokens.0.weight"), False, True, bias=self._p("vision_embed_tokens.0.bias"), epilogue=EPI_GELU, aux=u0)
-        img = ops.gemm(a0, w("vision_embed_tokens.2.weight"), False, True, bias=self._p("vision_embed_tokens.2.bias"))
-        x = ops.embed_concat_fwd(img, self._p("gpt_neox.embed_in.weight"), input_ids, B, P, T)  # fp32 residual stream
+        a0 = ops.gemm(fc, Wo.proj0_w, False, True, bias=Po.proj0_b, epilogue=EPI_GELU, aux=u0)
+        img = ops.gemm(a0, Wo.proj2_w, False, True, bias=Po.proj2_b)
+        x = ops.embed_concat_fwd(img, Po.embed_in, input_ids, B, P, T)  # fp32 residual stream
         if train:
             sv["proj"] = (fc, u0, a0)
         hidden = [x.view(B, S, h)]
@@ -760,22 +580,19 @@ class VLPythiaForCausalLM(nn.Module):
             hook(0, x)
         n_layers = L if n_hidden is None else max(0, min(L, n_hidden - 1))
         for i in range(n_layers):
-            pre = f"gpt_neox.layers.{i}."
+            w, p = wts.layers[i], pars.layers[i]
             if pe is not None:
                 main_st.wait_event(pe[("layer", i)])
-            ln1, ln2, mean, rstd = ops.layernorm_fwd(x, self._p(pre + "input_layernorm.weight"), self._p(pre + "input_layernorm.bias"),
-                                                     self._p(pre + "post_attention_layernorm.weight"), self._p(pre + "post_attention_layernorm.bias"),
-                                                     cfg.layer_norm_eps, cd, save_stats=train)
-            qkv = ops.gemm(ln1, w(pre + "attention.query_key_value.weight"), False, True, bias=self._p(pre + "attention.query_key_value.bias"),
+            ln1, ln2, mean, rstd = ops.layernorm_fwd(x, p.ln1_w, p.ln1_b, p.ln2_w, p.ln2_b, cfg.layer_norm_eps, cd, save_stats=train)
+            qkv = ops.gemm(ln1, w.qkv_w, False, True, bias=p.qkv_b,
                            out=qkv_out[i] if qkv_out is not None else None)  # (a captured decode graph reads its K/V cache at fixed addresses)
             ao, lse = ops.attn_fwd(qkv, B, S, H, D, rot, cos, sin, attention_mask)
             # the attention branch output is a bf16 tensor under the reference's autocast too (it meets the fp32 residual in the add)
-            attn = ops.gemm(ao, w(pre + "attention.dense.weight"), False, True, bias=self._p(pre + "attention.dense.bias"), out_dtype=cd)
+            attn = ops.gemm(ao, w.dense_w, False, True, bias=p.dense_b, out_dtype=cd)
             u = torch.empty((rows, cfg.intermediate_size), dtype=cd, device=x.device) if train else None
-            a = ops.gemm(ln2, w(pre + "mlp.dense_h_to_4h.weight"), False, True, bias=self._p(pre + "mlp.dense_h_to_4h.bias"), epilogue=EPI_GELU, aux=u)
+            a = ops.gemm(ln2, w.fc1_w, False, True, bias=p.fc1_b, epilogue=EPI_GELU, aux=u)
             # h + attn(LN1(h)) + mlp(LN2(h)) in the last GEMM's epilogue (tf:271-274)
-            xn = ops.gemm(a, w(pre + "mlp.dense_4h_to_h.weight"), False, True, bias=self._p(pre + "mlp.dense_4h_to_h.bias"),
-                          out_dtype=torch.float32, res1=attn, res2=x)
+            xn = ops.gemm(a, w.fc2_w, False, True, bias=p.fc2_b, out_dtype=torch.float32, res1=attn, res2=x)
             if train:
                 sv["layers"].append({"x": x, "mean": mean, "rstd": rstd, "ln1": ln1, "ln2": ln2, "qkv": qkv, "ao": ao, "lse": lse, "u": u, "a": a})
             elif keep_qkv:
@@ -798,22 +615,22 @@ class VLPythiaForCausalLM(nn.Module):
         if last_only:
             # a decode prefill only needs the last position's logits: final LN + head on B rows instead of B * T (-> logits [B, 1, V])
             xl = x.view(B, S, h)[:, -1, :].contiguous()
-            lnl, _, _, _ = ops.layernorm_fwd(xl, self._p("gpt_neox.final_layer_norm.weight"), self._p("gpt_neox.final_layer_norm.bias"),
+            lnl, _, _, _ = ops.layernorm_fwd(xl, Po.final_ln_w, Po.final_ln_b,
                                              None, None, cfg.layer_norm_eps, cd, save_stats=False)
-            sv["logits"] = ops.gemm(lnl, w("embed_out.weight"), False, True).view(B, 1, cfg.vocab_size)
+            sv["logits"] = ops.gemm(lnl, Wo.embed_out, False, True).view(B, 1, cfg.vocab_size)
             return sv
         if skip_head:
             # representation analysis: hidden_states[L] (the fp32 final-LN state) is the last thing anyone reads; no LM head, no loss
-            full, _, _, _ = ops.layernorm_fwd(x, self._p("gpt_neox.final_layer_norm.weight"), self._p("gpt_neox.final_layer_norm.bias"),
+            full, _, _, _ = ops.layernorm_fwd(x, Po.final_ln_w, Po.final_ln_b,
                                               None, None, cfg.layer_norm_eps, torch.float32, save_stats=False)
             hidden.append(full.view(B, S, h))
             return sv
         # final LN (fp32 hidden state L only when asked for) + LM head on the T text positions (vl_pythia.py:89,310)
         xt = x.view(B, S, h)[:, P:, :].reshape(B * T, h)
-        lnf, _, fmean, frstd = ops.layernorm_fwd(xt, self._p("gpt_neox.final_layer_norm.weight"), self._p("gpt_neox.final_layer_norm.bias"),
+        lnf, _, fmean, frstd = ops.layernorm_fwd(xt, Po.final_ln_w, Po.final_ln_b,
                                                  None, None, cfg.layer_norm_eps, cd, save_stats=train)
         if want_hidden:
-            full, _, _, _ = ops.layernorm_fwd(x, self._p("gpt_neox.final_layer_norm.weight"), self._p("gpt_neox.final_layer_norm.bias"),
+            full, _, _, _ = ops.layernorm_fwd(x, Po.final_ln_w, Po.final_ln_b,
                                               None, None, cfg.layer_norm_eps, torch.float32, save_stats=False)
             hidden.append(full.view(B, S, h))
         # Row-sparse head (training, with the caller's bound on labelled positions per sample): only rows whose shifted label is a token
@@ -831,7 +648,7 @@ class VLPythiaForCausalLM(nn.Module):
             # returns NaN (no host synchronisation: the step fails loudly instead of training on a wrong loss)
             self.last_label_overflow = ov
             lnf_c = ops.gather_rows(lnf, ros)
-            logits = ops.gemm(lnf_c, w("embed_out.weight"), False, True).view(B, Rc, cfg.vocab_size)
+            logits = ops.gemm(lnf_c, Wo.embed_out, False, True).view(B, Rc, cfg.vocab_size)
             sv["logits"] = logits
             loss, lse_ce = ops.ce_fwd(logits, labels_c, poison=ov)
             sv["loss"], sv["ce_lse"] = loss, lse_ce
@@ -839,7 +656,7 @@ class VLPythiaForCausalLM(nn.Module):
             sv["final"] = (xt, lnf_c, fmean, frstd)
             sv["x_last"] = x
             return sv
-        logits = ops.gemm(lnf, w("embed_out.weight"), False, True).view(B, T, cfg.vocab_size)
+        logits = ops.gemm(lnf, Wo.embed_out, False, True).view(B, T, cfg.vocab_size)
         sv["logits"] = logits
         if labels is not None:
             loss, lse_ce = ops.ce_fwd(logits, labels)
@@ -867,8 +684,8 @@ class VLPythiaForCausalLM(nn.Module):
     def _dw_group_fuses_squares(self, rows: int) -> bool:
         """Will a grouped weight-gradient launch of this model (``dw_group_layers`` layers x four matrices, K = rows) emit the squares of
         its outputs from the epilogue?  Asked of the library once per (rows, group size)."""
-        cache = self.__dict__.setdefault("_dw_fuse_cache", {})
-        key = (int(rows), int(getattr(self, "dw_group_layers", 2) or 0))
+        cache = self._dw_fuse_cache
+        key = (int(rows), int(self.dw_group_layers or 0))
         if key not in cache:
             cfg = self.config
             h, f = cfg.hidden_size, cfg.intermediate_size
@@ -884,7 +701,7 @@ class VLPythiaForCausalLM(nn.Module):
         # 128 x 128 kernels' many small blocks lose 1.1 - 1.45x.  So this backward runs on those (Trainer sets the flag).
         # (per call: every GEMM this thread issues inside the block carries MAFED_EPI_NO_PERSISTENT; no process-wide switch is touched, a
         #  forced tuning variant or another thread's / model's launches are unaffected)
-        cb = getattr(self, "contended_backward", False)
+        cb = self.contended_backward
         if cb and self.flat_params.is_cuda:
             # "ticketed": the persistent kernels stay, their blocks draw tiles from per-XCD queues (MAFED_EPI_TICKETED) -- a launch then
             # tolerates the CUs the collective holds (1.2 - 1.3x instead of 1.7 - 1.9x with 8 - 32 CUs taken, tools/contention_bench.py);
@@ -895,14 +712,15 @@ class VLPythiaForCausalLM(nn.Module):
         return self._engine_backward_impl(sv, dloss, dhidden, taps)
 
     def _engine_backward_impl(self, sv, dloss: Optional[torch.Tensor], dhidden: Sequence[Optional[torch.Tensor]], taps=None):
-        self._bw_serial = getattr(self, "_bw_serial", 0) + 1   # lets a gradient hook tell which backward sweep reported a range
+        self._bw_serial += 1   # lets a gradient hook tell which backward sweep reported a range
         cfg, cd = self.config, self.compute_dtype
         B, T, P, S = sv["B"], sv["T"], sv["P"], sv["S"]
         h, H, D, L = cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim, cfg.num_hidden_layers
         rows = B * S
         rot = cfg.rotary_ndims
         cos, sin = self.rotary_tables(S)
-        w, g = self._w, self._g
+        wts, pars, grads = self._tensors(0), self._tensors(1), self._tensors(2)   # compute-dtype weights, fp32 parameters, gradients
+        Wo, Po, Go = wts.outer, pars.outer, grads.outer
         am = sv["attention_mask"]
         dev = self.flat_params.device
         if len(dhidden) > L and dhidden[L] is not None:
@@ -937,48 +755,50 @@ class VLPythiaForCausalLM(nn.Module):
                 fn()
             keep.extend(tensors)
 
-        def wgrad(dY, X, wname, bname=None):
+        def wgrad(dY, X, gw, gb=None):
+            """gw += dY^T . X (and gb += column sums of dY) on a side stream."""
             def run():
-                ops.gemm(dY, X, True, False, out=g(wname), beta=1.0)
-                if bname is not None:
-                    ops.colsum_(dY, g(bname))
+                ops.gemm(dY, X, True, False, out=gw, beta=1.0)
+                if gb is not None:
+                    ops.colsum_(dY, gb)
             on_side(run, dY, X)
 
         # layer weight gradients, grouped: (dY, X, gradient) records wait here (the list keeps dY / X alive) until `flush_dw`
         # (beside collectives the weight gradients go back to one 128 x 128-kernel launch per product on the side streams, as in round 2:
         #  a grouped call would fall back to eight serial launches on the dX chain's stream)
-        group_dw = (cd == torch.bfloat16 and int(getattr(self, "dw_group_layers", 0)) > 0
-                    and getattr(self, "contended_backward", False) in (False, None, "ticketed"))
+        group_dw = (cd == torch.bfloat16 and int(self.dw_group_layers) > 0
+                    and self.contended_backward in (False, None, "ticketed"))
         # First micro-batch of an accumulation window (Trainer sets ``grad_overwrite``): the grouped weight-gradient GEMMs WRITE the layers'
         # matrix gradients (beta = 0) instead of adding to a zeroed buffer -- the optimiser pass then does not zero-write those 1.2 GB
         # (FlatAdamW: ``skip_matrix_zero``) and the GEMM epilogues do not read them back.  ``_dw_stale`` = the last optimiser pass left the
         # matrices un-zeroed: a sweep that accumulates anyway (another caller, another kernel path) zeroes them first.
-        overwrite = group_dw and bool(getattr(self, "grad_overwrite", False)) and taps is None
-        if getattr(self, "_dw_stale", False) and not overwrite:
+        overwrite = group_dw and bool(self.grad_overwrite) and taps is None
+        if self._dw_stale and not overwrite:
             self._zero_layer_matrices(range(L))
         self._dw_stale = False
         dw_beta = 0.0 if overwrite else 1.0
         # squares of the final matrix gradients from the weight-gradient epilogues (FlatAdamW.begin_incremental_norm): only a sweep whose
         # products all go through the grouped call can promise them -- it records its serial, the norm hook checks it
-        dw_sq = getattr(self, "dw_sumsq", None) if (group_dw and taps is None) else None
+        dw_sq = self.dw_sumsq if (group_dw and taps is None) else None
         if dw_sq is not None and not self._dw_group_fuses_squares(sv["B"] * sv["S"]):
             dw_sq = None   # (h = 768 / 2048: the 256 x 256-tile kernel has no fused squares -- the norm hook's range pass is cheaper than a pass per matrix)
         self._dw_sumsq_used = self._bw_serial if dw_sq is not None else None
-        DW_SLOT = {"attention.query_key_value.weight": 0, "attention.dense.weight": 1, "mlp.dense_h_to_4h.weight": 2, "mlp.dense_4h_to_h.weight": 3}
         pending_dw: List[dict] = []
         pending_layers: List[int] = []
 
-        def wgrad_layer(dY, X, wname, bname=None):
+        def wgrad_layer(dY, X, i, slot, with_bias=False):
+            """Weight gradient of layer i's matrix `slot` (0 .. 3 = query_key_value, dense, dense_h_to_4h, dense_4h_to_h: LayerTensors.matrix,
+            the order of ``dw_sumsq``), with its bias gradient if asked for."""
+            gw, gb = grads.layers[i].matrix(slot), grads.layers[i].bias(slot) if with_bias else None
             if not group_dw:
-                wgrad(dY, X, wname, bname)
+                wgrad(dY, X, gw, gb)
                 return
-            q = dict(A=dY, B=X, out=g(wname), beta=dw_beta)
+            q = dict(A=dY, B=X, out=gw, beta=dw_beta)
             if dw_sq is not None:
-                li_, kind = wname[len("gpt_neox.layers."):].split(".", 1)
-                q["sumsq"] = dw_sq[int(li_), DW_SLOT[kind]]
+                q["sumsq"] = dw_sq[i, slot]
             pending_dw.append(q)
-            if bname is not None:
-                on_side(lambda: ops.colsum_(dY, g(bname)), dY)
+            if gb is not None:
+                on_side(lambda: ops.colsum_(dY, gb), dY)
 
         def flush_dw():
             # at most PP_MAXP = 16 products per grouped launch (mafed_gemm_grouped launches larger lists one product at a time, serially on
@@ -1018,23 +838,22 @@ class VLPythiaForCausalLM(nn.Module):
             sp = sv.get("sparse_head")   # (slot of every text row, compact labels): the head ran on the labelled rows only
             n_head = logits.shape[0] * logits.shape[1]
             dlog = ops.ce_bwd(logits, sp[1] if sp is not None else sv["labels"], sv["ce_lse"], gl).view(n_head, cfg.vocab_size)
-            wgrad(dlog, lnf, "embed_out.weight")
+            wgrad(dlog, lnf, Go.embed_out)
             if cd == torch.bfloat16:
                 # [rows, V] . [V, h]: few output tiles with K = 50304 -- accumulate-only fp32 output so that the GEMM splits K
                 dlnf = torch.zeros((n_head, h), dtype=torch.float32, device=dev)
-                ops.gemm(dlog, w("embed_out.weight"), False, False, out=dlnf, beta=1.0)
+                ops.gemm(dlog, Wo.embed_out, False, False, out=dlnf, beta=1.0)
             else:
-                dlnf = ops.gemm(dlog, w("embed_out.weight"), False, False)
+                dlnf = ops.gemm(dlog, Wo.embed_out, False, False)
             if sp is not None:
                 dlnf = ops.gather_rows(dlnf if dlnf.dtype == torch.float32 else dlnf.float(), sp[0])   # back to the [B*T, h] text rows (zeros elsewhere)
             if defer_ln:
-                dxt, _, fws = ops.layernorm_bwd_rows(dlnf, None, xt, fmean, frstd, self._p("gpt_neox.final_layer_norm.weight"), None, None)
+                dxt, _, fws = ops.layernorm_bwd_rows(dlnf, None, xt, fmean, frstd, Po.final_ln_w, None, None)
                 main_moved()
-                on_side(lambda ws=fws: ops.layernorm_bwd_params(ws, B * T, h, g("gpt_neox.final_layer_norm.weight"),
-                                                                g("gpt_neox.final_layer_norm.bias")), fws)
+                on_side(lambda ws=fws: ops.layernorm_bwd_params(ws, B * T, h, Go.final_ln_w, Go.final_ln_b), fws)
             else:
-                dxt, _ = ops.layernorm_bwd(dlnf, None, xt, fmean, frstd, self._p("gpt_neox.final_layer_norm.weight"), None, None,
-                                           g("gpt_neox.final_layer_norm.weight"), g("gpt_neox.final_layer_norm.bias"))
+                dxt, _ = ops.layernorm_bwd(dlnf, None, xt, fmean, frstd, Po.final_ln_w, None, None,
+                                           Go.final_ln_w, Go.final_ln_b)
             dx, dy0 = ops.pad_text_rows(dxt, B, S, P, cd if cd != torch.float32 else None)
             main_moved()
             ready(L)
@@ -1048,8 +867,8 @@ class VLPythiaForCausalLM(nn.Module):
                 ext = ext.reshape(rows, h)
                 if dx is not None and dy_bias_done:
                     # the LayerNorm backward above already added colsum(dx) to this layer's bias gradients: add the rest
-                    ops.colsum_(ext.to(torch.float32).contiguous(), g(f"gpt_neox.layers.{i}.mlp.dense_4h_to_h.bias"))
-                    ops.colsum_(ext.to(torch.float32).contiguous(), g(f"gpt_neox.layers.{i}.attention.dense.bias"))
+                    ops.colsum_(ext.to(torch.float32).contiguous(), grads.layers[i].fc2_b)
+                    ops.colsum_(ext.to(torch.float32).contiguous(), grads.layers[i].dense_b)
                 dx = ext.to(torch.float32) if dx is None else dx.add_(ext)
                 dy = None
                 main_moved()
@@ -1067,45 +886,38 @@ class VLPythiaForCausalLM(nn.Module):
             if dy is None:
                 dy = dx if cd == torch.float32 else ops.cast(dx, cd)
                 main_moved()
-            pre = f"gpt_neox.layers.{i}."
+            w, p, g = wts.layers[i], pars.layers[i], grads.layers[i]
             s = sv["layers"][i]
             # parameter gradients that only need dy: MLP down-projection and attention output projection
-            wgrad_layer(dy, s["a"], pre + "mlp.dense_4h_to_h.weight", None if dy_bias_done else pre + "mlp.dense_4h_to_h.bias")
-            wgrad_layer(dy, s["ao"], pre + "attention.dense.weight", None if dy_bias_done else pre + "attention.dense.bias")
+            wgrad_layer(dy, s["a"], i, 3, with_bias=not dy_bias_done)
+            wgrad_layer(dy, s["ao"], i, 1, with_bias=not dy_bias_done)
             # MLP branch
             # (the bias gradients of the two up-projections are column sums of du / dqkv: folded into the producing kernels)
-            du = ops.gemm(dy, w(pre + "mlp.dense_4h_to_h.weight"), False, False, epilogue=EPI_GELU_BWD, aux=s["u"],
-                          colsum=g(pre + "mlp.dense_h_to_4h.bias"))
+            du = ops.gemm(dy, w.fc2_w, False, False, epilogue=EPI_GELU_BWD, aux=s["u"], colsum=g.fc1_b)
             main_moved()
-            wgrad_layer(du, s["ln2"], pre + "mlp.dense_h_to_4h.weight")
-            dln2 = ops.gemm(du, w(pre + "mlp.dense_h_to_4h.weight"), False, False)
+            wgrad_layer(du, s["ln2"], i, 2)
+            dln2 = ops.gemm(du, w.fc1_w, False, False)
             # attention branch
-            dao = ops.gemm(dy, w(pre + "attention.dense.weight"), False, False)
-            dqkv = ops.attn_bwd(s["qkv"], s["ao"], dao, s["lse"], B, S, H, D, rot, cos, sin, am,
-                                colsum=g(pre + "attention.query_key_value.bias"))
+            dao = ops.gemm(dy, w.dense_w, False, False)
+            dqkv = ops.attn_bwd(s["qkv"], s["ao"], dao, s["lse"], B, S, H, D, rot, cos, sin, am, colsum=g.qkv_b)
             main_moved()
-            wgrad_layer(dqkv, s["ln1"], pre + "attention.query_key_value.weight")
-            dln1 = ops.gemm(dqkv, w(pre + "attention.query_key_value.weight"), False, False)
+            wgrad_layer(dqkv, s["ln1"], i, 0)
+            dln1 = ops.gemm(dqkv, w.qkv_w, False, False)
             # both LayerNorms + the residual path, one pass; also emits the compute-dtype copy the next layer's GEMMs read
             ln_kw = dict(want_lp=(cd != torch.float32), teacher=inj[0].view(rows, h) if inj is not None else None,
                          attention_mask=am if inj is not None else None, S=S, P=P, inj_scale=inj[1] if inj is not None else None,
                          inj_mul=-1.0 if inj_cos else 2.0 / h)   # (a negative factor selects the cosine-distance gradient, mafed_hip.h)
-            dxa = g(f"gpt_neox.layers.{i - 1}.mlp.dense_4h_to_h.bias") if i > 0 else None
-            dxb = g(f"gpt_neox.layers.{i - 1}.attention.dense.bias") if i > 0 else None
+            dxa = grads.layers[i - 1].fc2_b if i > 0 else None   # colsum(dx) is the layer below's two residual-branch bias gradients
+            dxb = grads.layers[i - 1].dense_b if i > 0 else None
             if defer_ln:
                 # row kernel on the dX chain; the slab reduction into the LayerNorm / bias gradients goes to a side stream (it feeds
                 # parameter gradients only, and on the main stream the whole chip waited for it once per layer)
-                dx, dy, ln_ws = ops.layernorm_bwd_rows(dln1, dln2, s["x"], s["mean"], s["rstd"], self._p(pre + "input_layernorm.weight"),
-                                                       self._p(pre + "post_attention_layernorm.weight"), dx, want_dxsum=i > 0, **ln_kw)
+                dx, dy, ln_ws = ops.layernorm_bwd_rows(dln1, dln2, s["x"], s["mean"], s["rstd"], p.ln1_w, p.ln2_w, dx, want_dxsum=i > 0, **ln_kw)
                 main_moved()
-                on_side(lambda ws=ln_ws, pre=pre, dxa=dxa, dxb=dxb: ops.layernorm_bwd_params(
-                    ws, rows, h, g(pre + "input_layernorm.weight"), g(pre + "input_layernorm.bias"),
-                    g(pre + "post_attention_layernorm.weight"), g(pre + "post_attention_layernorm.bias"), dxa, dxb), ln_ws)
+                on_side(lambda ws=ln_ws, g=g, dxa=dxa, dxb=dxb: ops.layernorm_bwd_params(
+                    ws, rows, h, g.ln1_w, g.ln1_b, g.ln2_w, g.ln2_b, dxa, dxb), ln_ws)
             else:
-                dx, dy = ops.layernorm_bwd(dln1, dln2, s["x"], s["mean"], s["rstd"], self._p(pre + "input_layernorm.weight"),
-                                           self._p(pre + "post_attention_layernorm.weight"), dx,
-                                           g(pre + "input_layernorm.weight"), g(pre + "input_layernorm.bias"),
-                                           g(pre + "post_attention_layernorm.weight"), g(pre + "post_attention_layernorm.bias"),
+                dx, dy = ops.layernorm_bwd(dln1, dln2, s["x"], s["mean"], s["rstd"], p.ln1_w, p.ln2_w, dx, g.ln1_w, g.ln1_b, g.ln2_w, g.ln2_b,
                                            dxsum_a=dxa, dxsum_b=dxb, **ln_kw)
                 main_moved()
             dy_bias_done = i > 0
@@ -1131,111 +943,17 @@ class VLPythiaForCausalLM(nn.Module):
             main_moved()
         if dx is not None:
             fc, u0, a0 = sv["proj"]
-            dimg = ops.embed_concat_bwd(dx, sv["input_ids"], B, P, T, h, cfg.vocab_size, g("gpt_neox.embed_in.weight"), cd)
+            dimg = ops.embed_concat_bwd(dx, sv["input_ids"], B, P, T, h, cfg.vocab_size, Go.embed_in, cd)
             main_moved()
-            wgrad(dimg, a0, "vision_embed_tokens.2.weight", "vision_embed_tokens.2.bias")
-            du0 = ops.gemm(dimg, w("vision_embed_tokens.2.weight"), False, False, epilogue=EPI_GELU_BWD, aux=u0,
-                           colsum=g("vision_embed_tokens.0.bias"))
+            wgrad(dimg, a0, Go.proj2_w, Go.proj2_b)
+            du0 = ops.gemm(dimg, Wo.proj2_w, False, False, epilogue=EPI_GELU_BWD, aux=u0, colsum=Go.proj0_b)
             main_moved()
-            wgrad(du0, fc, "vision_embed_tokens.0.weight")
+            wgrad(du0, fc, Go.proj0_w)
         ready(-1)
         if sides is not None:
             for st in sides:
                 main.wait_stream(st)  # gradients complete (and `keep` safe to release) from the main stream's point of view
         keep.clear()
-
-
-class _DecodeCache:
-    """K/V cache of a greedy decode: per layer the prefill's [B*S0, 3*H*D] fused-QKV output (kept as written -- no split, no
-    transpose, k un-rotated) and a [B, cap, 3*H*D] tensor that receives one row per generated token."""
-
-    def __init__(self, model, prefix, B: int, S0: int, cap: int, attention_mask: torch.Tensor, prerotate: bool = True, fused: bool = True,
-                 prefix_storage: Optional[torch.Tensor] = None, beams: int = 1):
-        self.prefix, self.B, self.S0, self.cap, self.attention_mask = prefix, B, S0, max(1, cap), attention_mask
-        self.prefix_storage = prefix_storage   # [L, B*S0, 3h] holding every entry of `prefix` (then one rotation launch serves all layers)
-        # beam search: the prefix stays one per sample, the generated rows are one per beam slot ([B*beams, cap, 3h]); `anc` (int32
-        # [B*beams, cap], set by the caller before each step) names the slot holding each row of a beam's history
-        self.beams, self.anc = beams, None
-        rows = B * beams
-        cfg = model.config
-        n = 3 * cfg.num_attention_heads * cfg.head_dim
-        self.new = [torch.zeros((rows, self.cap, n), dtype=prefix[0].dtype, device=prefix[0].device) for _ in prefix]
-        # Pre-rotated cache (round 4): once the prefill's attention has read the un-rotated keys, rotate them in place -- every decode step
-        # then loads k and v only (mafed_attn_decode_prerot).  Needs rot % 16 == 0 and an MFMA head size (every VLPythia preset).
-        self.prerot = bool(prerotate) and cfg.rotary_ndims % 16 == 0 and cfg.head_dim in (64, 128, 256)
-        self._model = model
-        # fused decode layer (csrc/decode.hip): bf16 mode over the pre-rotated cache, shapes per mafed_decode_supported
-        # (more than 64 rows -- 64-row blocks of the fused kernels -- only for beam search: a greedy batch of B > 64 keeps the six launches)
-        self.fused = (bool(fused) and self.prerot and prefix[0].dtype == torch.bfloat16 and (rows <= 64 or beams > 1)
-                      and ops.decode_supported(rows, cfg.hidden_size, cfg.intermediate_size))
-        self.workspace = ops.decode_out_workspace(rows, cfg.hidden_size, prefix[0].device) if self.fused else None
-        if self.prerot:
-            self.rotate_prefix()
-
-    def rotate_prefix(self) -> None:
-        """Rotate the prefix keys in place (call once per prefill: the prefix must hold what the QKV GEMMs wrote)."""
-        cfg = self._model.config
-        cos, sin = self._model.rotary_tables(self.S0 + self.cap)
-        whole = self.prefix_storage   # every layer's prefix in ONE tensor: one launch for all
-        if whole is not None:
-            ops.rotate_k_rows_(whole, whole.shape[0] * self.B, self.S0, cfg.num_attention_heads, cfg.head_dim, cfg.rotary_ndims, cos, sin)
-            return
-        for p in self.prefix:
-            ops.rotate_k_rows_(p, self.B, self.S0, cfg.num_attention_heads, cfg.head_dim, cfg.rotary_ndims, cos, sin)
-
-
-class _GraphedDecode:
-    """Greedy decode steps 1 .. max_new-1 for one (B, T, max_new) shape as a single hipGraph.  Static buffers: the per-layer
-    K/V cache (prefix written by the prefill's QKV GEMMs through ``qkv_out``, plus the per-token rows), the prompt mask, the
-    prefill's last-position logits, the ``unfinished`` flags and the generated tokens."""
-
-    def __init__(self, model, B: int, T: int, max_new: int, eos_token_id, pad_token_id):
-        cfg = model.config
-        dev, cd = model.flat_params.device, model.compute_dtype
-        S0 = cfg.num_vision_tokens + T
-        n = 3 * cfg.num_attention_heads * cfg.head_dim
-        self.model, self.B, self.T, self.S0, self.max_new = model, B, T, S0, max_new
-        self.prefix_storage = torch.empty((cfg.num_hidden_layers, B * S0, n), dtype=cd, device=dev)   # [L, B*S0, 3h]: rotated by one launch
-        self.prefix = list(self.prefix_storage.unbind(0))
-        self.am = torch.ones((B, T), dtype=torch.int64, device=dev)
-        self.first_logits = torch.zeros((B, cfg.vocab_size), dtype=cd if cd != torch.float32 else torch.float32, device=dev)
-        self.tokens = torch.zeros((B, max_new), dtype=torch.int64, device=dev)
-        model.rotary_tables(S0 + max(1, max_new))  # built (host -> device copy) before the capture, not inside it
-        self.cache = _DecodeCache(model, self.prefix, B, S0, max_new, self.am, fused=getattr(model, "fused_decode", True),
-                                  prefix_storage=self.prefix_storage)   # (rotates the still-empty prefix once: harmless)
-        eos, pad = eos_token_id, pad_token_id
-
-        def body():
-            unfinished = torch.ones(B, dtype=torch.int64, device=dev)
-            logits = self.first_logits
-            for t in range(max_new):
-                nxt = logits.float().argmax(dim=-1)
-                if eos is not None:
-                    nxt = nxt * unfinished + pad * (1 - unfinished)
-                    unfinished = unfinished * (nxt != eos).to(torch.int64)
-                self.tokens[:, t] = nxt
-                if t + 1 < max_new:
-                    logits = model._engine_decode_step(nxt, t, self.cache)
-
-        # one eager pass on a side stream (lazy initialisations must not happen inside the capture), then the capture
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            body()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            body()
-
-    def run(self, feats, ids, am) -> torch.Tensor:
-        m = self.model
-        st = m._engine_forward(feats, ids, am, None, False, train=False, qkv_out=self.prefix, last_only=True)
-        if self.cache.prerot:
-            self.cache.rotate_prefix()   # this prefill's keys, rotated in place for the captured steps
-        self.am.copy_(am)
-        self.first_logits.copy_(st["logits"][:, -1, :])
-        self.graph.replay()
-        return self.tokens.clone()
 
 
 class _ModelFn(torch.autograd.Function):

@@ -154,7 +154,7 @@ class FlatAdamW:
         model.dw_sumsq = part[self._norm_dw_lo:self._norm_dw_lo + n_dw].view(L, 4, 16) if (fused_matrix_squares and n_dw) else None
 
         def hook(i):
-            fused = model.dw_sumsq is not None and 0 <= i < L and getattr(model, "_dw_sumsq_used", None) == getattr(model, "_bw_serial", 0)
+            fused = model.dw_sumsq is not None and 0 <= i < L and model._dw_sumsq_used == model._bw_serial
             for lo, hi, slot in plan.get(i, ()):
                 if fused:
                     hi = model.layer_matrix_range(i)[0]   # the LayerNorm weights in front of the matrices; the matrices' squares are in dw_sumsq
@@ -162,7 +162,7 @@ class FlatAdamW:
                     ops.gradnorm_partial(g[lo:hi], part[slot:])
             if self._norm_seen is None:     # a backward outside Trainer.step() while the hook is still installed (clip_grad_norm_ consumed the
                 self._norm_seen = {}        # last window's record): its partials are simply never used
-            self._norm_seen[i] = getattr(model, "_bw_serial", 0)   # which backward sweep this range's partials belong to
+            self._norm_seen[i] = model._bw_serial   # which backward sweep this range's partials belong to
         hook.is_norm_hook = True   # Trainer replaces / removes hooks of this kind only
         return hook
 
@@ -176,7 +176,7 @@ class FlatAdamW:
         optimiser steps have run -- instead of ``clip_out[0]``, which the next step overwrites (callers clone that one)."""
         plan = getattr(self, "_norm_plan_cache", None)
         seen = getattr(self, "_norm_seen", None)
-        last = getattr(self.model, "_bw_serial", 0)
+        last = self.model._bw_serial
         # complete = every range reported during the LAST backward sweep (a sweep that skipped layers, or a plugin's extra sweep
         # before it, leaves older partials behind: then the buffer is read in one pass as before)
         if plan is not None and seen is not None and len(seen) == len(plan) and all(v == last for v in seen.values()):

@@ -112,8 +112,8 @@ class Trainer:
 
     def _overwrite_ok(self) -> bool:
         m = self.model
-        return (self.overwrite_weight_grads and self.reducer is None and getattr(m, "compute_dtype", None) == torch.bfloat16
-                and int(getattr(m, "dw_group_layers", 0)) > 0 and hasattr(m, "layer_matrix_range") and m.flat_grads.is_cuda)
+        return (self.overwrite_weight_grads and self.reducer is None and hasattr(m, "layer_matrix_range")
+                and m.compute_dtype == torch.bfloat16 and int(m.dw_group_layers) > 0 and m.flat_grads.is_cuda)
 
     def _device_step(self, batch, is_replay: bool, window_end: bool, window_start: bool = False) -> Dict[str, Any]:
         """Everything of a step that runs on the GPU, in Lightning's order (no host synchronisation).  Launches are eager: a
@@ -132,7 +132,7 @@ class Trainer:
             cur = self.model.grad_ready_hook
             if cur is None or getattr(cur, "is_norm_hook", False):   # (a hook installed by somebody else is left alone)
                 self.model.grad_ready_hook = self.optimizer.begin_incremental_norm(fused_matrix_squares=self.fused_norm_squares) if inc_norm else None
-                if not inc_norm and hasattr(self.model, "dw_sumsq"):
+                if not inc_norm:
                     self.model.dw_sumsq = None
             else:
                 self.optimizer._norm_seen = None
@@ -147,7 +147,7 @@ class Trainer:
         if torch.cuda.is_available() and hasattr(self.cl_method, "_prefetch_teacher"):
             # lets the next step's frozen-teacher forward start here, under this step's clip + AdamW
             # (the model's own event marks the end of the dX chain: the teacher forward then starts under the parameter-gradient tail)
-            ev = getattr(self.model, "dx_chain_event", None) if _EARLY_TEACHER else None
+            ev = self.model.dx_chain_event if _EARLY_TEACHER else None
             self.cl_method.backward_done_event = ev if ev is not None else torch.cuda.current_stream().record_event()
             if ev is not None:
                 self.model.dx_chain_event = None

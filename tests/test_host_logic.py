@@ -355,3 +355,59 @@ def test_fused_squares_query_is_host_logic():
     assert not fuses(layer(2048) * 2)
     assert not fuses(layer(768) * 2)
     assert not fuses(layer(1024)[1:2])
+
+
+def _records_model(device="cpu"):
+    from mafed_amd import VLPythiaConfig, VLPythiaForCausalLM
+    mc = VLPythiaConfig(vocab_size=512, hidden_size=128, num_hidden_layers=3, num_attention_heads=2, intermediate_size=512,
+                        vision_hidden_size=32, num_vision_tokens=8)
+    return mc, VLPythiaForCausalLM(mc, compute_dtype=torch.bfloat16, device=device)
+
+
+def _check_records(model):
+    from mafed_amd import model as M
+    L = model.config.num_hidden_layers
+    for which, src, by_name in ((0, model.flat_shadow, model._w), (1, model.flat_params, model._p), (2, model.flat_grads, model._g)):
+        views = model._tensors(which)
+        assert views.src is src and len(views.layers) == L
+        recs = [(M.layer_tensor_name(i, f), getattr(views.layers[i], f)) for i in range(L) for f in M.LayerTensors._fields]
+        recs += [(M.OUTER_FIELD_NAMES[f], getattr(views.outer, f)) for f in M.OuterTensors._fields]
+        assert sorted(n for n, _ in recs) == sorted(model._offsets)
+        for name, v in recs:
+            o, n, shape = model._offsets[name]
+            assert v._base is src and v.storage_offset() == o and v.numel() == n and tuple(v.shape) == tuple(shape), (which, name)
+            assert v.is_contiguous() and by_name(name) is v, (which, name)
+        for rec in views.layers:
+            pairs = ((rec.qkv_w, rec.qkv_b), (rec.dense_w, rec.dense_b), (rec.fc1_w, rec.fc1_b), (rec.fc2_w, rec.fc2_b))
+            assert all(rec.matrix(s) is m and rec.bias(s) is b for s, (m, b) in enumerate(pairs))
+
+
+def test_parameter_records_are_views_at_the_layout_offsets(monkeypatch):
+    """The per-layer / outer records the engine reads (model._tensors: weights in compute dtype, fp32 parameters, gradients): every field is
+    a view of its flat buffer at the offset ``_offsets`` gives for its state-dict name, the by-name lookups return the same objects, and
+    a lookup follows a flat buffer that a caller replaced.  A field that names no tensor fails when the model is constructed."""
+    from mafed_amd import VLPythiaForCausalLM
+    from mafed_amd import model as M
+    mc, model = _records_model()
+    _check_records(model)
+    assert model.layer_matrix_range(1)[0] == model._offsets[M.layer_tensor_name(1, "qkv_w")][0]
+    stale = model._tensors(2)
+    model.flat_grads = torch.zeros_like(model.flat_grads)
+    assert model._tensors(2) is not stale
+    _check_records(model)
+    monkeypatch.setitem(M.OUTER_FIELD_NAMES, "final_ln_b", "gpt_neox.final_layer_norm.bais")
+    with pytest.raises(KeyError):
+        VLPythiaForCausalLM(mc, compute_dtype=torch.float32, device="cpu")
+
+
+@pytest.mark.gpu
+def test_parameter_records_follow_apply():
+    """``.cuda()`` (``_apply``) replaces the three flat buffers -- a CPU-only machine has no second device to move to, hence the marker:
+    the records built before the move are dropped and the next lookup views the new buffers."""
+    _, model = _records_model("cpu")
+    _check_records(model)
+    old = (model.flat_shadow, model.flat_params, model.flat_grads)
+    model.cuda()
+    assert all(new is not o and new.is_cuda for new, o in zip((model.flat_shadow, model.flat_params, model.flat_grads), old))
+    assert model._views == [None, None, None]
+    _check_records(model)
