@@ -181,6 +181,14 @@ class BufferViews:
             raise KeyError("the parameter records do not cover every tensor of the flat layout")
 
 
+@dataclass
+class SweepRecord:
+    """What a backward sweep reports: left on the model as ``last_sweep`` when the sweep starts, completed as it goes."""
+    serial: int = 0                  # counts the model's sweeps: tells a gradient hook which sweep reported a range
+    filled_squares: bool = False     # its weight-gradient GEMMs leave the squares of the layers' matrix gradients in ``dw_sumsq``
+    dx_chain_event: Optional[torch.cuda.Event] = None   # end of its dX chain; Trainer takes it and resets it to None
+
+
 class VLPythiaForCausalLM(GenerationMixin, nn.Module):
     """MI355X-native counterpart of ``VLCLIPGPTNeoXForCausalLM`` for the training hot path."""
 
@@ -251,21 +259,14 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
         self.beam_trace: Optional[List[Any]] = None   # a list: generate(num_beams > 1) appends every step's candidate lists to it
         self.fused_decode = True    # written by callers (tests, tools/decode_bench.py): False = the six-launch decode layer; read when a decode cache is built
         self._decode_graphs: Dict[Tuple, Any] = {}   # written and read by generate(use_graph=True): (B, T, max_new, eos, pad) -> _GraphedDecode
-        # The hand-over of a backward sweep (_engine_backward_impl) between Trainer, the optimiser and the model.  Before the sweep,
-        # Trainer._device_step sets `contended_backward` and `grad_overwrite` and, with the incremental norm, installs the hook of
-        # FlatAdamW.begin_incremental_norm as `grad_ready_hook` (that call sets `dw_sumsq`; Trainer clears it otherwise).  The sweep counts
-        # itself in `_bw_serial`, zeroes the layers' matrix gradients first if `_dw_stale` and it accumulates, clears `_dw_stale`, records in
-        # `_dw_sumsq_used` whether its weight-gradient GEMMs fill `dw_sumsq`, and leaves `dx_chain_event`.  Afterwards the norm hook takes the
-        # fused squares only if `_dw_sumsq_used == _bw_serial`, FlatAdamW.clip_grad_norm_ takes the hook's partials only if every range
-        # reported under the current `_bw_serial`, Trainer resets `grad_overwrite` and takes `dx_chain_event`, and an optimiser pass that
-        # leaves the matrices un-zeroed sets `_dw_stale`.
-        self.contended_backward: Any = False   # Trainer (bench.py, tests) writes, the sweep reads: False / None, True / "128x128" or "ticketed" GEMM kernels beside collectives
-        self.grad_overwrite = False   # Trainer writes around a window's first backward, the sweep reads: its grouped dW GEMMs write (beta = 0) the matrix gradients
-        self._dw_stale = False        # FlatAdamW._apply_chunks(skip_matrix_zero) sets, the sweep and zero_grad clear: the matrix gradients hold the last window's values
-        self.dw_sumsq: Optional[torch.Tensor] = None   # begin_incremental_norm / Trainer write, the sweep and the norm hook read: fp32 [L, 4, 16] slots of the norm partials
-        self._dw_sumsq_used: Optional[int] = None      # the sweep writes, the norm hook reads: `_bw_serial` of the last sweep if it filled `dw_sumsq`
-        self._bw_serial = 0                            # the sweep increments; the norm hook and clip_grad_norm_ read
-        self.dx_chain_event: Optional[torch.cuda.Event] = None   # the sweep writes (end of its dX chain), Trainer takes it and resets it to None
+        # The hand-over of a backward sweep (_engine_backward_impl).  Its inputs are the attributes below, written by Trainer._device_step and
+        # the optimiser before it; what it reports -- its serial, whether its weight-gradient GEMMs fill `dw_sumsq`, the end of its dX chain --
+        # is the SweepRecord it leaves in `last_sweep`, which the clip norm (optim.IncrementalNorm) and Trainer read.
+        self.contended_backward: Any = False   # Trainer (bench.py, tests) writes: False / None, True / "128x128" or "ticketed" GEMM kernels beside collectives
+        self.grad_overwrite = False   # Trainer writes around a window's first backward: the sweep's grouped dW GEMMs write (beta = 0) the matrix gradients
+        self._dw_stale = False        # an optimiser pass with skip_matrix_zero sets, the sweep and zero_grad clear: the matrix gradients hold the last window's values
+        self.dw_sumsq: Optional[torch.Tensor] = None   # IncrementalNorm.arm / disarm write, the sweep and the norm hook read: fp32 [L, 4, 16] slots of the norm partials
+        self.last_sweep = SweepRecord()
         self.reset_parameters(seed)
         self.register_load_state_dict_post_hook(lambda m, ik: setattr(m, "_shadow_dirty", True))
 
@@ -712,7 +713,7 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
         return self._engine_backward_impl(sv, dloss, dhidden, taps)
 
     def _engine_backward_impl(self, sv, dloss: Optional[torch.Tensor], dhidden: Sequence[Optional[torch.Tensor]], taps=None):
-        self._bw_serial += 1   # lets a gradient hook tell which backward sweep reported a range
+        sweep = self.last_sweep = SweepRecord(self.last_sweep.serial + 1)
         cfg, cd = self.config, self.compute_dtype
         B, T, P, S = sv["B"], sv["T"], sv["P"], sv["S"]
         h, H, D, L = cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim, cfg.num_hidden_layers
@@ -777,12 +778,12 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
             self._zero_layer_matrices(range(L))
         self._dw_stale = False
         dw_beta = 0.0 if overwrite else 1.0
-        # squares of the final matrix gradients from the weight-gradient epilogues (FlatAdamW.begin_incremental_norm): only a sweep whose
-        # products all go through the grouped call can promise them -- it records its serial, the norm hook checks it
+        # squares of the final matrix gradients from the weight-gradient epilogues (optim.IncrementalNorm.arm): only a sweep whose
+        # products all go through the grouped call can promise them -- its record says so, the norm hook checks it
         dw_sq = self.dw_sumsq if (group_dw and taps is None) else None
         if dw_sq is not None and not self._dw_group_fuses_squares(sv["B"] * sv["S"]):
             dw_sq = None   # (h = 768 / 2048: the 256 x 256-tile kernel has no fused squares -- the norm hook's range pass is cheaper than a pass per matrix)
-        self._dw_sumsq_used = self._bw_serial if dw_sq is not None else None
+        sweep.filled_squares = dw_sq is not None
         pending_dw: List[dict] = []
         pending_layers: List[int] = []
 
@@ -935,7 +936,7 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
         # every layer's LayerNorm / distillation kernel -- the last readers of the teacher's hidden states -- is queued: a consumer
         # that only has to stay behind THOSE (the next step's teacher forward re-uses that memory) can wait for this event instead of
         # for the whole backward, whose side streams still carry ~0.3 ms of parameter-gradient tail
-        self.dx_chain_event = main.record_event()
+        sweep.dx_chain_event = main.record_event()
         ext0 = dhidden[0] if len(dhidden) > 0 else None
         if ext0 is not None:
             ext0 = ext0.reshape(rows, h)

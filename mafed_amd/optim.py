@@ -17,6 +17,7 @@ from typing import Optional, Tuple
 import torch
 
 from mafed_amd import ops
+from mafed_amd.dist import layer_ranges
 
 
 def lr_lambda(current_step: int, warmup_steps: int, total_steps: int) -> float:
@@ -31,6 +32,84 @@ def compute_warmup(n_batches: int, accumulate_grad_batches: int, warmup_perc: fl
     hard-coded upstream -- and warm-up is ``warmup_perc`` of it unless ``warmup_steps`` is configured."""
     total = math.ceil(n_batches / accumulate_grad_batches) * 60
     return total, int(warmup_steps if warmup_steps is not None else warmup_perc * total)
+
+
+class IncrementalNorm:
+    """The global gradient norm in pieces: the backward's gradient hook launches a range's sum-of-squares partials as soon as the range is
+    final -- under the rest of the backward -- so that the clip only has the finish kernel left (the one-pass norm reads 1.6 GB on the
+    optimiser step's critical path: 0.28 ms at 410M).  Owns the range plan, the partials buffer, the norm log and the record of which
+    sweep reported which range."""
+
+    LOG_SLOTS = 4096
+
+    def __init__(self, model):
+        """``plan`` = {trigger id: [(lo, hi, first partial slot), ...]} over the flat gradient buffer, in the order the backward finishes
+        the ranges (LM head = L, layers L-1 .. 0, embeddings / projector / every bias = -1)."""
+        per_layer, head, tail = layer_ranges(model)
+        L = len(per_layer)
+        trig = {L: [head], -1: list(tail), **{i: [r] for i, r in enumerate(per_layer)}}
+        flat = sorted(r for rs in trig.values() for r in rs)
+        if not (flat[0][0] == 0 and flat[-1][1] == model.flat_grads.numel() and all(a[1] == b[0] for a, b in zip(flat, flat[1:]))
+                and all(lo % 4 == 0 for lo, _ in flat)):
+            raise ValueError("the gradient ranges must tile the flat buffer, each from a 16-byte boundary")
+        if not all(per_layer[i][0] <= model.layer_matrix_range(i)[0] and model.layer_matrix_range(i)[1] == per_layer[i][1] for i in range(L)):
+            raise ValueError("a layer's gradient range must end with its four weight matrices")
+        self.model, self.n_layers = model, L
+        self.plan, slot = {}, 0
+        for t in [L] + list(range(L - 1, -1, -1)) + [-1]:
+            self.plan[t] = []
+            for lo, hi in trig[t]:
+                self.plan[t].append((lo, hi, slot))
+                slot += ops.gradnorm_blocks(hi - lo)
+        # behind the range partials: 16 slots per layer weight matrix (4 per layer) for the squares the weight-gradient GEMMs' epilogues
+        # leave (mafed_gemm_problem.sumsq) -- zero unless a backward uses them (arm)
+        self.dw_lo, self.dw_n = slot, 16 * 4 * L
+        dev = model.flat_grads.device
+        self.partials = torch.zeros(slot + self.dw_n, dtype=torch.float32, device=dev)
+        self.log = torch.zeros(self.LOG_SLOTS, dtype=torch.float32, device=dev)   # one slot per fused finish, round robin
+        self.log_i = 0
+        self.seen: Optional[dict] = None   # {trigger id: serial of the sweep that reported it} since arm(); None = consumed / never armed
+
+    def arm(self, fused_matrix_squares: bool = False):
+        """-> hook(i) for ``model.grad_ready_hook``, for the coming backward: called by the sweep on the stream that finished range i.
+        ``fused_matrix_squares``: the grouped weight-gradient GEMMs of THIS backward leave the squares of the layers' matrix gradients in
+        ``model.dw_sumsq`` slots (their epilogues hold the final values in registers); the hook then reads only a layer's LayerNorm
+        weights -- 1.2 GB of the 1.63 GB pass gone.  A sweep that could not fill them says so in its record (then the hook reads the
+        whole range)."""
+        self.seen = {}
+        sq = self.partials[self.dw_lo:]
+        sq.zero_()
+        self.model.dw_sumsq = sq.view(-1, 4, 16) if fused_matrix_squares else None
+        return self.hook
+
+    def hook(self, i) -> None:
+        model, sweep = self.model, self.model.last_sweep
+        fused = model.dw_sumsq is not None and 0 <= i < self.n_layers and sweep.filled_squares
+        for lo, hi, slot in self.plan.get(i, ()):
+            if fused:
+                hi = model.layer_matrix_range(i)[0]   # the LayerNorm weights in front of the matrices; the matrices' squares are in dw_sumsq
+            if hi > lo:
+                ops.gradnorm_partial(model.flat_grads[lo:hi], self.partials[slot:])
+        if self.seen is None:     # a backward outside Trainer.step() while the hook is still installed (the clip consumed the last
+            self.seen = {}        # window's record): its partials are simply never used
+        self.seen[i] = sweep.serial
+    hook.is_norm_hook = True   # FlatAdamW.arm_norm replaces / removes hooks of this kind only
+
+    def complete(self, serial: int) -> bool:
+        """Every range reported during sweep ``serial`` (a sweep that skipped layers, or a plugin's extra sweep after the reports, leaves
+        older partials behind: then the buffer is read in one pass)."""
+        return self.seen is not None and len(self.seen) == len(self.plan) and all(v == serial for v in self.seen.values())
+
+    def finish(self, max_norm: float, clip_out: torch.Tensor, advance=None) -> torch.Tensor:
+        """Fold the partials into ``clip_out`` = {norm, clip scale} -> the norm.  ``advance`` (ops.gradnorm_finish): the schedule advance
+        rides in the same launch, and the norm also goes to a log slot of its own, which is what is returned."""
+        if advance is None:
+            ops.gradnorm_finish(self.partials, max_norm, clip_out)
+            return clip_out[0]
+        i = self.log_i % self.LOG_SLOTS
+        self.log_i += 1
+        ops.gradnorm_finish(self.partials, max_norm, clip_out, norm_log=self.log[i:i + 1], advance=advance)
+        return self.log[i]
 
 
 class FlatAdamW:
@@ -65,6 +144,10 @@ class FlatAdamW:
         self.state_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self._sched = (0, 0)  # (warmup_steps, total_steps); total 0 = constant lr
         self.clip_out = torch.ones(2, dtype=torch.float32, device=dev)  # {grad norm, clip scale}
+        self._clip_pending = False   # clip_grad_norm_ sets, the optimiser pass clears: clip_out holds THIS step's scale (and guards the advance)
+        self._advanced = False       # clip_grad_norm_(fuse_advance) sets, advance() clears: the finish launch has advanced the schedule
+        # the clip norm from per-range partials that the backward launches; None: the model has no flat layer layout (one-pass norm only)
+        self.norm = IncrementalNorm(model) if hasattr(model, "layer_matrix_range") else None
         self.step_count = 0
         n_decay = model.decay_split()
         self.param_groups = [{"lr": lr, "initial_lr": lr, "weight_decay": weight_decay, "range": (0, n_decay)},
@@ -81,13 +164,13 @@ class FlatAdamW:
     def advance(self) -> None:
         """First kernel of an optimiser step (capturable): t += 1 and {lr(t-1), 1-b1^t, sqrt(1-b2^t)} -> lr_dev.  A no-op when
         clip_grad_norm_(fuse_advance=True) has already done it for this step inside the norm's finish launch."""
-        if getattr(self, "_advanced", False):
+        if self._advanced:
             self._advanced = False
             return
         # (with a clip pending the advance is guarded by it: a step whose gradient norm was not finite is skipped on the device --
         #  no parameter / state update in the AdamW kernel, no step-counter advance here; the host sees the non-finite norm in its log)
         ops.optim_advance_(self.state_dev, self.base_lr, self._sched[0], self._sched[1], self.betas[0], self.betas[1], self.lr_dev,
-                           clip=self.clip_out if getattr(self, "_clip_pending", False) else None)
+                           clip=self.clip_out if self._clip_pending else None)
 
     def host_advance(self) -> None:
         """Host mirror of the step counter (logging, state_dict); no device work."""
@@ -97,107 +180,47 @@ class FlatAdamW:
         self.model.zero_grad()
 
     # ---- global-norm clip ------------------------------------------------------------------------------------------------
-    def _norm_plan(self):
-        """{trigger id: [(lo, hi, first partial slot), ...]} over the flat gradient buffer, in the order the backward finishes the
-        ranges (LM head = L, layers L-1 .. 0, embeddings / projector / every bias = -1), or None when the ranges do not tile the
-        buffer exactly (then the norm is always the one-pass form)."""
-        if not hasattr(self, "_norm_plan_cache"):
-            plan = None
-            try:
-                from mafed_amd.dist import layer_ranges
-                per_layer, head, tail = layer_ranges(self.model)
-                L = len(per_layer)
-                trig = {L: [head], -1: list(tail)}
-                for i, r in enumerate(per_layer):
-                    trig[i] = [r]
-                flat = sorted(r for rs in trig.values() for r in rs)
-                ok = flat[0][0] == 0 and flat[-1][1] == self.model.flat_grads.numel() and all(a[1] == b[0] for a, b in zip(flat, flat[1:]))
-                ok = ok and all(lo % 4 == 0 for lo, _ in flat)
-                if ok:
-                    plan, slot = {}, 0
-                    for t in [L] + list(range(L - 1, -1, -1)) + [-1]:
-                        plan[t] = []
-                        for lo, hi in trig[t]:
-                            plan[t].append((lo, hi, slot))
-                            slot += ops.gradnorm_blocks(hi - lo)
-                    # behind the range partials: 16 slots per layer weight matrix (4 per layer) for the squares the weight-gradient GEMMs'
-                    # epilogues leave (mafed_gemm_problem.sumsq) -- zero unless a backward uses them (begin_incremental_norm)
-                    self._norm_dw_lo = slot
-                    has_mat = hasattr(self.model, "layer_matrix_range") and all(
-                        per_layer[i][0] <= self.model.layer_matrix_range(i)[0] and self.model.layer_matrix_range(i)[1] == per_layer[i][1] for i in range(L))
-                    self._norm_dw_n = 16 * 4 * L if has_mat else 0
-                    slot += self._norm_dw_n
-                    self._norm_slots = slot
-                    self._norm_partials = torch.zeros(slot, dtype=torch.float32, device=self.model.flat_grads.device)
-            except Exception:
-                plan = None
-            self._norm_plan_cache = plan
-        return self._norm_plan_cache
-
     def begin_incremental_norm(self, fused_matrix_squares: bool = False):
-        """-> hook(i) for ``model.grad_ready_hook`` (or None): called by the backward on the stream that finished range i, it
-        launches that range's sum-of-squares partials at once -- under the rest of the backward -- so that ``clip_grad_norm_`` only
-        has the finish kernel left (the one-pass norm reads 1.6 GB on the optimiser step's critical path: 0.28 ms at 410M).
-        ``fused_matrix_squares``: the grouped weight-gradient GEMMs of THIS backward leave the squares of the layers' matrix gradients in
-        ``model.dw_sumsq`` slots (their epilogues hold the final values in registers); the hook then reads only a layer's LayerNorm
-        weights -- 1.2 GB of the 1.63 GB pass gone.  The model clears ``dw_sumsq`` when a sweep could not use it (then the hook reads
-        the whole range, as before)."""
-        plan = self._norm_plan()
-        self._norm_seen = {}
-        if plan is None:
-            return None
-        g, part, model = self.model.flat_grads, self._norm_partials, self.model
-        L = model.config.num_hidden_layers
-        n_dw = getattr(self, "_norm_dw_n", 0)
-        if n_dw:
-            part[self._norm_dw_lo:].zero_()
-        model.dw_sumsq = part[self._norm_dw_lo:self._norm_dw_lo + n_dw].view(L, 4, 16) if (fused_matrix_squares and n_dw) else None
+        """-> hook(i) for ``model.grad_ready_hook`` (IncrementalNorm.arm), or None for a model without the flat layer layout."""
+        return self.norm.arm(fused_matrix_squares) if self.norm is not None else None
 
-        def hook(i):
-            fused = model.dw_sumsq is not None and 0 <= i < L and model._dw_sumsq_used == model._bw_serial
-            for lo, hi, slot in plan.get(i, ()):
-                if fused:
-                    hi = model.layer_matrix_range(i)[0]   # the LayerNorm weights in front of the matrices; the matrices' squares are in dw_sumsq
-                if hi > lo:
-                    ops.gradnorm_partial(g[lo:hi], part[slot:])
-            if self._norm_seen is None:     # a backward outside Trainer.step() while the hook is still installed (clip_grad_norm_ consumed the
-                self._norm_seen = {}        # last window's record): its partials are simply never used
-            self._norm_seen[i] = model._bw_serial   # which backward sweep this range's partials belong to
-        hook.is_norm_hook = True   # Trainer replaces / removes hooks of this kind only
-        return hook
+    def arm_norm(self, incremental: bool, fused_matrix_squares: bool = False) -> None:
+        """Trainer, in front of every backward of a single process: installs the incremental norm's hook as ``model.grad_ready_hook`` for
+        this backward, or removes it.  A hook installed by somebody else is left alone (the norm is then the one-pass form)."""
+        if self.norm is None:
+            return
+        cur = self.model.grad_ready_hook
+        if cur is not None and not getattr(cur, "is_norm_hook", False):
+            self.norm.seen = None
+        elif incremental:
+            self.model.grad_ready_hook = self.norm.arm(fused_matrix_squares)
+        else:
+            self.model.grad_ready_hook = None
+            self.model.dw_sumsq = None
 
-    NORM_LOG_SLOTS = 4096
+    @property
+    def advance_fused(self) -> bool:
+        """The last clip_grad_norm_(fuse_advance=True) ran the schedule advance in its finish launch: the norm it returned is a log slot of
+        its own (stable for IncrementalNorm.LOG_SLOTS steps), and the next advance() launches nothing."""
+        return self._advanced
 
     def clip_grad_norm_(self, max_norm: float, fuse_advance: bool = False) -> torch.Tensor:
         """Global L2 norm + clip scale on the device; the scale is applied inside the AdamW kernel.  Uses the partials left by the
         backward's hooks when every range reported in this backward, the single pass otherwise.
         ``fuse_advance`` (Trainer): with the partials present, the schedule advance of this optimiser step runs in the finish launch
-        (advance() then does nothing) and the returned norm is a view of a log slot of its own -- valid until NORM_LOG_SLOTS further
+        (advance() then does nothing) and the returned norm is a view of a log slot of its own -- valid until IncrementalNorm.LOG_SLOTS further
         optimiser steps have run -- instead of ``clip_out[0]``, which the next step overwrites (callers clone that one)."""
-        plan = getattr(self, "_norm_plan_cache", None)
-        seen = getattr(self, "_norm_seen", None)
-        last = self.model._bw_serial
-        # complete = every range reported during the LAST backward sweep (a sweep that skipped layers, or a plugin's extra sweep
-        # before it, leaves older partials behind: then the buffer is read in one pass as before)
-        if plan is not None and seen is not None and len(seen) == len(plan) and all(v == last for v in seen.values()):
-            if fuse_advance:
-                if not hasattr(self, "_norm_log"):
-                    self._norm_log = torch.zeros(self.NORM_LOG_SLOTS, dtype=torch.float32, device=self.clip_out.device)
-                    self._norm_log_i = 0
-                slot = self._norm_log[self._norm_log_i % self.NORM_LOG_SLOTS: self._norm_log_i % self.NORM_LOG_SLOTS + 1]
-                self._norm_log_i += 1
-                ops.gradnorm_finish(self._norm_partials, max_norm, self.clip_out, norm_log=slot,
-                                    advance=(self.state_dev, self.base_lr, self._sched[0], self._sched[1], self.betas[0], self.betas[1], self.lr_dev))
-                self._advanced = True
-                self._norm_seen = None
-                self._clip_pending = True
-                return slot[0]
-            ops.gradnorm_finish(self._norm_partials, max_norm, self.clip_out)
+        out = self.clip_out[0]
+        if self.norm is not None and self.norm.complete(self.model.last_sweep.serial):
+            self._advanced = self._advanced or fuse_advance
+            out = self.norm.finish(max_norm, self.clip_out, advance=(self.state_dev, self.base_lr, self._sched[0], self._sched[1], self.betas[0],
+                                                                     self.betas[1], self.lr_dev) if fuse_advance else None)
         else:
             ops.gradnorm_clip(self.model.flat_grads, max_norm, self.clip_out)
-        self._norm_seen = None
+        if self.norm is not None:
+            self.norm.seen = None
         self._clip_pending = True
-        return self.clip_out[0]
+        return out
 
     def step(self, grad_mul: float = 1.0) -> None:
         self.host_advance()
@@ -207,23 +230,12 @@ class FlatAdamW:
     def apply(self, grad_mul: float = 1.0, zero_grads: bool = False, skip_matrix_zero: bool = False) -> None:
         """Device half of a step: the AdamW kernels, reading this step's scalars from device memory.  ``zero_grads``: the same
         pass also zeroes the gradient buffer (optimizer.zero_grad() of the next window).  ``skip_matrix_zero`` (with ``zero_grads``): the
-        layers' weight-matrix gradients are left as they are -- the next window's first backward overwrites them (model.grad_overwrite)."""
-        m = self.model
-        clip = self.clip_out if getattr(self, "_clip_pending", False) else None
+        layers' weight-matrix gradients are left as they are -- the next window's first backward overwrites them (model.grad_overwrite);
+        the pass then runs chunk by chunk (``_chunks()``), otherwise as one launch per weight-decay segment."""
         if zero_grads and skip_matrix_zero:
-            self._apply_chunks(clip, grad_mul)
-            self._clip_pending = False
-            if m.flat_shadow is not None:
-                m._shadow_dirty = False
-            return
-        for grp in self.param_groups:
-            lo, hi = grp["range"]
-            if hi <= lo:
-                continue
-            self._segment_step(lo, hi, grp["weight_decay"], clip, grad_mul, zero_grad=zero_grads)
-        self._clip_pending = False
-        if m.flat_shadow is not None:
-            m._shadow_dirty = False
+            self._pass(self._chunks(), grad_mul, True, skip_matrix_zero=True)
+        else:
+            self._pass([(None, *g["range"], g["weight_decay"]) for g in self.param_groups if g["range"][1] > g["range"][0]], grad_mul, zero_grads)
 
     def _segment_step(self, lo: int, hi: int, wd: float, clip, grad_mul: float, zero_grad: bool, zero_n: Optional[int] = None) -> None:
         """The update rule on flat range [lo, hi) with weight decay ``wd``: one launch, the bf16 shadow written and (``zero_grad``) the
@@ -233,26 +245,30 @@ class FlatAdamW:
         ops.adamw_step_(m.flat_params[lo:hi], m.flat_grads[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], self.lr_dev,
                         self.betas[0], self.betas[1], self.eps, wd, 0, clip, grad_mul, shadow, zero_grad=zero_grad, zero_n=zero_n)
 
-    def _apply_chunks(self, clip, grad_mul: float, skip_matrix_zero: bool = True, events: Optional[dict] = None, stream=None):
-        """One AdamW launch per chunk of ``_chunks()`` on the current stream, the gradient zeroed in the same pass; a layer chunk zeroes only
-        its LayerNorm-weight part when ``skip_matrix_zero`` (mafed_adamw_step_partial_zero)."""
+    def _pass(self, chunks, grad_mul: float, zero_grads: bool, skip_matrix_zero: bool = False, events: Optional[dict] = None, stream=None) -> None:
+        """One optimiser pass on the current stream: one launch per (key, lo, hi, weight_decay) of ``chunks``, the gradient zeroed in the same
+        pass if ``zero_grads`` -- of a layer chunk only its LayerNorm-weight part when ``skip_matrix_zero`` (mafed_adamw_step_partial_zero) --,
+        an event of ``stream`` per chunk into ``events``; then the end of the pass: the clip scale is used up, the bf16 shadow is current."""
         m = self.model
-        for key, lo, hi, wd in self._chunks():
+        clip = self.clip_out if self._clip_pending else None
+        for key, lo, hi, wd in chunks:
             zn = None
             if skip_matrix_zero and isinstance(key, tuple) and key[0] == "layer":
                 mlo, mhi = m.layer_matrix_range(key[1])
                 assert lo <= mlo and mhi == hi, "layer chunk = [LayerNorm weights | weight matrices]"
                 zn = mlo - lo
-            self._segment_step(lo, hi, wd, clip, grad_mul, zero_grad=True, zero_n=zn)
+            self._segment_step(lo, hi, wd, clip, grad_mul, zero_grad=zero_grads, zero_n=zn)
             if events is not None:
                 events[key] = stream.record_event()
         if skip_matrix_zero:
             m._dw_stale = True   # (cleared by the next backward sweep: it overwrites the matrices, or zeroes them first)
+        self._clip_pending = False
+        if m.flat_shadow is not None:
+            m._shadow_dirty = False
 
     def _chunks(self):
         """(key, lo, hi, weight_decay) in the order the NEXT forward touches the parameters: everything the first kernels
         read (all biases / non-decayed tensors, token embedding, projector), then the layers bottom-up, then final LN + head."""
-        from mafed_amd.dist import layer_ranges
         m = self.model
         wd = self.param_groups[0]["weight_decay"]
         per_layer, head, tail = layer_ranges(m)
@@ -268,21 +284,11 @@ class FlatAdamW:
         for "pre", then for ("layer", i) right before layer i, then for "head" -- so the HBM-bound update of the upper layers
         runs under the MFMA-bound forward of the lower ones instead of in front of it.  The caller's stream must not touch
         parameters, optimiser state or gradients until it has waited for these events (the model's forward does)."""
-        m = self.model
-        clip = self.clip_out if getattr(self, "_clip_pending", False) else None
         main = torch.cuda.current_stream()
         stream.wait_event(main.record_event())  # gradients final, clip scale and {lr, bias corrections} on the device
         events = {}
         with torch.cuda.stream(stream):
-            if zero_grads:
-                self._apply_chunks(clip, grad_mul, skip_matrix_zero=skip_matrix_zero, events=events, stream=stream)
-            else:
-                for key, lo, hi, wd in self._chunks():
-                    self._segment_step(lo, hi, wd, clip, grad_mul, zero_grad=False)
-                    events[key] = stream.record_event()
-        self._clip_pending = False
-        if m.flat_shadow is not None:
-            m._shadow_dirty = False
+            self._pass(self._chunks(), grad_mul, zero_grads, skip_matrix_zero=zero_grads and skip_matrix_zero, events=events, stream=stream)
         return events
 
     def state_dict(self):

@@ -11,6 +11,7 @@ Nothing in a step synchronises with the host: loss / grad-norm come back as devi
 """
 from __future__ import annotations
 
+import os
 from types import SimpleNamespace
 from typing import Any, Dict, Optional
 
@@ -22,10 +23,7 @@ from mafed_amd.optim import FlatAdam, FlatAdamax, FlatAdamW, compute_warmup, get
 # config.optim -> optimiser (configure_optimizers, vqa_cont_learner.py:104-112)
 _OPTIMIZERS = {"adamw": FlatAdamW, "adam": FlatAdam, "adamax": FlatAdamax}
 
-
-import os as _os
-
-_EARLY_TEACHER = _os.environ.get("MAFED_EARLY_TEACHER", "1") != "0"   # A/B switch
+_EARLY_TEACHER = os.environ.get("MAFED_EARLY_TEACHER", "1") != "0"   # A/B switch
 
 
 class Trainer:
@@ -71,7 +69,7 @@ class Trainer:
         # written by the optimiser pass and 1.2 GB less read by the weight-gradient epilogues per step at 410M.  Single process, grouped
         # bf16 weight gradients only (`_overwrite_ok`); after a step the matrices' ``.grad`` holds the last gradient, not zeros.
         self.overwrite_weight_grads = bool(overwrite_weight_grads)
-        # the clip's norm of the layers' weight matrices from the weight-gradient GEMMs' own epilogues (FlatAdamW.begin_incremental_norm)
+        # the clip's norm of the layers' weight matrices from the weight-gradient GEMMs' own epilogues (IncrementalNorm.arm)
         self.fused_norm_squares = True
         self.global_step = 0
         self._one = None
@@ -102,14 +100,6 @@ class Trainer:
             loss = self.cl_method.compute_loss(self.model, loss, batch=batch)
         return loss, branch
 
-    @property
-    def contention_aware(self) -> bool:   # (round-3 name: True = the 128 x 128 kernels beside collectives)
-        return self.contention_mode == "128x128"
-
-    @contention_aware.setter
-    def contention_aware(self, v) -> None:
-        self.contention_mode = "128x128" if v else None
-
     def _overwrite_ok(self) -> bool:
         m = self.model
         return (self.overwrite_weight_grads and self.reducer is None and hasattr(m, "layer_matrix_range")
@@ -125,17 +115,12 @@ class Trainer:
                 self.reducer.begin_window()
             # collectives run beside this backward: the model keeps its GEMMs off the one-block-per-CU persistent kernels meanwhile
             self.model.contended_backward = self.contention_mode if (window_end and self.reducer.world > 1 and self.contention_mode) else False
-        inc_norm = (window_end and self.reducer is None and self.grad_norm and self.grad_norm > 0 and self.incremental_norm
-                    and getattr(self.cl_method, "grads_only_through_model", False) and hasattr(self.model, "grad_ready_hook")
-                    and self.model.flat_grads.is_cuda)
-        if self.reducer is None and hasattr(self.model, "grad_ready_hook"):
-            cur = self.model.grad_ready_hook
-            if cur is None or getattr(cur, "is_norm_hook", False):   # (a hook installed by somebody else is left alone)
-                self.model.grad_ready_hook = self.optimizer.begin_incremental_norm(fused_matrix_squares=self.fused_norm_squares) if inc_norm else None
-                if not inc_norm:
-                    self.model.dw_sumsq = None
-            else:
-                self.optimizer._norm_seen = None
+        if self.reducer is None:
+            # the clip norm from the partials this backward's gradient hook launches: last micro-batch of a window, plugins that touch
+            # gradients only through the model's backward
+            self.optimizer.arm_norm(bool(window_end and self.grad_norm and self.grad_norm > 0 and self.incremental_norm
+                                         and getattr(self.cl_method, "grads_only_through_model", False) and self.model.flat_grads.is_cuda),
+                                    fused_matrix_squares=self.fused_norm_squares)
         ow = self._overwrite_ok()
         self.model.grad_overwrite = bool(ow and window_start)
         loss, branch = self._training_step(batch, is_replay)
@@ -147,10 +132,10 @@ class Trainer:
         if torch.cuda.is_available() and hasattr(self.cl_method, "_prefetch_teacher"):
             # lets the next step's frozen-teacher forward start here, under this step's clip + AdamW
             # (the model's own event marks the end of the dX chain: the teacher forward then starts under the parameter-gradient tail)
-            ev = self.model.dx_chain_event if _EARLY_TEACHER else None
+            sweep = self.model.last_sweep
+            ev = sweep.dx_chain_event if _EARLY_TEACHER else None
             self.cl_method.backward_done_event = ev if ev is not None else torch.cuda.current_stream().record_event()
-            if ev is not None:
-                self.model.dx_chain_event = None
+            sweep.dx_chain_event = None
         rec: Dict[str, Any] = {"loss": loss.detach(), "branch": branch, "stepped": False}
         if window_end:
             self.cl_method.update_after_backward(model=self.model)  # on_before_optimizer_step
@@ -162,7 +147,7 @@ class Trainer:
             if self.grad_norm and self.grad_norm > 0:
                 gn = self.optimizer.clip_grad_norm_(self.grad_norm, fuse_advance=True)
                 # (fused finish + advance leaves the norm in a log slot of its own; the one-pass form returns clip_out[0], overwritten next step)
-                rec["grad_norm"] = gn if getattr(self.optimizer, "_advanced", False) else gn.clone()
+                rec["grad_norm"] = gn if self.optimizer.advance_fused else gn.clone()
             self.optimizer.advance()
             if self.pipeline_optimizer:
                 self.model._param_events = self.optimizer.apply_pipelined(self._opt_stream, skip_matrix_zero=ow)

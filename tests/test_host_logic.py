@@ -216,18 +216,17 @@ def test_ewc_foreign_module_path_matches_oracle():
 
 
 def test_clip_norm_plan_tiles_the_gradient_buffer():
-    """FlatAdamW._norm_plan: the per-hook ranges of the incremental clip norm (LM head, layers L-1 .. 0, embeddings / projector / biases)
+    """IncrementalNorm.plan: the per-hook ranges of the incremental clip norm (LM head, layers L-1 .. 0, embeddings / projector / biases)
     must tile the flat gradient buffer exactly once -- otherwise the norm would miss or double-count elements -- with 16-byte aligned
     starts and consecutive partial slots."""
     from mafed_amd import VLPythiaConfig, VLPythiaForCausalLM, ops
-    from mafed_amd.optim import FlatAdamW
+    from mafed_amd.optim import IncrementalNorm
     for L, h in ((5, 32), (3, 64)):
         cfg = VLPythiaConfig(vocab_size=64, hidden_size=h, num_hidden_layers=L, num_attention_heads=2, intermediate_size=4 * h,
                              vision_hidden_size=16, num_vision_tokens=4)
         model = VLPythiaForCausalLM(cfg, compute_dtype=torch.float32, device="cpu")
-        opt = FlatAdamW.__new__(FlatAdamW)     # no device state: only the plan is under test
-        opt.model = model
-        plan = opt._norm_plan()
+        norm = IncrementalNorm(model)
+        plan = norm.plan
         assert plan is not None and sorted(plan) == [-1] + list(range(L)) + [L]
         ranges = sorted((lo, hi, slot) for rs in plan.values() for lo, hi, slot in rs)
         assert ranges[0][0] == 0 and ranges[-1][1] == model.flat_grads.numel()
@@ -239,8 +238,8 @@ def test_clip_norm_plan_tiles_the_gradient_buffer():
             assert s == slot
             slot += ops.gradnorm_blocks(hi - lo)
         # (behind the range partials: 16 slots per layer weight matrix for the squares the weight-gradient epilogues leave)
-        assert slot == opt._norm_dw_lo and opt._norm_dw_n == 16 * 4 * L
-        assert slot + opt._norm_dw_n == opt._norm_slots == opt._norm_partials.numel()
+        assert slot == norm.dw_lo and norm.dw_n == 16 * 4 * L
+        assert slot + norm.dw_n == norm.partials.numel()
 
 
 def test_clip_tower_row_padding_minimises_tile_rounds():
