@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "attn.h"
+#include "row8.h"
 
 namespace mafed {
 
@@ -42,23 +43,9 @@ __device__ __forceinline__ int tile_off(int row, int chunk) {
   return row * 512 + ((chunk ^ (((row & 7) << 1) | ((row >> 3) & 1))) << 4);
 }
 
-__device__ __forceinline__ void unpack8(const uint4& v, float (&f)[8]) {
-  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
-  f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);
-  f[4] = __uint_as_float(v.z << 16); f[5] = __uint_as_float(v.z & 0xffff0000u);
-  f[6] = __uint_as_float(v.w << 16); f[7] = __uint_as_float(v.w & 0xffff0000u);
-}
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-  uint4 r;
-  r.x = (uint32_t)f32_to_bf16(f[0]) | ((uint32_t)f32_to_bf16(f[1]) << 16);
-  r.y = (uint32_t)f32_to_bf16(f[2]) | ((uint32_t)f32_to_bf16(f[3]) << 16);
-  r.z = (uint32_t)f32_to_bf16(f[4]) | ((uint32_t)f32_to_bf16(f[5]) << 16);
-  r.w = (uint32_t)f32_to_bf16(f[6]) | ((uint32_t)f32_to_bf16(f[7]) << 16);
-  return r;
-}
-
 // One 16-byte chunk (8 head-dim elements starting at chunk*8) of row `pos` of a q or k matrix, rotated (tf:111-151).
-// rowp points at element 0 of that row; rows >= S give zeros.
+// rowp points at element 0 of that row; rows >= S give zeros.  (Not row8.h's load_chunk_rot8: the `valid` select, the chunk ^ hc
+// partner and the packed result are part of these kernels' generated code.)
 __device__ __forceinline__ uint4 load_chunk_rot(const bf16_t* __restrict__ rowp, int chunk, int rot, const float* __restrict__ rc,
                                                 const float* __restrict__ rs, int pos, bool valid) {
   if (!valid) return make_uint4(0u, 0u, 0u, 0u);

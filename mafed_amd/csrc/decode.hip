@@ -3,7 +3,7 @@
 //
 //   A  decode_ln_qkv_fc1   both LayerNorms of the parallel-residual block folded into the prologue of ONE skinny product over the
 //                          concatenated output columns [ q | k | v | 4h ]: qkv row -> K/V cache, gelu(fc1) row -> a
-//   B  attention           (attn_ref.hip: attn_decode_flat_kernel)
+//   B  attention           (attn_decode.hip: attn_decode_flat_kernel)
 //   C  decode_out          x' = x + b_dense + b_fc2 + [ ao | a ] . [ W_dense | W_fc2 ]^T: one product over the concatenated K
 //
 // instead of LayerNorm, QKV, attention, dense, fc1, fc2 (six launches of 3 - 17 us for 29.5 MB of weights and 37.7 MB of K/V per layer

@@ -1,6 +1,7 @@
 // Shared fused epilogue of the dense contractions: bias -> GELU / GELU' -> residual adds -> beta*C -> store.
 #pragma once
 #include "common.h"
+#include "row8.h"
 
 namespace mafed {
 
@@ -79,30 +80,7 @@ __device__ __forceinline__ void epilogue_store4_pre(const GemmEpi& e, CT* __rest
 
 // 8 consecutive columns n..n+7 of row m (n % 8 == 0): the coalesced form used after the accumulators went through LDS
 // (16-byte bf16 / 32-byte fp32 stores, 128/256 contiguous bytes per row per 8 lanes).
-__device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
-  const float4 a = load4(p), b = load4(p + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-__device__ __forceinline__ void load8(const bf16_t* p, float (&v)[8]) {
-  const uint4 r = *reinterpret_cast<const uint4*>(p);
-  v[0] = __uint_as_float(r.x << 16); v[1] = __uint_as_float(r.x & 0xffff0000u);
-  v[2] = __uint_as_float(r.y << 16); v[3] = __uint_as_float(r.y & 0xffff0000u);
-  v[4] = __uint_as_float(r.z << 16); v[5] = __uint_as_float(r.z & 0xffff0000u);
-  v[6] = __uint_as_float(r.w << 16); v[7] = __uint_as_float(r.w & 0xffff0000u);
-}
-__device__ __forceinline__ void store8(float* p, const float (&v)[8]) {
-  store4(p, make_float4(v[0], v[1], v[2], v[3]));
-  store4(p + 4, make_float4(v[4], v[5], v[6], v[7]));
-}
-__device__ __forceinline__ void store8(bf16_t* p, const float (&v)[8]) {
-  uint4 r;
-  r.x = (uint32_t)f32_to_bf16(v[0]) | ((uint32_t)f32_to_bf16(v[1]) << 16);
-  r.y = (uint32_t)f32_to_bf16(v[2]) | ((uint32_t)f32_to_bf16(v[3]) << 16);
-  r.z = (uint32_t)f32_to_bf16(v[4]) | ((uint32_t)f32_to_bf16(v[5]) << 16);
-  r.w = (uint32_t)f32_to_bf16(v[6]) | ((uint32_t)f32_to_bf16(v[7]) << 16);
-  *reinterpret_cast<uint4*>(p) = r;
-}
-
+// (load8 / store8 / unpack8: row8.h)
 template <typename CT>
 __device__ __forceinline__ void epilogue_store8(const GemmEpi& e, CT* __restrict__ C, int64_t m, int64_t n, float (&v)[8]) {
   const int64_t off = m * e.ldc + n;
@@ -183,13 +161,6 @@ __device__ __forceinline__ void epi_prefetch(const GemmEpi& e, const CT* __restr
     p.f0 = load4(reinterpret_cast<const float*>(C) + off);
     p.f1 = load4(reinterpret_cast<const float*>(C) + off + 4);
   }
-}
-
-__device__ __forceinline__ void unpack8(const uint4& r, float (&v)[8]) {
-  v[0] = __uint_as_float(r.x << 16); v[1] = __uint_as_float(r.x & 0xffff0000u);
-  v[2] = __uint_as_float(r.y << 16); v[3] = __uint_as_float(r.y & 0xffff0000u);
-  v[4] = __uint_as_float(r.z << 16); v[5] = __uint_as_float(r.z & 0xffff0000u);
-  v[6] = __uint_as_float(r.w << 16); v[7] = __uint_as_float(r.w & 0xffff0000u);
 }
 
 // epilogue_store8 with the read operands taken from `p` (same arithmetic, same order of additions)

@@ -47,11 +47,10 @@ __global__ __launch_bounds__(256) void sumsq_accumulate_kernel(const float* __re
   if (threadIdx.x == 0) atomicAdd(sumsq16 + (blockIdx.x & 15), s);
 }
 
-__global__ __launch_bounds__(256) void gradnorm_finish_kernel(const float* __restrict__ partial, int nblk, float max_norm,
-                                                              float* __restrict__ out2) {
-  __shared__ float sm[4];
-  // eight loads in flight per thread (the piecewise norm leaves ~27k partials at 410M: one load per trip was a 50 us chain on the
-  // optimiser step's critical path); fixed association, so the result does not depend on the launch
+// This thread's share of the sum of partial[0 .. nblk) over a 256-thread block.  Eight loads in flight per thread (the
+// piecewise norm leaves ~27k partials at 410M: one load per trip was a 50 us chain on the optimiser step's critical path); fixed
+// association, so the result depends neither on the launch nor on which finish kernel folds.
+__device__ __forceinline__ float fold_partials(const float* __restrict__ partial, int nblk) {
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   int b = threadIdx.x;
   for (; b + 7 * 256 < nblk; b += 8 * 256) {
@@ -62,8 +61,13 @@ __global__ __launch_bounds__(256) void gradnorm_finish_kernel(const float* __res
     for (int u = 0; u < 8; ++u) acc[u] += v[u];
   }
   for (; b < nblk; b += 256) acc[0] += partial[b];
-  float s = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-  s = block_sum<256>(s, sm);
+  return ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+}
+
+__global__ __launch_bounds__(256) void gradnorm_finish_kernel(const float* __restrict__ partial, int nblk, float max_norm,
+                                                              float* __restrict__ out2) {
+  __shared__ float sm[4];
+  const float s = block_sum<256>(fold_partials(partial, nblk), sm);
   if (threadIdx.x == 0) {
     const float norm = sqrtf(s);
     out2[0] = norm;
@@ -73,6 +77,7 @@ __global__ __launch_bounds__(256) void gradnorm_finish_kernel(const float* __res
   }
 }
 
+// (Not a third rule of adam_family_pass below: with its body in a device function this kernel's instructions change.)
 template <bool SHADOW, bool ZERO_G = false>
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, int64_t n, const float* __restrict__ lr_dev, float beta1,
@@ -251,18 +256,7 @@ __global__ __launch_bounds__(256) void gradnorm_finish_advance_kernel(const floa
                                                                       long long* __restrict__ state, double base_lr, long long warmup,
                                                                       long long total, double b1, double b2, float* __restrict__ hyper) {
   __shared__ float sm[4];
-  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  int b = threadIdx.x;
-  for (; b + 7 * 256 < nblk; b += 8 * 256) {   // (same association as gradnorm_finish_kernel: bit-identical norm)
-    float v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = partial[b + u * 256];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc[u] += v[u];
-  }
-  for (; b < nblk; b += 256) acc[0] += partial[b];
-  float s = ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-  s = block_sum<256>(s, sm);
+  const float s = block_sum<256>(fold_partials(partial, nblk), sm);
   if (threadIdx.x == 0) {
     const float norm = sqrtf(s);
     out2[0] = norm;
@@ -316,12 +310,10 @@ extern "C" int mafed_gradnorm_clip(const float* g, int64_t n, float max_norm, fl
     return MAFED_EWORKSPACE;
   }
   hipStream_t st = as_stream(stream);
-  int64_t nb = cdiv(n / 4 + 1, 256 * 4);
-  if (nb > GN_BLOCKS) nb = GN_BLOCKS;
-  if (nb < 1) nb = 1;
+  const int nb = mafed_gradnorm_blocks(n);
   launch(K_GRADNORM, (double)n * 4.0, gradnorm_partial_kernel, dim3((unsigned)nb), dim3(256), 0, st, g, n, (float*)workspace);
   MAFED_CHECK_LAUNCH("gradnorm(partial)");
-  launch(K_SMALL, 0.0, gradnorm_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, (int)nb, max_norm, out2);
+  launch(K_SMALL, 0.0, gradnorm_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, nb, max_norm, out2);
   MAFED_CHECK_LAUNCH("gradnorm(finish)");
   return MAFED_OK;
 }
@@ -362,55 +354,12 @@ extern "C" int mafed_gradnorm_finish_advance(const float* partial, int n_partial
   return MAFED_OK;
 }
 
-static int adamw_impl(float* p, float* g, float* m, float* v, int64_t n, const float* lr_dev, float beta1, float beta2, float eps,
-                      float weight_decay, int step, const float* clip_dev, float grad_mul, void* p_bf16, int64_t zero_n, void* stream) {
-  MAFED_CHECK_ARG(zero_n >= 0 && zero_n <= n && (zero_n == n || zero_n % 4 == 0), "adamw_step: zero_n must be 0 .. n and a multiple of 4 (or n)");
-  const bool zero_g = zero_n > 0;
-  MAFED_CHECK_ARG(p && g && m && v && lr_dev && n >= 0 && step >= 0, "adamw_step: bad arguments");
-  MAFED_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "adamw_step: buffers must be 16-byte aligned");
-  MAFED_CHECK_ARG(!p_bf16 || ((uintptr_t)p_bf16 & 7) == 0, "adamw_step: p_bf16 must be 8-byte aligned");
-  if (n == 0) return MAFED_OK;
-  // bias corrections in double on the host, exactly as math.sqrt(1 - b2**t) / (1 - b1**t) (adamw.py:94-97)
-  // step == 0: the kernel reads {lr, 1-b1^t, sqrt(1-b2^t)} from lr_dev[0..2] (graph-replayable form)
-  const double bc1 = step > 0 ? 1.0 - pow((double)beta1, (double)step) : 0.0;
-  const double bc2 = step > 0 ? 1.0 - pow((double)beta2, (double)step) : 0.0;
-  hipStream_t st = as_stream(stream);
-  int64_t nb = cdiv(n / 4 + 1, 256);
-  if (nb > 4096) nb = 4096;
-  // algorithmic bytes: p, m, v read + written, g read (+ the bf16 shadow weight written, + the gradient zeroed) per parameter
-  const double bytes = (double)n * (28.0 + (p_bf16 ? 2.0 : 0.0)) + (double)zero_n * 4.0;
-#define MAFED_ADAMW(SH, ZG)                                                                                                          \
-  launch(K_ADAMW, bytes, adamw_kernel<SH, ZG>, dim3((unsigned)nb), dim3(256), 0, st, p, g, m, v, n, lr_dev, beta1, beta2, eps, weight_decay, \
-         (float)bc1, (float)sqrt(bc2), clip_dev, grad_mul, (bf16_t*)p_bf16, zero_n)
-  if (p_bf16 && zero_g) MAFED_ADAMW(true, true);
-  else if (p_bf16) MAFED_ADAMW(true, false);
-  else if (zero_g) MAFED_ADAMW(false, true);
-  else MAFED_ADAMW(false, false);
-#undef MAFED_ADAMW
-  MAFED_CHECK_LAUNCH("adamw_step");
-  return MAFED_OK;
-}
+enum AdamRule { RULE_ADAMW = 0, RULE_ADAM_L2 = 1, RULE_ADAMAX = 2 };
 
-extern "C" int mafed_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_dev, float beta1, float beta2,
-                                float eps, float weight_decay, int step, const float* clip_dev, float grad_mul, void* p_bf16,
-                                void* stream) {
-  return adamw_impl(p, const_cast<float*>(g), m, v, n, lr_dev, beta1, beta2, eps, weight_decay, step, clip_dev, grad_mul, p_bf16, 0, stream);
-}
-
-extern "C" int mafed_adamw_step_zero_grad(float* p, float* g, float* m, float* v, int64_t n, const float* lr_dev, float beta1, float beta2,
-                                          float eps, float weight_decay, int step, const float* clip_dev, float grad_mul, void* p_bf16,
-                                          void* stream) {
-  return adamw_impl(p, g, m, v, n, lr_dev, beta1, beta2, eps, weight_decay, step, clip_dev, grad_mul, p_bf16, n, stream);
-}
-
-extern "C" int mafed_adamw_step_partial_zero(float* p, float* g, float* m, float* v, int64_t n, const float* lr_dev, float beta1, float beta2,
-                                             float eps, float weight_decay, int step, const float* clip_dev, float grad_mul, void* p_bf16,
-                                             int64_t zero_n, void* stream) {
-  return adamw_impl(p, g, m, v, n, lr_dev, beta1, beta2, eps, weight_decay, step, clip_dev, grad_mul, p_bf16, zero_n, stream);
-}
-
-enum AdamRule { RULE_ADAM_L2 = 0, RULE_ADAMAX = 1 };
-
+// The three update rules behind every entry point below.  The betas come in double, as torch's Python floats and mafed_optim_advance's
+// (AdamW's fp32 betas widen exactly): for the torch rules 1 - beta is formed before the rounding to fp32 (from fp32 betas, 1 - 0.999f
+// is 1.3e-5 off).  step > 0: bias corrections in double on the host, exactly as math.sqrt(1 - b2**t) / (1 - b1**t) (adamw.py:94-97) and
+// the same numbers as the device advance's; step == 0: the kernel reads {lr, 1-b1^t, sqrt(1-b2^t)} from lr_dev[0..2] (graph-replayable).
 static int adam_family_impl(AdamRule rule, const char* name, float* p, float* g, float* m, float* s, int64_t n, const float* lr_dev,
                             double beta1, double beta2, float eps, float weight_decay, int step, const float* clip_dev, float grad_mul,
                             void* p_bf16, int64_t zero_n, void* stream) {
@@ -418,36 +367,52 @@ static int adam_family_impl(AdamRule rule, const char* name, float* p, float* g,
   MAFED_CHECK_ARG(zero_n >= 0 && zero_n <= n && (zero_n == n || zero_n % 4 == 0), "%s: zero_n must be 0 .. n and a multiple of 4 (or n)", name);
   MAFED_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)s) & 15) == 0, "%s: buffers must be 16-byte aligned", name);
   MAFED_CHECK_ARG(!p_bf16 || ((uintptr_t)p_bf16 & 7) == 0, "%s: p_bf16 must be 8-byte aligned", name);
-  MAFED_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.f && weight_decay >= 0.f,
+  MAFED_CHECK_ARG(rule == RULE_ADAMW || (beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.f && weight_decay >= 0.f),
                   "%s: betas must be in [0, 1), eps and weight_decay >= 0", name);
   if (n == 0) return MAFED_OK;
-  // the betas come in double, as torch's Python floats and mafed_optim_advance's: 1 - beta is formed before the rounding to fp32 (from
-  // fp32 betas, 1 - 0.999f is 1.3e-5 off).  step > 0: bias corrections in double on the host, the same numbers as the device advance's;
-  // step == 0: the kernel reads {lr, 1-b1^t, sqrt(1-b2^t)} from lr_dev[0..2]
   const double bc1 = step > 0 ? 1.0 - pow(beta1, (double)step) : 0.0;
   const double bc2 = step > 0 ? 1.0 - pow(beta2, (double)step) : 0.0;
   hipStream_t st = as_stream(stream);
   int64_t nb = cdiv(n / 4 + 1, 256);
   if (nb > 4096) nb = 4096;
-  const double bytes = (double)n * (28.0 + (p_bf16 ? 2.0 : 0.0)) + (double)zero_n * 4.0;   // as adamw_impl
+  // algorithmic bytes: p, m, s read + written, g read (+ the bf16 shadow weight written, + the gradient zeroed) per parameter
+  const double bytes = (double)n * (28.0 + (p_bf16 ? 2.0 : 0.0)) + (double)zero_n * 4.0;
   const bool zero_g = zero_n > 0;
-#define MAFED_ADAM_FAMILY(KERNEL, SH, ZG)                                                                                                \
-  launch(K_ADAMW, bytes, KERNEL<SH, ZG>, dim3((unsigned)nb), dim3(256), 0, st, p, g, m, s, n, lr_dev, (float)beta1, (float)beta2,          \
-         (float)(1.0 - beta1), (float)(1.0 - beta2), eps, weight_decay, (float)bc1, (float)sqrt(bc2), clip_dev, grad_mul, (bf16_t*)p_bf16, zero_n)
-#define MAFED_ADAM_FAMILY_ALL(KERNEL)                              \
-  if (p_bf16 && zero_g) MAFED_ADAM_FAMILY(KERNEL, true, true);     \
-  else if (p_bf16) MAFED_ADAM_FAMILY(KERNEL, true, false);         \
-  else if (zero_g) MAFED_ADAM_FAMILY(KERNEL, false, true);         \
-  else MAFED_ADAM_FAMILY(KERNEL, false, false)
-  if (rule == RULE_ADAM_L2) {
-    MAFED_ADAM_FAMILY_ALL(adam_l2_kernel);
-  } else {
-    MAFED_ADAM_FAMILY_ALL(adamax_kernel);
-  }
-#undef MAFED_ADAM_FAMILY_ALL
-#undef MAFED_ADAM_FAMILY
+#define MAFED_ADAM_HEAD(KERNEL, SH, ZG) K_ADAMW, bytes, KERNEL<SH, ZG>, dim3((unsigned)nb), dim3(256), 0, st, p, g, m, s, n, lr_dev, (float)beta1, (float)beta2
+#define MAFED_ADAM_TAIL eps, weight_decay, (float)bc1, (float)sqrt(bc2), clip_dev, grad_mul, (bf16_t*)p_bf16, zero_n
+#define MAFED_ADAM_GO(SH, ZG)                                                                                                                   \
+  do {                                                                                                                                          \
+    if (rule == RULE_ADAMW) launch(MAFED_ADAM_HEAD(adamw_kernel, SH, ZG), MAFED_ADAM_TAIL);                                                     \
+    else if (rule == RULE_ADAM_L2) launch(MAFED_ADAM_HEAD(adam_l2_kernel, SH, ZG), (float)(1.0 - beta1), (float)(1.0 - beta2), MAFED_ADAM_TAIL); \
+    else launch(MAFED_ADAM_HEAD(adamax_kernel, SH, ZG), (float)(1.0 - beta1), (float)(1.0 - beta2), MAFED_ADAM_TAIL);                            \
+  } while (0)
+  if (p_bf16 && zero_g) MAFED_ADAM_GO(true, true);
+  else if (p_bf16) MAFED_ADAM_GO(true, false);
+  else if (zero_g) MAFED_ADAM_GO(false, true);
+  else MAFED_ADAM_GO(false, false);
+#undef MAFED_ADAM_GO
+#undef MAFED_ADAM_TAIL
+#undef MAFED_ADAM_HEAD
   MAFED_CHECK_LAUNCH(name);
   return MAFED_OK;
+}
+
+extern "C" int mafed_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, const float* lr_dev, float beta1, float beta2,
+                                float eps, float weight_decay, int step, const float* clip_dev, float grad_mul, void* p_bf16,
+                                void* stream) {
+  return adam_family_impl(RULE_ADAMW, "adamw_step", p, const_cast<float*>(g), m, v, n, lr_dev, beta1, beta2, eps, weight_decay, step, clip_dev, grad_mul, p_bf16, 0, stream);
+}
+
+extern "C" int mafed_adamw_step_zero_grad(float* p, float* g, float* m, float* v, int64_t n, const float* lr_dev, float beta1, float beta2,
+                                          float eps, float weight_decay, int step, const float* clip_dev, float grad_mul, void* p_bf16,
+                                          void* stream) {
+  return adam_family_impl(RULE_ADAMW, "adamw_step", p, g, m, v, n, lr_dev, beta1, beta2, eps, weight_decay, step, clip_dev, grad_mul, p_bf16, n, stream);
+}
+
+extern "C" int mafed_adamw_step_partial_zero(float* p, float* g, float* m, float* v, int64_t n, const float* lr_dev, float beta1, float beta2,
+                                             float eps, float weight_decay, int step, const float* clip_dev, float grad_mul, void* p_bf16,
+                                             int64_t zero_n, void* stream) {
+  return adam_family_impl(RULE_ADAMW, "adamw_step", p, g, m, v, n, lr_dev, beta1, beta2, eps, weight_decay, step, clip_dev, grad_mul, p_bf16, zero_n, stream);
 }
 
 extern "C" int mafed_adam_step(float* p, float* g, float* m, float* v, int64_t n, const float* lr_dev, double beta1, double beta2, float eps,

@@ -158,7 +158,8 @@ class GenerationMixin:
 
     def _beam_search(self, feats, ids, am, pad_token_id, eos_token_id, k: int, max_new: int, use_cache: bool, length_penalty: float,
                      early_stopping, nrs: int, return_dict: bool):
-        """Beam search (generate(num_beams=k)); every decision on the device (csrc/beam.hip), one host synchronisation at the end.
+        """Beam search (generate(num_beams=k)); every decision on the device (csrc/beam.hip; the beams' attention is
+        csrc/attn_decode_beam.hip), one host synchronisation at the end.
         Per step: mafed_beam_candidates (top 2k of log_softmax + running score per sample) and mafed_beam_update (finished set,
         continuing beams, early stopping, ancestry / history rewrite).  The loop runs to max_new_tokens like the greedy path: a sample
         whose result is final stops changing (HF leaves the loop once every sample is such), and the output is cut at the end."""

@@ -1,5 +1,5 @@
 """GPU: beam search (``generate(num_beams=k)``) over the shared-prefix KV cache against transformers' own beam search
-(tests/golden/beam.npz, tools/gen_beam_golden.py), and the three beam kernels (csrc/beam.hip) plus the 64-row blocks of the
+(tests/golden/beam.npz, tools/gen_beam_golden.py), and the three beam kernels (csrc/beam.hip, csrc/attn_decode_beam.hip) plus the 64-row blocks of the
 decode layer kernels against their references."""
 import numpy as np
 import pytest
