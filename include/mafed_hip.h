@@ -142,6 +142,27 @@ int mafed_layernorm_bwd_rows(const void* dy1, const void* dy2, mafed_dtype dy_dt
                              float inj_mul, int want_dxsum, void* workspace, size_t workspace_bytes, void* stream);
 int mafed_layernorm_bwd_params(int64_t rows, int h, float* dw1, float* db1, float* dw2, float* db2, float* dxsum_a, float* dxsum_b,
                                const void* workspace, size_t workspace_bytes, void* stream);
+/* mafed_layernorm_bwd / mafed_layernorm_bwd_rows with the teacher rows of the injection read where they are stored (a slab of a resident
+ * teacher cache, FeatureDistillation.build_teacher_cache) instead of from a dense fp32 [rows,h] copy of the batch's rows:
+ *   teacher        [n,S,h] in teacher_dtype: MAFED_F32, or MAFED_BF16 (widened to fp32 at the load; needs an 8-byte aligned base)
+ *   sample_index   int32 [rows / S] device, or NULL: the teacher row of token (b, s) is teacher[(sample_index ? sample_index[b] : b) * S + s]
+ *                  (offset formed in 64 bits); x, dy, the mask and the row class keep using b.  Entries must lie in [0, n); an index
+ *                  without a teacher is MAFED_EINVAL.
+ * Every other argument as in the call without the suffix, which is this one with (teacher, MAFED_F32, NULL): same kernel, same bits. */
+int mafed_layernorm_bwd_indexed(const void* dy1, const void* dy2, mafed_dtype dy_dtype,
+                                const float* x, const float* mean, const float* rstd,
+                                const float* w1, const float* w2, int64_t rows, int h,
+                                const float* dres, float* dx, void* dx_lp,
+                                float* dw1, float* db1, float* dw2, float* db2,
+                                const void* teacher, mafed_dtype teacher_dtype, const int* sample_index,
+                                const int64_t* attention_mask, int S, int P, int T,
+                                const float* inj_scale_dev, float inj_mul, float* dxsum_a, float* dxsum_b,
+                                void* workspace, size_t workspace_bytes, void* stream);
+int mafed_layernorm_bwd_rows_indexed(const void* dy1, const void* dy2, mafed_dtype dy_dtype, const float* x, const float* mean,
+                                     const float* rstd, const float* w1, const float* w2, int64_t rows, int h, const float* dres, float* dx,
+                                     void* dx_lp, const void* teacher, mafed_dtype teacher_dtype, const int* sample_index,
+                                     const int64_t* attention_mask, int S, int P, int T, const float* inj_scale_dev, float inj_mul,
+                                     int want_dxsum, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- attention (tf:154-236 eager path / flash-attn-2 wheel, README.md:16) ------------------------------------
  * qkv: [B,S,H,3,D] exactly as the fused query_key_value GEMM leaves it (per-head {q,k,v} interleave, tf:204-207).
@@ -349,6 +370,25 @@ int mafed_distill_combine(const float* sums, int n_layers, const float* layer_co
 int mafed_distill_cls_fwd(const float* s, const float* t, int B, int S, int h, float* out1, void* stream);
 int mafed_distill_cls_bwd(const float* s, const float* t, int B, int S, int h, const float* coef_dev, float* ds,
                           int accumulate, void* stream);
+/* The four calls above with the teacher rows read where they are stored (one layer's slab of a resident teacher cache) instead of from
+ * a dense fp32 [B,S,h] tensor:
+ *   teacher        [n,S,h] in teacher_dtype: MAFED_F32, or MAFED_BF16 (each element widened to fp32 at the load, everything after the
+ *                  load unchanged; needs h % 4 == 0 and an 8-byte aligned base).  A bf16 teacher IS the distillation target: the sums
+ *                  and gradients are those of the rounded rows (relative rounding <= 2^-9 per element).
+ *   sample_index   int32 [B] device, or NULL: the teacher row of token (b, s) is teacher[(sample_index ? sample_index[b] : b) * S + s]
+ *                  (offset formed in 64 bits); s, ds, attention_mask and the row class keep using b.  Entries must lie in [0, n).
+ * mafed_distill_fwd(s, t, ...) is mafed_distill_fwd_indexed(s, t, MAFED_F32, NULL, ...), and likewise the other three: the same kernel on
+ * the same values, the same order of every sum. */
+int mafed_distill_fwd_indexed(const float* s, const void* teacher, mafed_dtype teacher_dtype, const int* sample_index,
+                              const int64_t* attention_mask, int B, int S, int P, int h, int cosine, float* out4,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int mafed_distill_bwd_indexed(const float* s, const void* teacher, mafed_dtype teacher_dtype, const int* sample_index,
+                              const int64_t* attention_mask, int B, int S, int P, int h, int cosine, const float* coef_dev,
+                              float* ds, int accumulate, void* stream);
+int mafed_distill_cls_fwd_indexed(const float* s, const void* teacher, mafed_dtype teacher_dtype, const int* sample_index,
+                                  int B, int S, int h, float* out1, void* stream);
+int mafed_distill_cls_bwd_indexed(const float* s, const void* teacher, mafed_dtype teacher_dtype, const int* sample_index,
+                                  int B, int S, int h, const float* coef_dev, float* ds, int accumulate, void* stream);
 
 /* ---- optimiser side -------------------------------------------------------------------------------------------
  * Global L2 norm of a flat fp32 gradient buffer (Lightning gradient_clip_val -> clip_grad_norm_, mafed/train.py:288):

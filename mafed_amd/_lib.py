@@ -58,6 +58,9 @@ SIGNATURES = {
     "mafed_layernorm_bwd": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _f, _p, _p, _p, _z, _p]),
     "mafed_layernorm_bwd_rows": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _l, _i, _p, _p, _p, _p, _p, _i, _i, _i, _p, _f, _i, _p, _z, _p]),
     "mafed_layernorm_bwd_params": (_i, [_l, _i, _p, _p, _p, _p, _p, _p, _p, _z, _p]),
+    "mafed_layernorm_bwd_indexed": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _p, _f, _p, _p,
+                                         _p, _z, _p]),
+    "mafed_layernorm_bwd_rows_indexed": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _l, _i, _p, _p, _p, _p, _i, _p, _p, _i, _i, _i, _p, _f, _i, _p, _z, _p]),
     "mafed_attn_fwd": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
     "mafed_attn_bwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
     "mafed_attn_bwd_colsum": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p]),
@@ -73,6 +76,10 @@ SIGNATURES = {
     "mafed_distill_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p]),
     "mafed_distill_cls_fwd": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "mafed_distill_cls_bwd": (_i, [_p, _p, _i, _i, _i, _p, _p, _i, _p]),
+    "mafed_distill_fwd_indexed": (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p, _z, _p]),
+    "mafed_distill_bwd_indexed": (_i, [_p, _p, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p]),
+    "mafed_distill_cls_fwd_indexed": (_i, [_p, _p, _i, _p, _i, _i, _i, _p, _p]),
+    "mafed_distill_cls_bwd_indexed": (_i, [_p, _p, _i, _p, _i, _i, _i, _p, _p, _i, _p]),
     "mafed_gradnorm_workspace_bytes": (_z, [_l]),
     "mafed_gradnorm_clip": (_i, [_p, _l, _f, _p, _p, _z, _p]),
     "mafed_gradnorm_blocks": (_i, [_l]),

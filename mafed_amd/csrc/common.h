@@ -182,6 +182,13 @@ __device__ __forceinline__ int modality_class(int64_t row, int S, int P, int T, 
   return attention_mask[b * T + (s - P)] != 0 ? 0 : 2;
 }
 
+// Teacher rows are read where they are stored: token (b, s) of the batch is row sample_index[b] * S + s of the teacher pointer (a slab
+// of the teacher cache, [n, S, h]), or row b * S + s without an index (a dense [B, S, h] tensor).  The index word is wave-uniform and is
+// fetched beside the mask word; the student row, the mask and the modality class keep using b.
+__device__ __forceinline__ int64_t teacher_sample(const int* __restrict__ sample_index, int64_t b) {
+  return sample_index ? (int64_t)sample_index[b] : b;
+}
+
 static inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 

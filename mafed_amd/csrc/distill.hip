@@ -11,8 +11,10 @@ constexpr int DS_MAX_BLOCKS = 1024;
 
 // Row sums over h columns, 1024 columns (4 x 16 B per lane and tensor) per step: the eight loads of a step are unconditional
 // (columns past h re-read column 0 and are masked out afterwards) so that they are all in flight together -- a `c < h` loop with one
-// load pair per trip ran as h / 256 dependent round trips per row.
-__device__ __forceinline__ void row_stats(const float* __restrict__ s, const float* __restrict__ t, int h, int lane, float& dd,
+// load pair per trip ran as h / 256 dependent round trips per row.  TT = teacher element type: fp32 (16 B per lane and piece) or bf16
+// (8 B, widened at the load); the column mapping and with it the order of every sum is the same for both.
+template <typename TT>
+__device__ __forceinline__ void row_stats(const float* __restrict__ s, const TT* __restrict__ t, int h, int lane, float& dd,
                                           float& ss, float& tt, float& st) {
   dd = ss = tt = st = 0.f;
   for (int c0 = 0; c0 < h; c0 += 1024) {
@@ -43,8 +45,9 @@ __device__ __forceinline__ float cos_dist(float ss, float tt, float st) {
   return 1.0f - st / sqrtf((ss + EPS) * (tt + EPS));
 }
 
-template <bool COSINE>
-__global__ __launch_bounds__(256) void distill_fwd_kernel(const float* __restrict__ s, const float* __restrict__ t,
+template <bool COSINE, typename TT>
+__global__ __launch_bounds__(256) void distill_fwd_kernel(const float* __restrict__ s, const TT* __restrict__ t,
+                                                          const int* __restrict__ sample_index,
                                                           const int64_t* __restrict__ attention_mask, int64_t rows, int S, int P,
                                                           int T, int h, float* __restrict__ partial) {
   __shared__ float sm[4][4];
@@ -56,8 +59,9 @@ __global__ __launch_bounds__(256) void distill_fwd_kernel(const float* __restric
     const int64_t bi = row / S;
     const int si = (int)(row - bi * S);
     const int64_t mv = attention_mask[bi * T + (si < P ? 0 : si - P)];
+    const int64_t trow = teacher_sample(sample_index, bi) * S + si;
     float dd, ss, tt, st;
-    row_stats(s + row * h, t + row * h, h, lane, dd, ss, tt, st);
+    row_stats(s + row * h, t + trow * h, h, lane, dd, ss, tt, st);
     const int cls = si < P ? 1 : (mv != 0 ? 0 : 2);
     if (cls == 2) continue;
     float d;
@@ -89,18 +93,21 @@ __global__ __launch_bounds__(256) void distill_finish_kernel(const float* __rest
   }
 }
 
-template <bool COSINE>
-__global__ __launch_bounds__(256) void distill_bwd_kernel(const float* __restrict__ s, const float* __restrict__ t,
+template <bool COSINE, typename TT>
+__global__ __launch_bounds__(256) void distill_bwd_kernel(const float* __restrict__ s, const TT* __restrict__ t,
+                                                          const int* __restrict__ sample_index,
                                                           const int64_t* __restrict__ attention_mask, int64_t rows, int S, int P,
                                                           int T, int h, const float* __restrict__ coef, float* __restrict__ ds,
                                                           int accumulate) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t row = (int64_t)blockIdx.x * 4 + wave;
   if (row >= rows) return;
+  const int64_t bi = row / S;
+  const int64_t trow = teacher_sample(sample_index, bi) * S + (row - bi * S);
   const int cls = modality_class(row, S, P, T, attention_mask);
   const float c = cls == 2 ? 0.f : coef[cls];
   const float* sr = s + row * h;
-  const float* tr = t + row * h;
+  const TT* tr = t + trow * h;
   float* dr = ds + row * h;
   if (c == 0.f) {
     if (!accumulate)
@@ -134,14 +141,16 @@ __global__ __launch_bounds__(256) void distill_bwd_kernel(const float* __restric
 }
 
 // CLS variant: token 0 of every sample, cosine, mean over the batch.  B is small: one block, one wave per sample.
-__global__ __launch_bounds__(256) void distill_cls_fwd_kernel(const float* __restrict__ s, const float* __restrict__ t, int B, int S,
-                                                              int h, float* __restrict__ out1) {
+template <typename TT>
+__global__ __launch_bounds__(256) void distill_cls_fwd_kernel(const float* __restrict__ s, const TT* __restrict__ t,
+                                                              const int* __restrict__ sample_index, int B, int S, int h,
+                                                              float* __restrict__ out1) {
   __shared__ float sm[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float acc = 0.f;
   for (int b = wave; b < B; b += 4) {
     float dd, ss, tt, st;
-    row_stats(s + (int64_t)b * S * h, t + (int64_t)b * S * h, h, lane, dd, ss, tt, st);
+    row_stats(s + (int64_t)b * S * h, t + teacher_sample(sample_index, b) * S * h, h, lane, dd, ss, tt, st);
     ss = wave_sum(ss); tt = wave_sum(tt); st = wave_sum(st);
     acc += cos_dist(ss, tt, st);
   }
@@ -150,9 +159,10 @@ __global__ __launch_bounds__(256) void distill_cls_fwd_kernel(const float* __res
   if (threadIdx.x == 0) out1[0] = ((sm[0] + sm[1]) + (sm[2] + sm[3])) / (float)B;
 }
 
-__global__ __launch_bounds__(256) void distill_cls_bwd_kernel(const float* __restrict__ s, const float* __restrict__ t, int B, int S,
-                                                              int h, const float* __restrict__ coef, float* __restrict__ ds,
-                                                              int accumulate) {
+template <typename TT>
+__global__ __launch_bounds__(256) void distill_cls_bwd_kernel(const float* __restrict__ s, const TT* __restrict__ t,
+                                                              const int* __restrict__ sample_index, int B, int S, int h,
+                                                              const float* __restrict__ coef, float* __restrict__ ds, int accumulate) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t row = (int64_t)blockIdx.x * 4 + wave;  // over all B*S rows so that non-CLS rows get zeros when !accumulate
   if (row >= (int64_t)B * S) return;
@@ -163,7 +173,7 @@ __global__ __launch_bounds__(256) void distill_cls_bwd_kernel(const float* __res
     return;
   }
   const float* sr = s + row * h;
-  const float* tr = t + row * h;
+  const TT* tr = t + teacher_sample(sample_index, row / S) * S * h;
   float dd, ss, tt, st;
   row_stats(sr, tr, h, lane, dd, ss, tt, st);
   ss = wave_sum(ss); tt = wave_sum(tt); st = wave_sum(st);
@@ -227,10 +237,18 @@ using namespace mafed;
 
 extern "C" size_t mafed_distill_workspace_bytes(int64_t rows) { return (size_t)ds_blocks(rows) * 4 * sizeof(float); }
 
-extern "C" int mafed_distill_fwd(const float* s, const float* t, const int64_t* attention_mask, int B, int S, int P, int h, int cosine,
-                                 float* out4, void* workspace, size_t workspace_bytes, void* stream) {
-  MAFED_CHECK_ARG(s && t && attention_mask && out4, "distill_fwd: null pointer");
+// bf16 teacher rows are read as one 8-byte word per lane and piece
+static bool teacher_ok(const void* t, mafed_dtype teacher_dtype, int h) {
+  if (teacher_dtype == MAFED_F32) return true;
+  return teacher_dtype == MAFED_BF16 && h % 4 == 0 && ((uintptr_t)t & 7) == 0;
+}
+
+extern "C" int mafed_distill_fwd_indexed(const float* s, const void* teacher, mafed_dtype teacher_dtype, const int* sample_index,
+                                         const int64_t* attention_mask, int B, int S, int P, int h, int cosine, float* out4, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+  MAFED_CHECK_ARG(s && teacher && attention_mask && out4, "distill_fwd: null pointer");
   MAFED_CHECK_ARG(B > 0 && S > 0 && P >= 0 && P <= S && h > 0 && h % 4 == 0, "distill_fwd: bad shape (h must be a multiple of 4)");
+  MAFED_CHECK_ARG(teacher_ok(teacher, teacher_dtype, h), "distill_fwd: a bf16 teacher needs h %% 4 == 0 and an 8-byte aligned base");
   const int64_t rows = (int64_t)B * S;
   const int nblk = ds_blocks(rows);
   if (!workspace || workspace_bytes < (size_t)nblk * 4 * sizeof(float)) {
@@ -238,13 +256,23 @@ extern "C" int mafed_distill_fwd(const float* s, const float* t, const int64_t* 
     return MAFED_EWORKSPACE;
   }
   hipStream_t st = as_stream(stream);
-  const double dbytes = 2.0 * rows * h * 4.0;  // student + teacher hidden state of one layer
-  if (cosine) launch(K_DISTILL_FWD, dbytes, distill_fwd_kernel<true>, dim3(nblk), dim3(256), 0, st, s, t, attention_mask, rows, S, P, S - P, h, (float*)workspace);
-  else launch(K_DISTILL_FWD, dbytes, distill_fwd_kernel<false>, dim3(nblk), dim3(256), 0, st, s, t, attention_mask, rows, S, P, S - P, h, (float*)workspace);
+  const bool tb = teacher_dtype == MAFED_BF16;
+  const double dbytes = (double)rows * h * (4.0 + (tb ? 2.0 : 4.0));  // student + teacher hidden state of one layer
+#define LAUNCH(COS, TT)                                                                                                          \
+  launch(K_DISTILL_FWD, dbytes, distill_fwd_kernel<COS, TT>, dim3(nblk), dim3(256), 0, st, s, (const TT*)teacher, sample_index, \
+         attention_mask, rows, S, P, S - P, h, (float*)workspace)
+  if (cosine) { if (tb) LAUNCH(true, bf16_t); else LAUNCH(true, float); }
+  else { if (tb) LAUNCH(false, bf16_t); else LAUNCH(false, float); }
+#undef LAUNCH
   MAFED_CHECK_LAUNCH("distill_fwd");
   launch(K_SMALL, 0.0, distill_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, nblk, out4);
   MAFED_CHECK_LAUNCH("distill_fwd(finish)");
   return MAFED_OK;
+}
+
+extern "C" int mafed_distill_fwd(const float* s, const float* t, const int64_t* attention_mask, int B, int S, int P, int h, int cosine,
+                                 float* out4, void* workspace, size_t workspace_bytes, void* stream) {
+  return mafed_distill_fwd_indexed(s, t, MAFED_F32, nullptr, attention_mask, B, S, P, h, cosine, out4, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mafed_distill_combine(const float* sums, int n_layers, const float* layer_coeff_dev, int modality_mode, float lang_weight,
@@ -260,32 +288,63 @@ extern "C" int mafed_distill_combine(const float* sums, int n_layers, const floa
   return MAFED_OK;
 }
 
-extern "C" int mafed_distill_bwd(const float* s, const float* t, const int64_t* attention_mask, int B, int S, int P, int h, int cosine,
-                                 const float* coef_dev, float* ds, int accumulate, void* stream) {
-  MAFED_CHECK_ARG(s && t && attention_mask && coef_dev && ds, "distill_bwd: null pointer");
+extern "C" int mafed_distill_bwd_indexed(const float* s, const void* teacher, mafed_dtype teacher_dtype, const int* sample_index,
+                                         const int64_t* attention_mask, int B, int S, int P, int h, int cosine, const float* coef_dev,
+                                         float* ds, int accumulate, void* stream) {
+  MAFED_CHECK_ARG(s && teacher && attention_mask && coef_dev && ds, "distill_bwd: null pointer");
   MAFED_CHECK_ARG(B > 0 && S > 0 && P >= 0 && P <= S && h > 0 && h % 4 == 0, "distill_bwd: bad shape (h must be a multiple of 4)");
+  MAFED_CHECK_ARG(teacher_ok(teacher, teacher_dtype, h), "distill_bwd: a bf16 teacher needs h %% 4 == 0 and an 8-byte aligned base");
   const int64_t rows = (int64_t)B * S;
   hipStream_t st = as_stream(stream);
   dim3 grid((unsigned)cdiv(rows, 4)), block(256);
-  const double dbytes = (accumulate ? 4.0 : 3.0) * rows * h * 4.0;
-  if (cosine) launch(K_DISTILL_BWD, dbytes, distill_bwd_kernel<true>, grid, block, 0, st, s, t, attention_mask, rows, S, P, S - P, h, coef_dev, ds, accumulate);
-  else launch(K_DISTILL_BWD, dbytes, distill_bwd_kernel<false>, grid, block, 0, st, s, t, attention_mask, rows, S, P, S - P, h, coef_dev, ds, accumulate);
+  const bool tb = teacher_dtype == MAFED_BF16;
+  const double dbytes = (double)rows * h * ((accumulate ? 3.0 : 2.0) * 4.0 + (tb ? 2.0 : 4.0));
+#define LAUNCH(COS, TT)                                                                                                                 \
+  launch(K_DISTILL_BWD, dbytes, distill_bwd_kernel<COS, TT>, grid, block, 0, st, s, (const TT*)teacher, sample_index, attention_mask, rows, S, \
+         P, S - P, h, coef_dev, ds, accumulate)
+  if (cosine) { if (tb) LAUNCH(true, bf16_t); else LAUNCH(true, float); }
+  else { if (tb) LAUNCH(false, bf16_t); else LAUNCH(false, float); }
+#undef LAUNCH
   MAFED_CHECK_LAUNCH("distill_bwd");
   return MAFED_OK;
 }
 
-extern "C" int mafed_distill_cls_fwd(const float* s, const float* t, int B, int S, int h, float* out1, void* stream) {
-  MAFED_CHECK_ARG(s && t && out1 && B > 0 && S > 0 && h > 0 && h % 4 == 0, "distill_cls_fwd: bad arguments");
-  distill_cls_fwd_kernel<<<dim3(1), dim3(256), 0, as_stream(stream)>>>(s, t, B, S, h, out1);
+extern "C" int mafed_distill_bwd(const float* s, const float* t, const int64_t* attention_mask, int B, int S, int P, int h, int cosine,
+                                 const float* coef_dev, float* ds, int accumulate, void* stream) {
+  return mafed_distill_bwd_indexed(s, t, MAFED_F32, nullptr, attention_mask, B, S, P, h, cosine, coef_dev, ds, accumulate, stream);
+}
+
+extern "C" int mafed_distill_cls_fwd_indexed(const float* s, const void* teacher, mafed_dtype teacher_dtype, const int* sample_index, int B,
+                                             int S, int h, float* out1, void* stream) {
+  MAFED_CHECK_ARG(s && teacher && out1 && B > 0 && S > 0 && h > 0 && h % 4 == 0, "distill_cls_fwd: bad arguments");
+  MAFED_CHECK_ARG(teacher_ok(teacher, teacher_dtype, h), "distill_cls_fwd: a bf16 teacher needs h %% 4 == 0 and an 8-byte aligned base");
+  if (teacher_dtype == MAFED_BF16)
+    distill_cls_fwd_kernel<bf16_t><<<dim3(1), dim3(256), 0, as_stream(stream)>>>(s, (const bf16_t*)teacher, sample_index, B, S, h, out1);
+  else
+    distill_cls_fwd_kernel<float><<<dim3(1), dim3(256), 0, as_stream(stream)>>>(s, (const float*)teacher, sample_index, B, S, h, out1);
   MAFED_CHECK_LAUNCH("distill_cls_fwd");
+  return MAFED_OK;
+}
+
+extern "C" int mafed_distill_cls_fwd(const float* s, const float* t, int B, int S, int h, float* out1, void* stream) {
+  return mafed_distill_cls_fwd_indexed(s, t, MAFED_F32, nullptr, B, S, h, out1, stream);
+}
+
+extern "C" int mafed_distill_cls_bwd_indexed(const float* s, const void* teacher, mafed_dtype teacher_dtype, const int* sample_index, int B,
+                                             int S, int h, const float* coef_dev, float* ds, int accumulate, void* stream) {
+  MAFED_CHECK_ARG(s && teacher && coef_dev && ds && B > 0 && S > 0 && h > 0 && h % 4 == 0, "distill_cls_bwd: bad arguments");
+  MAFED_CHECK_ARG(teacher_ok(teacher, teacher_dtype, h), "distill_cls_bwd: a bf16 teacher needs h %% 4 == 0 and an 8-byte aligned base");
+  const int64_t rows = (int64_t)B * S;
+  dim3 grid((unsigned)cdiv(rows, 4)), block(256);
+  if (teacher_dtype == MAFED_BF16)
+    distill_cls_bwd_kernel<bf16_t><<<grid, block, 0, as_stream(stream)>>>(s, (const bf16_t*)teacher, sample_index, B, S, h, coef_dev, ds, accumulate);
+  else
+    distill_cls_bwd_kernel<float><<<grid, block, 0, as_stream(stream)>>>(s, (const float*)teacher, sample_index, B, S, h, coef_dev, ds, accumulate);
+  MAFED_CHECK_LAUNCH("distill_cls_bwd");
   return MAFED_OK;
 }
 
 extern "C" int mafed_distill_cls_bwd(const float* s, const float* t, int B, int S, int h, const float* coef_dev, float* ds,
                                      int accumulate, void* stream) {
-  MAFED_CHECK_ARG(s && t && coef_dev && ds && B > 0 && S > 0 && h > 0 && h % 4 == 0, "distill_cls_bwd: bad arguments");
-  const int64_t rows = (int64_t)B * S;
-  distill_cls_bwd_kernel<<<dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, as_stream(stream)>>>(s, t, B, S, h, coef_dev, ds, accumulate);
-  MAFED_CHECK_LAUNCH("distill_cls_bwd");
-  return MAFED_OK;
+  return mafed_distill_cls_bwd_indexed(s, t, MAFED_F32, nullptr, B, S, h, coef_dev, ds, accumulate, stream);
 }

@@ -72,13 +72,16 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
 // ln_param_reduce_kernel then sums the slabs deterministically and accumulates into dw/db.
 // DXSUM: additionally accumulate the column sums of dx (= the bias gradients of the two Linear layers that produced the
 // residual branches of the layer below: both are sum_rows(dY) with dY = this dx), saving two column-sum passes per layer.
-template <int NV, typename DyT, bool DUAL, bool DXSUM>
+// TeT = element type of the teacher rows of the distillation injection (fp32, or bf16 widened at the load); sample_index as in
+// teacher_sample() (common.h).
+template <int NV, typename DyT, bool DUAL, bool DXSUM, typename TeT>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const DyT* __restrict__ dy1, const DyT* __restrict__ dy2,
                                                             const float* __restrict__ x, const float* __restrict__ mean,
                                                             const float* __restrict__ rstd, const float* __restrict__ w1,
                                                             const float* __restrict__ w2, int64_t rows, int h,
                                                             const float* __restrict__ dres, float* __restrict__ dx,
-                                                            DyT* __restrict__ dx_lp, const float* __restrict__ teacher,
+                                                            DyT* __restrict__ dx_lp, const TeT* __restrict__ teacher,
+                                                            const int* __restrict__ sample_index,
                                                             const int64_t* __restrict__ attention_mask, int S, int P, int T,
                                                             const float* __restrict__ inj_scale, float inj_mul,
                                                             float* __restrict__ partial) {
@@ -110,7 +113,10 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const DyT* __restric
     // the first phase's loads, so that their latency hides behind the reductions instead of following them
     float4 rres[NV], rte[NV];
     float inj = 0.f;
+    int64_t trow = row;
     if (teacher) {
+      const int64_t bi = row / S;
+      trow = teacher_sample(sample_index, bi) * S + (row - bi * S);
       const int cls = modality_class(row, S, P, T, attention_mask);
       inj = cls == 0 ? ls : (cls == 1 ? vs : 0.f);
     }
@@ -118,7 +124,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const DyT* __restric
     for (int i = 0; i < NV; ++i) {
       const int c = (lane + 64 * i) * 4;
       rres[i] = (dres && c < h) ? load4(dres + row * h + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-      rte[i] = (teacher && c < h) ? load4(teacher + row * h + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+      rte[i] = (teacher && c < h) ? load4(teacher + trow * h + c) : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     float sg = 0.f, sgx = 0.f;
 #pragma unroll
@@ -329,9 +335,19 @@ extern "C" size_t mafed_layernorm_bwd_workspace_bytes(int64_t rows, int h) {
 static int layernorm_bwd_impl(int phase, const void* dy1, const void* dy2, mafed_dtype dy_dtype, const float* x, const float* mean,
                               const float* rstd, const float* w1, const float* w2, int64_t rows, int h,
                               const float* dres, float* dx, void* dx_lp, float* dw1, float* db1, float* dw2, float* db2,
-                              const float* teacher, const int64_t* attention_mask, int S, int P, int T,
-                              const float* inj_scale_dev, float inj_mul, float* dxsum_a, float* dxsum_b, void* workspace,
-                              size_t workspace_bytes, void* stream);
+                              const void* teacher, mafed_dtype teacher_dtype, const int* sample_index, const int64_t* attention_mask,
+                              int S, int P, int T, const float* inj_scale_dev, float inj_mul, float* dxsum_a, float* dxsum_b,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
+extern "C" int mafed_layernorm_bwd_indexed(const void* dy1, const void* dy2, mafed_dtype dy_dtype, const float* x, const float* mean,
+                                           const float* rstd, const float* w1, const float* w2, int64_t rows, int h, const float* dres, float* dx,
+                                           void* dx_lp, float* dw1, float* db1, float* dw2, float* db2, const void* teacher,
+                                           mafed_dtype teacher_dtype, const int* sample_index, const int64_t* attention_mask, int S, int P, int T,
+                                           const float* inj_scale_dev, float inj_mul, float* dxsum_a, float* dxsum_b, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+  return layernorm_bwd_impl(0, dy1, dy2, dy_dtype, x, mean, rstd, w1, w2, rows, h, dres, dx, dx_lp, dw1, db1, dw2, db2, teacher, teacher_dtype,
+                            sample_index, attention_mask, S, P, T, inj_scale_dev, inj_mul, dxsum_a, dxsum_b, workspace, workspace_bytes, stream);
+}
 
 extern "C" int mafed_layernorm_bwd(const void* dy1, const void* dy2, mafed_dtype dy_dtype, const float* x, const float* mean,
                                    const float* rstd, const float* w1, const float* w2, int64_t rows, int h,
@@ -339,8 +355,19 @@ extern "C" int mafed_layernorm_bwd(const void* dy1, const void* dy2, mafed_dtype
                                    const float* teacher, const int64_t* attention_mask, int S, int P, int T,
                                    const float* inj_scale_dev, float inj_mul, float* dxsum_a, float* dxsum_b, void* workspace,
                                    size_t workspace_bytes, void* stream) {
-  return layernorm_bwd_impl(0, dy1, dy2, dy_dtype, x, mean, rstd, w1, w2, rows, h, dres, dx, dx_lp, dw1, db1, dw2, db2, teacher, attention_mask, S, P,
-                            T, inj_scale_dev, inj_mul, dxsum_a, dxsum_b, workspace, workspace_bytes, stream);
+  return mafed_layernorm_bwd_indexed(dy1, dy2, dy_dtype, x, mean, rstd, w1, w2, rows, h, dres, dx, dx_lp, dw1, db1, dw2, db2, teacher, MAFED_F32,
+                                     nullptr, attention_mask, S, P, T, inj_scale_dev, inj_mul, dxsum_a, dxsum_b, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mafed_layernorm_bwd_rows_indexed(const void* dy1, const void* dy2, mafed_dtype dy_dtype, const float* x, const float* mean,
+                                                const float* rstd, const float* w1, const float* w2, int64_t rows, int h, const float* dres,
+                                                float* dx, void* dx_lp, const void* teacher, mafed_dtype teacher_dtype, const int* sample_index,
+                                                const int64_t* attention_mask, int S, int P, int T, const float* inj_scale_dev, float inj_mul,
+                                                int want_dxsum, void* workspace, size_t workspace_bytes, void* stream) {
+  float dummy = 0.f;   // the row kernel never dereferences the parameter-gradient pointers: non-null stands for "wanted"
+  return layernorm_bwd_impl(1, dy1, dy2, dy_dtype, x, mean, rstd, w1, w2, rows, h, dres, dx, dx_lp, &dummy, &dummy, dy2 ? &dummy : nullptr,
+                            dy2 ? &dummy : nullptr, teacher, teacher_dtype, sample_index, attention_mask, S, P, T, inj_scale_dev, inj_mul,
+                            want_dxsum ? &dummy : nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mafed_layernorm_bwd_rows(const void* dy1, const void* dy2, mafed_dtype dy_dtype, const float* x, const float* mean,
@@ -348,32 +375,34 @@ extern "C" int mafed_layernorm_bwd_rows(const void* dy1, const void* dy2, mafed_
                                         void* dx_lp, const float* teacher, const int64_t* attention_mask, int S, int P, int T,
                                         const float* inj_scale_dev, float inj_mul, int want_dxsum, void* workspace, size_t workspace_bytes,
                                         void* stream) {
-  float dummy = 0.f;   // the row kernel never dereferences the parameter-gradient pointers: non-null stands for "wanted"
-  return layernorm_bwd_impl(1, dy1, dy2, dy_dtype, x, mean, rstd, w1, w2, rows, h, dres, dx, dx_lp, &dummy, &dummy, dy2 ? &dummy : nullptr,
-                            dy2 ? &dummy : nullptr, teacher, attention_mask, S, P, T, inj_scale_dev, inj_mul, want_dxsum ? &dummy : nullptr, nullptr,
-                            workspace, workspace_bytes, stream);
+  return mafed_layernorm_bwd_rows_indexed(dy1, dy2, dy_dtype, x, mean, rstd, w1, w2, rows, h, dres, dx, dx_lp, teacher, MAFED_F32, nullptr,
+                                          attention_mask, S, P, T, inj_scale_dev, inj_mul, want_dxsum, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mafed_layernorm_bwd_params(int64_t rows, int h, float* dw1, float* db1, float* dw2, float* db2, float* dxsum_a, float* dxsum_b,
                                           const void* workspace, size_t workspace_bytes, void* stream) {
   float dummy = 0.f;   // operands of the row kernel: only tested for presence in this phase
   return layernorm_bwd_impl(2, &dummy, dw2 ? &dummy : nullptr, MAFED_F32, &dummy, &dummy, &dummy, &dummy, dw2 ? &dummy : nullptr, rows, h, nullptr, &dummy,
-                            nullptr, dw1, db1, dw2, db2, nullptr, nullptr, 0, 0, 0, nullptr, 0.f, dxsum_a, dxsum_b, const_cast<void*>(workspace),
+                            nullptr, dw1, db1, dw2, db2, nullptr, MAFED_F32, nullptr, nullptr, 0, 0, 0, nullptr, 0.f, dxsum_a, dxsum_b, const_cast<void*>(workspace),
                             workspace_bytes, stream);
 }
 
 static int layernorm_bwd_impl(int phase, const void* dy1, const void* dy2, mafed_dtype dy_dtype, const float* x, const float* mean,
                               const float* rstd, const float* w1, const float* w2, int64_t rows, int h,
                               const float* dres, float* dx, void* dx_lp, float* dw1, float* db1, float* dw2, float* db2,
-                              const float* teacher, const int64_t* attention_mask, int S, int P, int T,
-                              const float* inj_scale_dev, float inj_mul, float* dxsum_a, float* dxsum_b, void* workspace,
-                              size_t workspace_bytes, void* stream) {
+                              const void* teacher, mafed_dtype teacher_dtype, const int* sample_index, const int64_t* attention_mask,
+                              int S, int P, int T, const float* inj_scale_dev, float inj_mul, float* dxsum_a, float* dxsum_b,
+                              void* workspace, size_t workspace_bytes, void* stream) {
   MAFED_CHECK_ARG(dy1 && x && mean && rstd && w1 && dx && dw1 && db1, "layernorm_bwd: null pointer");
   MAFED_CHECK_ARG(h > 0 && h % 4 == 0, "layernorm_bwd: h=%d must be a positive multiple of 4", h);
   const bool dual = dy2 != nullptr;
   MAFED_CHECK_ARG(!dual || (w2 && dw2 && db2), "layernorm_bwd: dual LN needs w2, dw2, db2");
   MAFED_CHECK_ARG(!teacher || (attention_mask && inj_scale_dev && S > 0 && P >= 0 && T == S - P && rows % S == 0),
                   "layernorm_bwd: distillation injection needs attention_mask, inj_scale, S=P+T, rows %% S == 0");
+  MAFED_CHECK_ARG(!sample_index || teacher, "layernorm_bwd: a sample index needs the teacher rows it indexes");
+  const bool tbf = teacher && teacher_dtype == MAFED_BF16;
+  MAFED_CHECK_ARG(!teacher || teacher_dtype == MAFED_F32 || (tbf && ((uintptr_t)teacher & 7) == 0),
+                  "layernorm_bwd: a bf16 teacher needs h %% 4 == 0 and an 8-byte aligned base");
   const int nv = ln_nv(h);
   MAFED_CHECK_ARG(nv > 0, "layernorm_bwd: h=%d > 2048 unsupported", h);
   if (rows == 0) return MAFED_OK;
@@ -389,25 +418,28 @@ static int layernorm_bwd_impl(int phase, const void* dy1, const void* dy2, mafed
   hipStream_t st = as_stream(stream);
   float* partial = (float*)workspace;
   dim3 grid(nblk), block(256);
-#define LAUNCH(NV, T, DUAL, DXS)                                                                                         \
+#define LAUNCH(NV, T, DUAL, DXS, TE)                                                                                     \
   do {                                                                                                                   \
-    auto kfn = layernorm_bwd_kernel<NV, T, DUAL, DXS>;                                                                        \
+    auto kfn = layernorm_bwd_kernel<NV, T, DUAL, DXS, TE>;                                                                    \
     if (lds_bytes > 64 * 1024) (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); \
     launch(K_LN_BWD, ln_bwd_bytes, kfn, grid, block, lds_bytes, st, (const T*)dy1, (const T*)dy2, x, mean, rstd, w1, w2, rows, h, dres, dx, (T*)dx_lp, \
-           teacher, attention_mask, S, P, T_, inj_scale_dev, inj_mul, partial);                                               \
+           (const TE*)teacher, sample_index, attention_mask, S, P, T_, inj_scale_dev, inj_mul, partial);                      \
   } while (0)
   const int T_ = T;
   // algorithmic bytes: dy1 (+ dy2) and x in, the residual gradient and the teacher rows where present, dx (+ its low-precision copy) out
   const double esz = dy_dtype == MAFED_F32 ? 4.0 : 2.0;
-  const double ln_bwd_bytes = (double)rows * h * ((dual ? 2.0 : 1.0) * esz + 4.0 + (dres ? 4.0 : 0.0) + (teacher ? 4.0 : 0.0) + 4.0 + (dx_lp ? esz : 0.0));
-#define DISPATCH_D(NV, TT)                       \
-  if (dual && dxsum) LAUNCH(NV, TT, true, true);  \
-  else if (dual) LAUNCH(NV, TT, true, false);     \
-  else if (dxsum) LAUNCH(NV, TT, false, true);    \
-  else LAUNCH(NV, TT, false, false)
+  const double ln_bwd_bytes = (double)rows * h * ((dual ? 2.0 : 1.0) * esz + 4.0 + (dres ? 4.0 : 0.0) + (teacher ? (tbf ? 2.0 : 4.0) : 0.0) + 4.0 + (dx_lp ? esz : 0.0));
+#define DISPATCH_D(NV, TT, TE)                        \
+  if (dual && dxsum) LAUNCH(NV, TT, true, true, TE);   \
+  else if (dual) LAUNCH(NV, TT, true, false, TE);      \
+  else if (dxsum) LAUNCH(NV, TT, false, true, TE);     \
+  else LAUNCH(NV, TT, false, false, TE)
+#define DISPATCH_E(NV, TT)                      \
+  if (tbf) { DISPATCH_D(NV, TT, bf16_t); }      \
+  else { DISPATCH_D(NV, TT, float); }
 #define DISPATCH_T(NV)                          \
-  if (dy_dtype == MAFED_F32) { DISPATCH_D(NV, float); } \
-  else { DISPATCH_D(NV, bf16_t); }
+  if (dy_dtype == MAFED_F32) { DISPATCH_E(NV, float); } \
+  else { DISPATCH_E(NV, bf16_t); }
   if (phase != 2) {
     switch (nv) {
       case 1: DISPATCH_T(1); break;
@@ -419,6 +451,7 @@ static int layernorm_bwd_impl(int phase, const void* dy1, const void* dy2, mafed
     MAFED_CHECK_LAUNCH("layernorm_bwd");
   }
 #undef DISPATCH_T
+#undef DISPATCH_E
 #undef DISPATCH_D
 #undef LAUNCH
   if (phase == 1) return MAFED_OK;

@@ -118,14 +118,25 @@ class _FusedDistillLossFn(torch.autograd.Function):
 class _DistillClsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, s, t):
-        ctx.save_for_backward(s, t)
+        ctx.save_for_backward(s)
+        ctx.teacher = t    # a detached tensor or ops.TeacherRows (rows of the teacher cache, read in place)
         return ops.distill_cls_fwd(s, t).reshape(())
 
     @staticmethod
     def backward(ctx, g):
-        s, t = ctx.saved_tensors
+        s, = ctx.saved_tensors
         coef = (g.reshape(1) / s.shape[0]).contiguous()
-        return ops.distill_cls_bwd(s, t, coef), None
+        return ops.distill_cls_bwd(s, ctx.teacher, coef), None
+
+
+def _cache_dtype(dtype) -> torch.dtype:
+    """``teacher_cache_dtype``: torch.float32 / "fp32" or torch.bfloat16 / "bf16"."""
+    named = {"fp32": torch.float32, "bf16": torch.bfloat16}
+    if isinstance(dtype, str) and dtype in named:
+        return named[dtype]
+    if dtype in (torch.float32, torch.bfloat16):
+        return dtype
+    raise ValueError(f"teacher_cache_dtype must be torch.float32 / 'fp32' or torch.bfloat16 / 'bf16', not {dtype!r}")
 
 
 class FeatureDistillation(CLStrategy):
@@ -171,6 +182,10 @@ class FeatureDistillation(CLStrategy):
         # keep the frozen teacher's distilled hidden states for the whole replay memory resident in HBM (build_teacher_cache; filled by
         # update() once per task).  Off by default: the reference runs the teacher forward in every replay step.
         self.teacher_cache = bool(kwargs.get("teacher_cache", False))
+        # storage type of that cache.  fp32 (default) keeps the step bit-identical to the per-step teacher forward.  bf16 halves the
+        # memory and the traffic but CHANGES THE TARGET: every teacher element is rounded to 8 significant bits (relative error <= 2^-9)
+        # and the student is pulled towards the rounded teacher.
+        self.teacher_cache_dtype = _cache_dtype(kwargs.get("teacher_cache_dtype", torch.float32))
         self._tcache = None
         self._mem_index = None
         self._prefetched = None
@@ -290,7 +305,7 @@ class FeatureDistillation(CLStrategy):
         layers = list(self.loss_weights.get_distillation_layers())
         if not layers or max(layers) + 1 > n:
             return False
-        dev = hs[0].device
+        dev = batch["attention_mask"].device if batch["attention_mask"].is_cuda else self.past_model.flat_params.device
         am = batch["attention_mask"].to(dev, torch.int64).contiguous()
         P = self.num_vision_tokens
         B, T = am.shape
@@ -338,7 +353,7 @@ class FeatureDistillation(CLStrategy):
                 v.record_stream(side)
         kw = {"patch_embeddings": batch["patch_embeddings"]} if "patch_embeddings" in batch else {"pixel_values": batch["pixel_values"]}
         with torch.cuda.stream(side):
-            hs = self._cached_teacher_states(max(layers) + 1)       # teacher cache: a gather instead of the forward
+            hs = self._teacher_rows(max(layers) + 1, consumer=main)   # teacher cache: its rows, read in place, instead of the forward
             if hs is None:
                 hs = [x.detach() for x in pm.hidden_states_upto(batch["input_ids"], batch["attention_mask"], n_hidden=max(layers) + 1, **kw)]
             ev = side.record_event()
@@ -356,7 +371,7 @@ class FeatureDistillation(CLStrategy):
                 return hs
         pm = self.past_model
         with torch.no_grad():
-            cached = self._cached_teacher_states(n_hidden)
+            cached = self._teacher_rows(n_hidden)
             if cached is not None:
                 return cached
             if hasattr(pm, "hidden_states_upto"):
@@ -366,14 +381,18 @@ class FeatureDistillation(CLStrategy):
             return [x.detach() for x in hs]
 
     # ---- teacher cache (MI355X-only design point: 288 GB of HBM) ------------------------------------------------------------
-    def build_teacher_cache(self, mem=None, batch_size: Optional[int] = None) -> Dict[str, float]:
+    def build_teacher_cache(self, mem=None, batch_size: Optional[int] = None, dtype=None) -> Dict[str, float]:
         """The frozen teacher sees the same stored samples for a whole task: run it ONCE over (this rank's shard of) the replay
-        memory and keep the distilled hidden states resident -- fp32 [n_layers, n, S, h], 27 MB per sample at 410M = 108 GB for the
-        reference's 4000-sample memory, sharded 1/N under data parallelism.  A replay step then gathers its batch's rows
-        (``memory_index`` from the buffer) instead of running the teacher forward: 5.2 of the step's 22.5 TFLOP.  The cache is
-        written by the same kernels on the same batch shapes as the per-step forward (the tail re-runs the last full batch), so the
-        cached step is bit-identical to the uncached one.  Dropped whenever the teacher changes (``_update_model``)."""
+        memory and keep the distilled hidden states resident -- [n_layers, n, S, h]; in fp32 27 MB per sample at 410M = 108 GB for the
+        reference's 4000-sample memory, sharded 1/N under data parallelism.  A replay step then skips the teacher forward (5.2 of the
+        step's 22.5 TFLOP): its distillation kernels read the batch's rows where they are stored, through the buffer's
+        ``memory_index`` (``ops.TeacherRows``) -- no gathered copy.  The cache is written by the same kernels on the same batch shapes
+        as the per-step forward (the tail re-runs the last full batch), so the fp32-cached step is bit-identical to the uncached one.
+        ``dtype`` (default: ``self.teacher_cache_dtype``) torch.bfloat16 / "bf16" stores the states rounded to nearest even, half the
+        size; the step then distils towards the ROUNDED teacher (relative rounding <= 2^-9 per element), not a bit-identical one.
+        Dropped whenever the teacher changes (``_update_model``)."""
         import time
+        dtype = _cache_dtype(dtype if dtype is not None else getattr(self, "teacher_cache_dtype", torch.float32))
         mem = mem if mem is not None else self.mem_dataloader
         pm = self.past_model
         if pm is None or not hasattr(pm, "hidden_states_upto") or not hasattr(mem, "data") or len(mem) == 0:
@@ -392,11 +411,8 @@ class FeatureDistillation(CLStrategy):
         n = hi - lo
         if n <= 0:
             raise RuntimeError(f"teacher cache: this rank's shard of the replay memory is empty ({len(mem)} samples over the ranks)")
-        if len(layers) * n * S >= 2 ** 31:
-            raise RuntimeError(f"teacher cache: {len(layers)} layers x {n} samples x {S} tokens = {len(layers) * n * S} rows exceed the 32-bit "
-                               "row ids of the gather kernel (shard the memory over more ranks or distil fewer layers)")
         t0 = time.time()
-        states = torch.empty((len(layers), n, S, h), dtype=torch.float32, device=dev)
+        states = torch.empty((len(layers), n, S, h), dtype=dtype, device=dev)
         with torch.no_grad():
             for i in range(lo, hi, B):
                 j = min(i, max(lo, hi - B))            # the tail re-runs the last FULL batch: same kernel shapes as in the step
@@ -404,14 +420,17 @@ class FeatureDistillation(CLStrategy):
                 hs = pm.hidden_states_upto(data["input_ids"][j:e], data["attention_mask"][j:e], patch_embeddings=data["patch_embeddings"][j:e],
                                            n_hidden=n_hidden)
                 for k, l in enumerate(layers):
-                    states[k, j - lo: e - lo] = hs[l].view(e - j, S, h)
+                    if dtype == torch.float32:
+                        states[k, j - lo: e - lo] = hs[l].view(e - j, S, h)
+                    else:
+                        ops.cast(hs[l].contiguous().view(e - j, S, h), dtype, out=states[k, j - lo: e - lo])   # round to nearest even
         torch.cuda.synchronize(dev)
         mem.attach_index = True
         mem._next = None      # (a batch gathered ahead carries no index)
-        self._tcache = {"states": states, "layers": layers, "lo": lo, "n": n, "S": S, "h": h, "mem": mem, "mem_len": len(mem),
+        self._tcache = {"states": states, "layers": layers, "lo": lo, "n": n, "S": S, "h": h, "mem": mem, "mem_len": len(mem), "streams": set(),
                         "layer_off": (torch.arange(len(layers), device=dev, dtype=torch.int64) * (n * S)).view(-1, 1, 1),
                         "ar": torch.arange(S, device=dev, dtype=torch.int64).view(1, 1, S)}
-        return {"GB": states.numel() * 4 / 1e9, "samples": n, "seconds": time.time() - t0}
+        return {"GB": states.numel() * states.element_size() / 1e9, "samples": n, "seconds": time.time() - t0}
 
     def drop_teacher_cache(self) -> None:
         tc = getattr(self, "_tcache", None)
@@ -420,17 +439,60 @@ class FeatureDistillation(CLStrategy):
             tc["mem"]._next = None
         self._tcache = None
 
-    def _cached_teacher_states(self, n_hidden: Optional[int]):
-        """hidden_states[l] of the cached teacher for the batch handed out last, or None when the cache does not cover it."""
+    def _cache_for_batch(self):
+        """(cache, memory index of the batch handed out last, distilled layers), or None when the cache does not cover that batch."""
         tc, idx = getattr(self, "_tcache", None), getattr(self, "_mem_index", None)
         if tc is None or idx is None or tc["mem"] is not self.mem_dataloader or len(tc["mem"]) != tc["mem_len"]:
             return None
         layers = list(self.loss_weights.get_distillation_layers())
         if layers != tc["layers"]:
             return None
+        return tc, idx, layers
+
+    def _teacher_rows(self, n_hidden: Optional[int], consumer=None):
+        """hidden_states[l] of the cached teacher for the batch handed out last as ``ops.TeacherRows`` -- the layer's slab of the cache
+        and the batch's sample index within it, which the distillation kernels read in place -- or None when the cache does not cover
+        it.  The index is computed here, once per step, on the current stream; ``consumer`` is another stream whose kernels will read
+        the rows (the caller's stream when this runs on the teacher's side stream)."""
+        got = self._cache_for_batch()
+        if got is None:
+            return None
+        tc, idx, layers = got
+        states = tc["states"]
+        idx = idx.to(states.device)
+        index = (idx - tc["lo"]).to(torch.int32)
+        if states.is_cuda:
+            cur = torch.cuda.current_stream(states.device)
+            idx.record_stream(cur)             # (gathered on the loader's stream)
+            for st in (cur, consumer):
+                # the cache lives on the stream that built it: every other stream that reads it is recorded once, so that a dropped
+                # cache (new teacher) is not handed out again while such a reader is still queued
+                if st is not None and st not in tc["streams"]:
+                    tc["streams"].add(st)
+                    states.record_stream(st)
+            if consumer is not None:
+                index.record_stream(consumer)
+        hs = [None] * (max(layers) + 1)
+        for k, l in enumerate(layers):
+            hs[l] = ops.TeacherRows(states[k], index)
+        return hs
+
+    def _cached_teacher_states(self, n_hidden: Optional[int]):
+        """hidden_states[l] of the cached teacher for the batch handed out last as dense fp32 tensors (gathered; bf16 rows upcast), or
+        None when the cache does not cover it.  The accessor for anything that is not one of the distillation kernels: the step itself
+        reads the rows in place (``_teacher_rows``)."""
+        got = self._cache_for_batch()
+        if got is None:
+            return None
+        tc, idx, layers = got
         B, S, h = idx.numel(), tc["S"], tc["h"]
+        if len(layers) * tc["n"] * S >= 2 ** 31:
+            raise RuntimeError(f"teacher cache: {len(layers)} layers x {tc['n']} samples x {S} tokens = {len(layers) * tc['n'] * S} rows exceed "
+                               "the 32-bit row ids of the gather kernel")
         rows = (tc["layer_off"] + ((idx.to(tc["ar"].device) - tc["lo"]) * S).view(1, B, 1) + tc["ar"]).to(torch.int32).view(-1)
         out = ops.gather_rows(tc["states"].view(-1, h), rows)          # ONE launch for every distilled layer
+        if out.dtype != torch.float32:
+            out = ops.cast(out, torch.float32)
         hs = [None] * (max(layers) + 1)
         for k, l in enumerate(layers):
             hs[l] = out[k * B * S: (k + 1) * B * S].view(B, S, h)
@@ -458,7 +520,8 @@ class FeatureDistillation(CLStrategy):
             if not self._cosine:
                 # upstream passes three tensors to MSELoss here and raises
                 raise TypeError("cls_distillation requires distillation_loss='cosine'")
-            per_layer = torch.stack([_DistillClsFn.apply(output.hidden_states[l].contiguous(), past[l].contiguous()) for l in layers])
+            per_layer = torch.stack([_DistillClsFn.apply(output.hidden_states[l].contiguous(),
+                                                         past[l] if isinstance(past[l], ops.TeacherRows) else past[l].contiguous()) for l in layers])
             self.last_modality_losses = None
         else:
             B, T = am.shape

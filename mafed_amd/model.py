@@ -905,7 +905,7 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
             wgrad_layer(dqkv, s["ln1"], i, 0)
             dln1 = ops.gemm(dqkv, w.qkv_w, False, False)
             # both LayerNorms + the residual path, one pass; also emits the compute-dtype copy the next layer's GEMMs read
-            ln_kw = dict(want_lp=(cd != torch.float32), teacher=inj[0].view(rows, h) if inj is not None else None,
+            ln_kw = dict(want_lp=(cd != torch.float32), teacher=(inj[0].view(rows, h) if torch.is_tensor(inj[0]) else inj[0]) if inj is not None else None,
                          attention_mask=am if inj is not None else None, S=S, P=P, inj_scale=inj[1] if inj is not None else None,
                          inj_mul=-1.0 if inj_cos else 2.0 / h)   # (a negative factor selects the cosine-distance gradient, mafed_hip.h)
             dxa = grads.layers[i - 1].fc2_b if i > 0 else None   # colsum(dx) is the layer below's two residual-branch bias gradients

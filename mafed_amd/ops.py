@@ -198,6 +198,60 @@ def layernorm_fwd(x: torch.Tensor, w1, b1, w2=None, b2=None, eps: float = 1e-5, 
     return y1, y2, mean, rstd
 
 
+class TeacherRows:
+    """The frozen teacher's hidden state of ONE layer for the samples of a batch, not materialised: ``states`` is that layer's slab of a
+    resident teacher cache, [n, S, h] fp32 or bf16, and ``index`` [B] int32 names the batch's samples within it (None: the states ARE
+    the batch, [B, S, h] -- a dense teacher that is not fp32).  The distillation
+    kernels (``distill_fwd / bwd``, ``distill_cls_fwd / bwd``, the injection of ``layernorm_bwd`` / ``layernorm_bwd_rows``) take it
+    wherever they take a dense fp32 [B, S, h] teacher tensor and read row ``index[b] * S + s`` in place, widening bf16 at the load.
+    Anything else calls ``materialize()``."""
+    __slots__ = ("states", "index")
+
+    def __init__(self, states: torch.Tensor, index: Optional[torch.Tensor] = None):
+        if states.dim() != 3 or states.dtype not in (torch.float32, torch.bfloat16) or not states.is_contiguous():
+            raise ValueError("TeacherRows: states must be a contiguous [n, S, h] fp32 / bf16 tensor")
+        if index is not None and (index.dim() != 1 or index.dtype != torch.int32 or not index.is_contiguous() or index.device != states.device):
+            raise ValueError("TeacherRows: index must be a contiguous int32 [B] tensor on the device of the states")
+        self.states, self.index = states, index
+
+    @property
+    def shape(self):
+        return (self.states.shape[0] if self.index is None else self.index.numel(), self.states.shape[1], self.states.shape[2])
+
+    @property
+    def dtype(self):
+        return self.states.dtype
+
+    def record_stream(self, stream) -> None:
+        self.states.record_stream(stream)
+        if self.index is not None:
+            self.index.record_stream(stream)
+
+    def materialize(self) -> torch.Tensor:
+        """The dense fp32 [B, S, h] tensor these rows stand for (``gather_rows`` + an exact upcast of bf16 rows)."""
+        n, S, h = self.states.shape
+        if self.index is None:
+            return self.states if self.states.dtype == torch.float32 else cast(self.states, torch.float32)
+        if n * S >= 2 ** 31:
+            raise RuntimeError(f"TeacherRows.materialize: {n} samples x {S} tokens exceed the 32-bit row ids of the gather kernel")
+        B = self.index.numel()
+        rows = (self.index.view(B, 1) * S + torch.arange(S, device=self.index.device, dtype=torch.int32).view(1, S)).view(-1)
+        out = gather_rows(self.states.view(n * S, h), rows)
+        return (out if out.dtype == torch.float32 else cast(out, torch.float32)).view(B, S, h)
+
+
+def _teacher(t, B: Optional[int] = None, S: Optional[int] = None, h: Optional[int] = None):
+    """(pointer, mafed_dtype, index pointer) of a teacher argument: a dense fp32 tensor (no index), ``TeacherRows``, or None."""
+    if t is None:
+        return 0, F32, 0
+    if isinstance(t, TeacherRows):
+        if (B is not None and t.shape[0] != B) or (S is not None and t.shape[1] != S) or (h is not None and t.shape[2] != h):
+            raise ValueError(f"TeacherRows of shape {t.shape} for a batch of [{B}, {S}, {h}]")
+        return _ptr(t.states), _dt(t.states), _ptr(t.index)
+    assert t.dtype == torch.float32 and t.is_contiguous()
+    return _ptr(t), F32, 0
+
+
 def layernorm_bwd(dy1, dy2, x, mean, rstd, w1, w2, dres, dw1, db1, dw2=None, db2=None, want_lp: bool = False,
                   teacher=None, attention_mask=None, S: int = 0, P: int = 0, inj_scale=None, inj_mul: float = 1.0,
                   dxsum_a=None, dxsum_b=None):
@@ -207,10 +261,11 @@ def layernorm_bwd(dy1, dy2, x, mean, rstd, w1, w2, dres, dw1, db1, dw2=None, db2
     lib = _lib.load()
     nb = lib.mafed_layernorm_bwd_workspace_bytes(rows, h)
     ws = workspace(x.device).get(nb)
-    check(lib.mafed_layernorm_bwd(_ptr(dy1), _ptr(dy2), _dt(dy1), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(w1), _ptr(w2), rows, h,
-                                  _ptr(dres), _ptr(dx), _ptr(dx_lp), _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2), _ptr(teacher),
-                                  _ptr(attention_mask), S, P, S - P, _ptr(inj_scale), float(inj_mul), _ptr(dxsum_a), _ptr(dxsum_b), _ptr(ws), ws.numel(),
-                                  _stream()),
+    tp, tdt, tix = _teacher(teacher, rows // S if S else None, S or None, h)
+    check(lib.mafed_layernorm_bwd_indexed(_ptr(dy1), _ptr(dy2), _dt(dy1), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(w1), _ptr(w2), rows, h,
+                                          _ptr(dres), _ptr(dx), _ptr(dx_lp), _ptr(dw1), _ptr(db1), _ptr(dw2), _ptr(db2), tp, tdt, tix,
+                                          _ptr(attention_mask), S, P, S - P, _ptr(inj_scale), float(inj_mul), _ptr(dxsum_a), _ptr(dxsum_b), _ptr(ws),
+                                          ws.numel(), _stream()),
           "mafed_layernorm_bwd")
     return dx, dx_lp
 
@@ -224,9 +279,10 @@ def layernorm_bwd_rows(dy1, dy2, x, mean, rstd, w1, w2, dres, want_lp: bool = Fa
     dx_lp = torch.empty((rows, h), dtype=dy1.dtype, device=x.device) if want_lp else None
     lib = _lib.load()
     ws = torch.empty(lib.mafed_layernorm_bwd_workspace_bytes(rows, h), dtype=torch.uint8, device=x.device)
-    check(lib.mafed_layernorm_bwd_rows(_ptr(dy1), _ptr(dy2), _dt(dy1), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(w1), _ptr(w2), rows, h, _ptr(dres),
-                                       _ptr(dx), _ptr(dx_lp), _ptr(teacher), _ptr(attention_mask), S, P, S - P, _ptr(inj_scale), float(inj_mul),
-                                       1 if want_dxsum else 0, _ptr(ws), ws.numel(), _stream()), "mafed_layernorm_bwd_rows")
+    tp, tdt, tix = _teacher(teacher, rows // S if S else None, S or None, h)
+    check(lib.mafed_layernorm_bwd_rows_indexed(_ptr(dy1), _ptr(dy2), _dt(dy1), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(w1), _ptr(w2), rows, h,
+                                               _ptr(dres), _ptr(dx), _ptr(dx_lp), tp, tdt, tix, _ptr(attention_mask), S, P, S - P, _ptr(inj_scale),
+                                               float(inj_mul), 1 if want_dxsum else 0, _ptr(ws), ws.numel(), _stream()), "mafed_layernorm_bwd_rows")
     return dx, dx_lp, ws
 
 
@@ -473,18 +529,19 @@ def ce_bwd(logits: torch.Tensor, labels: torch.Tensor, lse: torch.Tensor, gloss:
     return out
 
 
-def distill_fwd(s: torch.Tensor, t: torch.Tensor, attention_mask: torch.Tensor, P: int, cosine: bool = False,
+def distill_fwd(s: torch.Tensor, t, attention_mask: torch.Tensor, P: int, cosine: bool = False,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """-> out[4] = {lang_sum, vision_sum, n_lang, n_vision}"""
+    """-> out[4] = {lang_sum, vision_sum, n_lang, n_vision}; ``t`` a dense fp32 [B, S, h] tensor or ``TeacherRows``"""
     B, S, h = s.shape
-    assert s.dtype == torch.float32 and t.dtype == torch.float32 and s.is_contiguous() and t.is_contiguous()
+    assert s.dtype == torch.float32 and s.is_contiguous()
+    tp, tdt, tix = _teacher(t, B, S, h)
     lib = _lib.load()
     if out is None:
         out = torch.empty(4, dtype=torch.float32, device=s.device)
     nb = lib.mafed_distill_workspace_bytes(B * S)
     ws = workspace(s.device).get(nb)
-    check(lib.mafed_distill_fwd(_ptr(s), _ptr(t), _ptr(attention_mask), B, S, P, h, int(cosine), _ptr(out), _ptr(ws), ws.numel(),
-                                _stream()), "mafed_distill_fwd")
+    check(lib.mafed_distill_fwd_indexed(_ptr(s), tp, tdt, tix, _ptr(attention_mask), B, S, P, h, int(cosine), _ptr(out), _ptr(ws), ws.numel(),
+                                        _stream()), "mafed_distill_fwd")
     return out
 
 
@@ -494,8 +551,9 @@ def distill_bwd(s, t, attention_mask, P: int, coef: torch.Tensor, cosine: bool =
     if out is None:
         out = torch.empty_like(s)
         accumulate = False
-    check(_lib.load().mafed_distill_bwd(_ptr(s), _ptr(t), _ptr(attention_mask), B, S, P, h, int(cosine), _ptr(coef), _ptr(out),
-                                        int(accumulate), _stream()), "mafed_distill_bwd")
+    tp, tdt, tix = _teacher(t, B, S, h)
+    check(_lib.load().mafed_distill_bwd_indexed(_ptr(s), tp, tdt, tix, _ptr(attention_mask), B, S, P, h, int(cosine), _ptr(coef), _ptr(out),
+                                                int(accumulate), _stream()), "mafed_distill_bwd")
     return out
 
 
@@ -517,14 +575,16 @@ def distill_combine(sums: torch.Tensor, layer_coeff: torch.Tensor, mode: int, la
 def distill_cls_fwd(s, t) -> torch.Tensor:
     B, S, h = s.shape
     out = torch.empty(1, dtype=torch.float32, device=s.device)
-    check(_lib.load().mafed_distill_cls_fwd(_ptr(s), _ptr(t), B, S, h, _ptr(out), _stream()), "mafed_distill_cls_fwd")
+    tp, tdt, tix = _teacher(t, B, S, h)
+    check(_lib.load().mafed_distill_cls_fwd_indexed(_ptr(s), tp, tdt, tix, B, S, h, _ptr(out), _stream()), "mafed_distill_cls_fwd")
     return out
 
 
 def distill_cls_bwd(s, t, coef) -> torch.Tensor:
     B, S, h = s.shape
     out = torch.empty_like(s)
-    check(_lib.load().mafed_distill_cls_bwd(_ptr(s), _ptr(t), B, S, h, _ptr(coef), _ptr(out), 0, _stream()), "mafed_distill_cls_bwd")
+    tp, tdt, tix = _teacher(t, B, S, h)
+    check(_lib.load().mafed_distill_cls_bwd_indexed(_ptr(s), tp, tdt, tix, B, S, h, _ptr(coef), _ptr(out), 0, _stream()), "mafed_distill_cls_bwd")
     return out
 
 
