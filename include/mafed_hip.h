@@ -481,6 +481,11 @@ int mafed_pad_text_rows(const float* src, int B, int S, int P, int h, float* dst
 int mafed_label_rows(const int64_t* labels, int B, int T, int Rc, int* row_of_slot, int* slot_of_row, int64_t* labels_c, int* overflow,
                      void* stream);
 int mafed_gather_rows(const void* src, mafed_dtype dtype, const int* idx, int64_t n_out, int h, void* dst, void* stream);
+/* Right padding of a text batch in one launch: ids / mask / labels [B,T] int64 -> [B,Tp] (Tp >= T) with id 0, mask 0 and label -100 at
+ * positions T .. Tp-1.  labels / labels_out may both be NULL.  The engine's ``text_bucket`` policy uses it to make B * (P + Tp) a multiple
+ * of the GEMM tile: positions appended BEHIND the text are invisible to every real query and carry no loss term. */
+int mafed_pad_text_batch(const int64_t* ids, const int64_t* mask, const int64_t* labels, int B, int T, int Tp, int64_t* ids_out,
+                         int64_t* mask_out, int64_t* labels_out, void* stream);
 /* y = gelu_erf(x) elementwise (used by tests; the product path fuses GELU into mafed_gemm) */
 int mafed_gelu(const void* x, void* y, mafed_dtype dtype, int64_t n, void* stream);
 
@@ -527,6 +532,9 @@ int mafed_gemm_get_variant(int which);
  * (0: 144x256 tiles, 1: 128x256 tiles, 2: 256x256 tiles) wherever the shape tiles it.  mafed_gemm_pp_launches(): launches that took that kernel so far
  * (tests assert that a forced configuration really ran). */
 int mafed_gemm_pp_launches(void);
+/* bf16 launches that reached the register-staged MFMA kernel so far: the kernel of last resort, taken when a shape tiles neither the
+ * persistent nor the LDS-DMA kernels (K % 64 != 0, or M a multiple of neither 128 nor 144).  Read-only. */
+int mafed_gemm_fallback_launches(void);
 
 /* test / tuning hook: 0 = automatic (one-block-per-head "resident" kernels when K/V fit in LDS), 1 = tiled kernels only */
 int mafed_attn_set_variant(int variant);

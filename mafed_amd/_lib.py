@@ -29,6 +29,7 @@ SIGNATURES = {
     "mafed_gemm_set_variant": (_i, [_i]),
     "mafed_gemm_get_variant": (_i, [_i]),
     "mafed_gemm_pp_launches": (_i, []),
+    "mafed_gemm_fallback_launches": (_i, []),
     "mafed_attn_decode": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
     "mafed_attn_decode_prerot": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
     "mafed_rotate_k_rows": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
@@ -102,6 +103,7 @@ SIGNATURES = {
     "mafed_pad_text_rows": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
     "mafed_label_rows": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _p]),
     "mafed_gather_rows": (_i, [_p, _i, _p, _l, _i, _p, _p]),
+    "mafed_pad_text_batch": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
     "mafed_gelu": (_i, [_p, _p, _i, _l, _p]),
     "mafed_patchify": (_i, [_p, _i, _i, _i, _i, _i, _i, _l, _i, _p, _i, _p]),
     "mafed_vit_assemble": (_i, [_p, _i, _l, _p, _p, _i, _i, _i, _p, _p]),

@@ -192,6 +192,24 @@ __global__ void label_rows_kernel(const int64_t* __restrict__ labels, int B, int
   }
 }
 
+// Right padding of a text batch: ids / mask / labels [B, T] -> [B, Tp] with id 0, mask 0 and label -100 behind the last text position, all
+// three tensors in one launch (labels optional).  Appended positions are invisible to every real query (causal mask), carry no loss term and
+// leave the rotary positions of the real tokens alone: the engine uses it to bring B * (P + T) up to a multiple of the GEMM tile.
+__global__ __launch_bounds__(256) void pad_text_batch_kernel(const int64_t* __restrict__ ids, const int64_t* __restrict__ mask,
+                                                             const int64_t* __restrict__ labels, int T, int Tp, int64_t n,
+                                                             int64_t* __restrict__ ids_out, int64_t* __restrict__ mask_out,
+                                                             int64_t* __restrict__ labels_out) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int64_t b = i / Tp;
+    const int t = (int)(i - b * Tp);
+    const bool real = t < T;
+    const int64_t j = b * T + t;
+    ids_out[i] = real ? ids[j] : 0;
+    mask_out[i] = real ? mask[j] : 0;
+    if (labels_out) labels_out[i] = real ? labels[j] : -100;
+  }
+}
+
 // dst[r, :] = idx[r] >= 0 ? src[idx[r], :] : 0   (16-byte pieces; h % 8 == 0 for bf16, % 4 for fp32)
 template <typename TT>
 __global__ __launch_bounds__(256) void gather_rows_kernel(const TT* __restrict__ src, const int* __restrict__ idx, int64_t n_out, int hv,
@@ -237,6 +255,16 @@ extern "C" int mafed_pad_text_rows(const float* src, int B, int S, int P, int h,
   launch(K_CAST, (double)B * h * ((S - P) * 4.0 + S * (4.0 + (dst_lp ? 2.0 : 0.0))), pad_text_rows_kernel, dim3(grid_for(n4)), dim3(256), 0, as_stream(stream), src, S, P,
          h / 4, n4, dst, (bf16_t*)dst_lp);
   MAFED_CHECK_LAUNCH("pad_text_rows");
+  return MAFED_OK;
+}
+
+extern "C" int mafed_pad_text_batch(const int64_t* ids, const int64_t* mask, const int64_t* labels, int B, int T, int Tp, int64_t* ids_out,
+                                    int64_t* mask_out, int64_t* labels_out, void* stream) {
+  MAFED_CHECK_ARG(ids && mask && ids_out && mask_out && B > 0 && T > 0 && Tp >= T, "pad_text_batch: bad arguments");
+  MAFED_CHECK_ARG((labels != nullptr) == (labels_out != nullptr), "pad_text_batch: labels and labels_out go together");
+  const int64_t n = (int64_t)B * Tp;
+  pad_text_batch_kernel<<<dim3(grid_for(n)), dim3(256), 0, as_stream(stream)>>>(ids, mask, labels, T, Tp, n, ids_out, mask_out, labels_out);
+  MAFED_CHECK_LAUNCH("pad_text_batch");
   return MAFED_OK;
 }
 

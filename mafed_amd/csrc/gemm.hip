@@ -613,6 +613,8 @@ static int launch_bf16_glds_cfg(int cfg, int64_t M, int64_t N, int64_t K, const 
   return launch_bf16_glds<2, 2, 4, 4, A_KS, B_KS, CT>(M, N, K, A, lda, B, ldb, C, epi, st);
 }
 
+static int g_gemm_fallback_launches = 0;   // launches of the register-staged kernel below (mafed_gemm_fallback_launches)
+
 template <bool A_KS, bool B_KS, typename CT>
 static int launch_bf16(int64_t M, int64_t N, int64_t K, const void* A, int64_t lda, const void* B, int64_t ldb, void* C,
                        const GemmEpi& epi, hipStream_t st) {
@@ -627,6 +629,7 @@ static int launch_bf16(int64_t M, int64_t N, int64_t K, const void* A, int64_t l
   }
   launch(K_GEMM_BF16, 2.0 * M * N * K, kfn, dim3((unsigned)nwg), dim3(256), GEMM_LDS_BYTES, st, M, N, K, (const bf16_t*)A, lda, (const bf16_t*)B, ldb,
          (CT*)C, epi, (int)tn, (int)nwg);
+  ++g_gemm_fallback_launches;
   return MAFED_OK;
 }
 
@@ -644,6 +647,7 @@ static int g_gemm_pp_force = -1;
 static int g_gemm_pp_launches = 0;   // test hook: how many launches took the ping-pong kernel
 static int g_gemm_pp_fc2 = 0;        // tuning (730 off / 731 on): the fp32 + two-residual epilogue (4h -> h product) on the persistent kernel too
 extern "C" int mafed_gemm_pp_launches(void) { return g_gemm_pp_launches; }
+extern "C" int mafed_gemm_fallback_launches(void) { return mafed::g_gemm_fallback_launches; }
 namespace mafed { extern int g_skinny_ns, g_skinny_wide, g_attn_decode_flat, g_decode_lds; }
 extern "C" int mafed_gemm_get_variant(int which) {   // which: 0 = tile-configuration variant, 7 = persistent-kernel mode (700 / 701 / 710 + c)
   if (which == 7) return g_gemm_pp_force >= 0 ? 710 + g_gemm_pp_force : (g_gemm_pp ? 701 : 700);

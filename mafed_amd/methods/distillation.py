@@ -266,12 +266,15 @@ class FeatureDistillation(CLStrategy):
             # the features were just written on THIS stream: the loader's event says nothing about them, the teacher's stream has
             # to wait for everything queued here (an event recorded after the tower), not for the loader
             ready = None
+        # ``run``: the batch at the text length the engine runs it at (the model's text_bucket; ``batch`` itself when nothing is appended).
+        # Student, teacher and the distillation kernels all see ``run``; the caller's dict keeps its shapes.
+        run, ready = self._engine_batch(model, batch, ready)
         if self.distillation_coeff != 0:
             # frozen-teacher forward on a second HIP stream, concurrent with the student's
-            self._prefetch_teacher(batch, ready)
-        hooked = self._install_early_sums(model, batch)
+            self._prefetch_teacher(run, ready)
+        hooked = self._install_early_sums(model, run)
         try:
-            output = model(**batch, compute_loss=do_replay, output_hidden_states=True, return_dict=True)
+            output = model(**run, compute_loss=do_replay, output_hidden_states=True, return_dict=True)
         finally:
             if hooked:
                 model.hidden_ready_hook = None
@@ -280,9 +283,41 @@ class FeatureDistillation(CLStrategy):
         loss = (output.loss if self.replay_coeff == 1.0 else self.replay_coeff * output.loss) if do_replay else None
         if self.distillation_coeff == 0:
             return loss, n_ex
-        dloss = self.distill(output=output, batch=batch)
+        dloss = self.distill(output=output, batch=batch, run=run)
         loss = dloss if loss is None else loss + dloss
         return loss, n_ex
+
+    def _engine_batch(self, model, batch, ready=None):
+        """(the batch right-padded to the model's bucketed text length, the event its tensors are ready at).  One launch for ids, mask and
+        labels; with a loader that hands out an event it runs on the teacher's stream, so that the teacher forward still starts behind the
+        loader alone and not behind the caller's stream (_prefetch_teacher)."""
+        if not hasattr(model, "padded_text_len"):
+            return batch, ready
+        B, T = batch["input_ids"].shape
+        if model.padded_text_len(B, T) == T:
+            return batch, ready
+        pm = self.past_model
+        parts = (batch["input_ids"], batch["attention_mask"], batch.get("labels"))
+        if (ready is not None and self.distillation_coeff != 0 and self.overlap_teacher and hasattr(pm, "side_stream") and pm.flat_params.is_cuda):
+            main, side = torch.cuda.current_stream(), pm.side_stream()
+            side.wait_event(ready)
+            with torch.cuda.stream(side):
+                padded = model.pad_text_batch(*parts)
+                ready = side.record_event()
+            for src, dst in zip(parts, padded):
+                if src is not None and src.is_cuda:
+                    src.record_stream(side)
+                if dst is not None:
+                    dst.record_stream(main)
+            main.wait_event(ready)
+        else:
+            padded = model.pad_text_batch(*parts)
+            ready = None   # written on this stream: the teacher's stream waits for it, not for the loader
+        run = dict(batch)
+        run["input_ids"], run["attention_mask"] = padded[0], padded[1]
+        if padded[2] is not None:
+            run["labels"] = padded[2]
+        return run, ready
 
     def _cached(self, key, make):
         """Constant device tensors of the step (mask pieces, the coefficient vector), built once per shape instead of per step."""
@@ -353,15 +388,19 @@ class FeatureDistillation(CLStrategy):
                 v.record_stream(side)
         kw = {"patch_embeddings": batch["patch_embeddings"]} if "patch_embeddings" in batch else {"pixel_values": batch["pixel_values"]}
         with torch.cuda.stream(side):
-            hs = self._teacher_rows(max(layers) + 1, consumer=main)   # teacher cache: its rows, read in place, instead of the forward
+            # teacher cache: its rows, read in place, instead of the forward
+            hs = self._teacher_rows(max(layers) + 1, consumer=main, S=self.num_vision_tokens + batch["input_ids"].shape[1])
             if hs is None:
                 hs = [x.detach() for x in pm.hidden_states_upto(batch["input_ids"], batch["attention_mask"], n_hidden=max(layers) + 1, **kw)]
             ev = side.record_event()
         self._prefetched = (hs, ev, max(layers) + 1)
 
-    def _get_past_hidden_states(self, batch, n_hidden: Optional[int] = None):
-        """Frozen-teacher hidden states; pops ``labels`` from the caller's dict like upstream (distillation.py:218-224)."""
+    def _get_past_hidden_states(self, batch, n_hidden: Optional[int] = None, run=None):
+        """Frozen-teacher hidden states; pops ``labels`` from the caller's dict like upstream (distillation.py:218-224).  ``run``: the batch
+        as the engine runs it (_engine_batch), when that is not ``batch``."""
         batch.pop("labels", None)
+        if run is not None and run is not batch:
+            batch = {k: v for k, v in run.items() if k != "labels"}
         pre = getattr(self, "_prefetched", None)
         if pre is not None:
             self._prefetched = None
@@ -371,7 +410,7 @@ class FeatureDistillation(CLStrategy):
                 return hs
         pm = self.past_model
         with torch.no_grad():
-            cached = self._teacher_rows(n_hidden)
+            cached = self._teacher_rows(n_hidden, S=self.num_vision_tokens + batch["input_ids"].shape[1])
             if cached is not None:
                 return cached
             if hasattr(pm, "hidden_states_upto"):
@@ -407,8 +446,11 @@ class FeatureDistillation(CLStrategy):
         data = mem.data
         dev = pm.flat_params.device
         T = data["input_ids"].shape[1]
-        S, h = self.num_vision_tokens + T, pm.config.hidden_size
         n = hi - lo
+        # rows are stored at the length the forward that fills them runs at: the teacher's text_bucket applied to the batches below (all of
+        # min(B, n) samples), i.e. what a replay step of the same batch size reads
+        Tp = pm.padded_text_len(min(B, n), T) if hasattr(pm, "padded_text_len") and n > 0 else T
+        S, h = self.num_vision_tokens + Tp, pm.config.hidden_size
         if n <= 0:
             raise RuntimeError(f"teacher cache: this rank's shard of the replay memory is empty ({len(mem)} samples over the ranks)")
         t0 = time.time()
@@ -417,8 +459,12 @@ class FeatureDistillation(CLStrategy):
             for i in range(lo, hi, B):
                 j = min(i, max(lo, hi - B))            # the tail re-runs the last FULL batch: same kernel shapes as in the step
                 e = min(j + B, hi)
-                hs = pm.hidden_states_upto(data["input_ids"][j:e], data["attention_mask"][j:e], patch_embeddings=data["patch_embeddings"][j:e],
-                                           n_hidden=n_hidden)
+                ids, am = data["input_ids"][j:e], data["attention_mask"][j:e]
+                if Tp != T:
+                    ids, am, _ = pm.pad_text_batch(ids, am)   # (fed at the padded length, the forward hands its states out untrimmed)
+                hs = pm.hidden_states_upto(ids, am, patch_embeddings=data["patch_embeddings"][j:e], n_hidden=n_hidden)
+                if hs[0].shape[1] != S:
+                    raise RuntimeError(f"teacher cache: the forward ran at {hs[0].shape[1]} positions, the cache was sized for {S}")
                 for k, l in enumerate(layers):
                     if dtype == torch.float32:
                         states[k, j - lo: e - lo] = hs[l].view(e - j, S, h)
@@ -427,7 +473,7 @@ class FeatureDistillation(CLStrategy):
         torch.cuda.synchronize(dev)
         mem.attach_index = True
         mem._next = None      # (a batch gathered ahead carries no index)
-        self._tcache = {"states": states, "layers": layers, "lo": lo, "n": n, "S": S, "h": h, "mem": mem, "mem_len": len(mem), "streams": set(),
+        self._tcache = {"states": states, "layers": layers, "lo": lo, "n": n, "S": S, "T": T, "h": h, "mem": mem, "mem_len": len(mem), "streams": set(),
                         "layer_off": (torch.arange(len(layers), device=dev, dtype=torch.int64) * (n * S)).view(-1, 1, 1),
                         "ar": torch.arange(S, device=dev, dtype=torch.int64).view(1, 1, S)}
         return {"GB": states.numel() * states.element_size() / 1e9, "samples": n, "seconds": time.time() - t0}
@@ -439,22 +485,28 @@ class FeatureDistillation(CLStrategy):
             tc["mem"]._next = None
         self._tcache = None
 
-    def _cache_for_batch(self):
-        """(cache, memory index of the batch handed out last, distilled layers), or None when the cache does not cover that batch."""
+    def _cache_for_batch(self, S: Optional[int] = None):
+        """(cache, memory index of the batch handed out last, distilled layers), or None when the cache does not cover that batch.
+        ``S``: the positions per sample the step runs at (padding included).  The cache holds rows of ONE length, the padded length of the
+        forward that filled it; a step at another length would read other samples' rows, so it raises."""
         tc, idx = getattr(self, "_tcache", None), getattr(self, "_mem_index", None)
         if tc is None or idx is None or tc["mem"] is not self.mem_dataloader or len(tc["mem"]) != tc["mem_len"]:
             return None
         layers = list(self.loss_weights.get_distillation_layers())
         if layers != tc["layers"]:
             return None
+        if S is not None and int(S) != tc["S"]:
+            raise RuntimeError(f"teacher cache: this batch runs at {int(S)} positions per sample, the cache holds rows of {tc['S']} "
+                               f"(filled from text length {tc.get('T', '?')}, batch size and text_bucket of build_teacher_cache); "
+                               "rebuild the cache for this shape or drop it (drop_teacher_cache)")
         return tc, idx, layers
 
-    def _teacher_rows(self, n_hidden: Optional[int], consumer=None):
+    def _teacher_rows(self, n_hidden: Optional[int], consumer=None, S: Optional[int] = None):
         """hidden_states[l] of the cached teacher for the batch handed out last as ``ops.TeacherRows`` -- the layer's slab of the cache
         and the batch's sample index within it, which the distillation kernels read in place -- or None when the cache does not cover
         it.  The index is computed here, once per step, on the current stream; ``consumer`` is another stream whose kernels will read
         the rows (the caller's stream when this runs on the teacher's side stream)."""
-        got = self._cache_for_batch()
+        got = self._cache_for_batch(S)
         if got is None:
             return None
         tc, idx, layers = got
@@ -508,19 +560,34 @@ class FeatureDistillation(CLStrategy):
             return None
         return dist.group.WORLD if en is True else en
 
-    def distill(self, output, batch):
+    def distill(self, output, batch, run=None):
+        """``run``: the batch as the engine ran it (replay: _engine_batch) when that is not ``batch`` -- ``output`` and the teacher states
+        are then at its text length; the masks left in ``batch`` keep the caller's."""
         layers = self.loss_weights.get_distillation_layers()
-        past = self._get_past_hidden_states(batch, n_hidden=max(layers) + 1)
+        run = batch if run is None else run
+        past = self._get_past_hidden_states(batch, n_hidden=max(layers) + 1, run=run)
         dev = output.hidden_states[0].device
+        hidden_states = output.hidden_states
+        S_in = self.num_vision_tokens + batch["attention_mask"].shape[1]
+        fused = (not self._cls_distillation) and self.fused_distill and getattr(output, "mafed_ctx", None) is not None
+        if run is not batch and not fused:
+            # the per-sample kernels of the generic paths (CLS token, autograd sums) take dense [B, S, h] blocks and the caller's mask:
+            # trim the student's states (under autograd: the gradient comes back with zeros behind the text) and the teacher's
+            hidden_states = [x[:, :S_in].contiguous() for x in hidden_states]
+            if any(isinstance(t, ops.TeacherRows) for t in past):
+                past = self._cached_teacher_states(max(layers) + 1)
+            past = [t[:, :S_in].contiguous() if t is not None else None for t in past]
+            run = batch
         base = self.loss_weights.layer_coeff_vector(dev)
         coeffs = self._cached(("coeffs", id(base), float(self.distillation_coeff)), lambda: (base * float(self.distillation_coeff)).contiguous())
         P = self.num_vision_tokens
         am = batch["attention_mask"].to(dev, torch.int64).contiguous()
+        am_run = am if run is batch else run["attention_mask"].to(dev, torch.int64).contiguous()
         if self._cls_distillation:
             if not self._cosine:
                 # upstream passes three tensors to MSELoss here and raises (SURVEY.md quirk 11)
                 raise TypeError("cls_distillation requires distillation_loss='cosine'")
-            per_layer = torch.stack([_DistillClsFn.apply(output.hidden_states[l].contiguous(),
+            per_layer = torch.stack([_DistillClsFn.apply(hidden_states[l].contiguous(),
                                                          past[l] if isinstance(past[l], ops.TeacherRows) else past[l].contiguous()) for l in layers])
             self.last_modality_losses = None
         else:
@@ -530,7 +597,7 @@ class FeatureDistillation(CLStrategy):
             batch["lang_masks"] = torch.cat([zeros_p, am], dim=1)
             batch["image_masks"] = self._cached(("im", B, P, T, str(dev)), lambda: torch.cat(
                 [torch.ones((B, P), dtype=am.dtype, device=dev), torch.zeros((B, T), dtype=am.dtype, device=dev)], dim=1))
-            students = [output.hidden_states[l] for l in layers]
+            students = [hidden_states[l] for l in layers]
             teachers = [past[l] for l in layers]
             mctx = getattr(output, "mafed_ctx", None)
             if self.fused_distill and mctx is not None:
@@ -540,13 +607,13 @@ class FeatureDistillation(CLStrategy):
                     early = None
                 mode, lang_w, lang_vec = self.loss_weights.modality_mode(layers, dev)
                 loss, per_layer, modality = _FusedDistillLossFn.apply(
-                    mctx[1], am, P, teachers, mctx[0], layers, (early["sums"], early["stream"].record_event()) if early is not None else None,
+                    mctx[1], am_run, P, teachers, mctx[0], layers, (early["sums"], early["stream"].record_event()) if early is not None else None,
                     coeffs, mode, lang_w, lang_vec, bool(self._cosine), self._exact_group(), *students)
                 self.last_modality_losses = modality
                 self.last_layer_losses = per_layer
                 self.step += 1
                 return loss
-            sums = _DistillSumsFn.apply(am, P, self._cosine, teachers, *students)  # [nl, 4]
+            sums = _DistillSumsFn.apply(am_run, P, self._cosine, teachers, *students)  # [nl, 4]
             if self._exact_group() is not None:
                 counts = global_token_counts(sums.detach(), self._exact_group())[:, 2:4]
                 sums = torch.cat([sums[:, 0:2], counts], dim=1)

@@ -181,6 +181,33 @@ class BufferViews:
             raise KeyError("the parameter records do not cover every tensor of the flat layout")
 
 
+TEXT_BUCKET_ROWS = 128      # rows = B * (P + T) that every tiled kernel of the step takes: a multiple of this
+TEXT_BUCKET_MAX_PAD = 16    # "auto" appends at most this many positions per sample; a batch that needs more runs unpadded
+
+
+def bucket_text_len(text_bucket, B: int, P: int, T: int) -> int:
+    """Text length T' >= T that a batch of B samples (P image positions each) runs at under the ``text_bucket`` policy:
+    ``"auto"``: the smallest T' with B * (P + T') a multiple of TEXT_BUCKET_ROWS if T' - T <= TEXT_BUCKET_MAX_PAD, else T (an odd B, such
+    as a short last batch, would need up to 127 positions: left alone); an int m > 0: the smallest T' with (P + T') a multiple of m;
+    0: T.  The policy is idempotent: a batch already at T' stays there."""
+    if isinstance(text_bucket, str):
+        if text_bucket != "auto":
+            raise ValueError(f"text_bucket must be 'auto', 0 or a positive int, not {text_bucket!r}")
+        for Tp in range(T, T + TEXT_BUCKET_MAX_PAD + 1):
+            if (B * (P + Tp)) % TEXT_BUCKET_ROWS == 0:
+                return Tp
+        return T
+    m = int(text_bucket or 0)
+    if m < 0:
+        raise ValueError(f"text_bucket must be 'auto', 0 or a positive int, not {text_bucket!r}")
+    return T if m == 0 else T + (-(P + T)) % m
+
+
+def _trim(x: torch.Tensor, n: int) -> torch.Tensor:
+    """The first n positions of a [B, n', ...] tensor as a contiguous tensor (x itself when nothing was appended)."""
+    return x if x.shape[1] == n else x[:, :n].contiguous()
+
+
 @dataclass
 class SweepRecord:
     """What a backward sweep reports: left on the model as ``last_sweep`` when the sweep starts, completed as it goes."""
@@ -193,9 +220,14 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
     """MI355X-native counterpart of ``VLCLIPGPTNeoXForCausalLM`` for the training hot path."""
 
     def __init__(self, config: VLPythiaConfig, compute_dtype: torch.dtype = torch.bfloat16, device: Any = None,
-                 vision_encoder: Optional[nn.Module] = None, seed: Optional[int] = None):
+                 vision_encoder: Optional[nn.Module] = None, seed: Optional[int] = None, text_bucket: Any = None):
         super().__init__()
         assert compute_dtype in (torch.bfloat16, torch.float32)
+        # Right padding of the text to a length at which rows = B * (P + T) tile the fast GEMMs (bucket_text_len; DESIGN 4g): "auto" /
+        # int / 0 = off.  The engine appends masked positions behind the text and trims what callers see, so only the speed changes.
+        # Default: "auto" in bf16; 0 in fp32, whose exact kernels take any shape.
+        self.text_bucket = text_bucket if text_bucket is not None else ("auto" if compute_dtype == torch.bfloat16 else 0)
+        bucket_text_len(self.text_bucket, 1, 0, 1)   # (a bad value fails here, not in the first step)
         assert config.use_parallel_residual, "GPT-NeoX sequential residual is not on the MAFED path (config/vlpythia-base.json:30)"
         self.config = config
         self.compute_dtype = compute_dtype
@@ -347,7 +379,7 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
         """Teacher snapshot (mafed/methods/distillation.py:211-213): one flat device copy instead of a per-tensor walk."""
         # (the frozen tower is shared, not copied: upstream's deepcopy duplicates ~0.3 B frozen parameters per teacher)
         enc = self.vision_encoder if not isinstance(self.vision_encoder, _FrozenVision) else getattr(self.vision_encoder, "encoder", None)
-        new = VLPythiaForCausalLM(self.config, self.compute_dtype, self.flat_params.device, vision_encoder=enc)
+        new = VLPythiaForCausalLM(self.config, self.compute_dtype, self.flat_params.device, vision_encoder=enc, text_bucket=self.text_bucket)
         with torch.no_grad():
             new.flat_params.copy_(self.flat_params)
         new._shadow_dirty = True
@@ -500,17 +532,38 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
             hint = kwargs.get("max_label_rows") if (self.sparse_lm_head and labels is not None) else None
             outs = _ModelFn.apply(self._anchor, self, feats, input_ids, attention_mask, labels, want_h, ctx_box, hint)
             loss = outs[0] if labels is not None else None
-            logits, hs = (outs[1] if outs[1].numel() else None), tuple(outs[3:]) if want_h else None
+            # (the node's hidden states are the engine's own, at the padded length: trimmed here, under autograd, so that a gradient a
+            #  caller sends into one comes back with zeros at the appended positions)
+            S_in = ctx_box[0]["P"] + ctx_box[0]["T_in"]
+            logits, hs = (outs[1] if outs[1].numel() else None), tuple(_trim(x, S_in) for x in outs[3:]) if want_h else None
             mctx = (ctx_box[0], outs[2]) if want_h else None
         else:
             mctx = None
-            st = self._engine_forward(feats, input_ids, attention_mask, labels, want_h, train=False)
+            st = self._engine_forward(feats, input_ids, attention_mask, labels, want_h, train=False, pad_text=True)
             loss = st["loss"].reshape(()) if st["loss"] is not None else None
-            logits, hs = st["logits"], tuple(st["hidden"]) if want_h else None
+            logits, hs = _trim(st["logits"], st["T_in"]), tuple(_trim(x, st["P"] + st["T_in"]) for x in st["hidden"]) if want_h else None
         out = CausalLMOutput(loss=loss, logits=logits, hidden_states=hs, mafed_ctx=mctx)
         if return_dict is False:
             return tuple(v for v in (out.loss, out.logits, out.hidden_states) if v is not None)
         return out
+
+    def padded_text_len(self, B: int, T: int) -> int:
+        """The text length a [B, T] batch runs at under this model's ``text_bucket`` (bucket_text_len)."""
+        return bucket_text_len(self.text_bucket, int(B), self.config.num_vision_tokens, int(T))
+
+    def pad_text_batch(self, input_ids, attention_mask, labels=None):
+        """(ids, mask, labels) of a [B, T] batch on this model's device at ``padded_text_len(B, T)``: one launch, or the tensors themselves
+        when nothing is appended.  What every engine entry does with its batch; a caller that feeds the same batch to two models (student
+        and frozen teacher) pads once and passes the result to both -- a batch at the padded length is left alone."""
+        dev = self.flat_params.device
+        input_ids = input_ids.to(dev, torch.int64).contiguous()
+        attention_mask = attention_mask.to(dev, torch.int64).contiguous()
+        labels = labels.to(dev, torch.int64).contiguous() if labels is not None else None
+        B, T = input_ids.shape
+        Tp = self.padded_text_len(B, T)
+        if Tp == T:
+            return input_ids, attention_mask, labels
+        return ops.pad_text_batch(input_ids, attention_mask, labels, Tp)
 
     @torch.no_grad()
     def hidden_states_upto(self, input_ids, attention_mask, pixel_values=None, patch_embeddings=None, n_hidden: Optional[int] = None):
@@ -519,8 +572,8 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
         feats = patch_embeddings if patch_embeddings is not None else self.get_patch_embeddings(pixel_values)
         dev = self.flat_params.device
         st = self._engine_forward(feats.to(dev).contiguous(), input_ids.to(dev, torch.int64).contiguous(),
-                                  attention_mask.to(dev, torch.int64).contiguous(), None, True, train=False, n_hidden=n_hidden)
-        return tuple(st["hidden"])
+                                  attention_mask.to(dev, torch.int64).contiguous(), None, True, train=False, n_hidden=n_hidden, pad_text=True)
+        return tuple(_trim(x, st["P"] + st["T_in"]) for x in st["hidden"])
 
     @torch.no_grad()
     def modality_features(self, input_ids, attention_mask, pixel_values=None, patch_embeddings=None, out: Optional[torch.Tensor] = None,
@@ -545,7 +598,7 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
     # ---- engine ------------------------------------------------------------------------------------------------------
     def _engine_forward(self, feats, input_ids, attention_mask, labels, want_hidden, train, n_hidden: Optional[int] = None,
                         keep_qkv: bool = False, qkv_out: Optional[Sequence[torch.Tensor]] = None, label_rows_hint: Optional[int] = None,
-                        last_only: bool = False, skip_head: bool = False):
+                        last_only: bool = False, skip_head: bool = False, pad_text: bool = False):
         if not self.flat_params.is_cuda:
             raise RuntimeError("mafed_amd runs on the GPU only (no CPU fallback); move the model with .cuda()")
         pe, main_st = self._param_events, torch.cuda.current_stream()
@@ -554,15 +607,21 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
         if self._shadow_dirty:
             self.sync_shadow()
         cfg, cd = self.config, self.compute_dtype
-        B, T = input_ids.shape
+        B, T_in = input_ids.shape
         P, h, H, D, L = cfg.num_vision_tokens, cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim, cfg.num_hidden_layers
+        # ``pad_text`` (training, evaluation and teacher forwards; not the prefill, whose caches index real positions): masked positions
+        # behind the text bring the row count to a tile multiple (text_bucket).  Everything below, the activation record and the
+        # backward run at T; the public entry points trim what they hand out to ``T_in``.
+        T = bucket_text_len(self.text_bucket, B, P, T_in) if pad_text else T_in
+        if T != T_in:
+            input_ids, attention_mask, labels = ops.pad_text_batch(input_ids, attention_mask, labels, T)
         S = P + T
         rows = B * S
         rot = cfg.rotary_ndims
         cos, sin = self.rotary_tables(S)
         wts, pars = self._tensors(0), self._tensors(1)   # compute-dtype weights; fp32 LayerNorm parameters, biases and embedding
         Wo, Po = wts.outer, pars.outer
-        sv: Dict[str, Any] = {"B": B, "T": T, "P": P, "S": S, "input_ids": input_ids, "attention_mask": attention_mask, "labels": labels,
+        sv: Dict[str, Any] = {"B": B, "T": T, "T_in": T_in, "P": P, "S": S, "input_ids": input_ids, "attention_mask": attention_mask, "labels": labels,
                               "layers": []}
         # projector: Linear -> GELU(erf) -> Linear (vl_pythia.py:226-234,270)
         f2 = feats.reshape(B * P, cfg.vision_hidden_size)
@@ -676,11 +735,11 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
         dev = self.flat_params.device
         sv = self._engine_forward(feats.to(dev).contiguous(), batch["input_ids"].to(dev, torch.int64).contiguous(),
                                   batch["attention_mask"].to(dev, torch.int64).contiguous(),
-                                  batch["labels"].to(dev, torch.int64).contiguous(), False, train=True)
+                                  batch["labels"].to(dev, torch.int64).contiguous(), False, train=True, pad_text=True)
         taps: Dict[int, torch.Tensor] = {int(l): None for l in layers}
         self._engine_backward(sv, torch.ones(1, device=dev), [], taps=taps)
         S = sv["S"]
-        return {l: t.view(sv["B"], S, -1) for l, t in taps.items()}
+        return {l: _trim(t.view(sv["B"], S, -1), sv["P"] + sv["T_in"]) for l, t in taps.items()}
 
     def _dw_group_fuses_squares(self, rows: int) -> bool:
         """Will a grouped weight-gradient launch of this model (``dw_group_layers`` layers x four matrices, K = rows) emit the squares of
@@ -962,7 +1021,7 @@ class _ModelFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, anchor, model: VLPythiaForCausalLM, feats, input_ids, attention_mask, labels, want_hidden, ctx_box, label_rows_hint=None):
-        sv = model._engine_forward(feats, input_ids, attention_mask, labels, want_hidden, train=True, label_rows_hint=label_rows_hint)
+        sv = model._engine_forward(feats, input_ids, attention_mask, labels, want_hidden, train=True, label_rows_hint=label_rows_hint, pad_text=True)
         ctx.model, ctx.sv = model, sv
         ctx_box.append(sv)
         ctx.set_materialize_grads(False)  # outputs nobody differentiated arrive as None, not as zero tensors
@@ -971,7 +1030,7 @@ class _ModelFn(torch.autograd.Function):
         # outs[2] is a 0-dim "hook": the fused distillation node takes it as an input so that this node's backward runs
         # (after the distillation node has left its per-layer coefficients in sv["inject"]) even without a CE gradient; nobody reads
         # its value, so it is not filled
-        pub = sv["logits"] if sv.get("sparse_head") is None else torch.empty(0, device=anchor.device)   # compact logits are internal
+        pub = _trim(sv["logits"], sv["T_in"]) if sv.get("sparse_head") is None else torch.empty(0, device=anchor.device)   # compact logits are internal
         # (one cached zero per device: an uninitialised scalar may hold NaN / Inf, which trips anomaly detection and would propagate if
         #  autograd ever accumulated the hook's gradient with another path; re-using the tensor costs no fill kernel per step)
         outs = [loss, pub.detach(), model._hook_zero().view(())]

@@ -693,6 +693,21 @@ def label_rows(labels: torch.Tensor, Rc: int):
     return ros, sor, lc, ov
 
 
+def pad_text_batch(input_ids: torch.Tensor, attention_mask: torch.Tensor, labels: Optional[torch.Tensor], Tp: int):
+    """ids / mask / labels [B,T] int64 (contiguous) -> the same at [B,Tp]: id 0, mask 0, label -100 behind the text.  One launch."""
+    B, T = input_ids.shape
+    dev = input_ids.device
+    out = torch.empty((3 if labels is not None else 2, B, Tp), dtype=torch.int64, device=dev)
+    check(_lib.load().mafed_pad_text_batch(_ptr(input_ids), _ptr(attention_mask), _ptr(labels), B, T, int(Tp), _ptr(out[0]), _ptr(out[1]),
+                                           _ptr(out[2]) if labels is not None else 0, _stream()), "mafed_pad_text_batch")
+    return out[0], out[1], (out[2] if labels is not None else None)
+
+
+def gemm_fallback_launches() -> int:
+    """bf16 GEMM launches that reached the register-staged kernel so far (shapes that tile none of the fast kernels)."""
+    return int(_lib.load().mafed_gemm_fallback_launches())
+
+
 def gather_rows(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """dst[r] = src[idx[r]] (zeros where idx[r] < 0); src [n,h] contiguous fp32 / bf16, idx int32"""
     h = src.shape[-1]
