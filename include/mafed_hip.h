@@ -270,6 +270,26 @@ int mafed_attn_decode_beam(const void* qkv_prefix, int S0, void* qkv_new, int ca
                            const int* anc, int H, int D, int rot, const float* rot_cos, const float* rot_sin,
                            const int64_t* attention_mask, int T, void* out, void* stream);
 
+/* ---- sampled decoding (model.sample) -------------------------------------------------------------------------------------------
+ * One launch draws one token per row: what transformers.GenerationMixin._sample does per step with TemperatureLogitsWarper,
+ * TopKLogitsWarper, TopPLogitsWarper and MinPLogitsWarper (in that order), softmax and torch.multinomial, plus the eos / pad tail of
+ * the greedy pick.  logits [R, V] fp32 or bf16, row stride ldl elements, V <= 65536.  With z = logit / temperature (> 0):
+ *   top_k  (0 = off)       keep z >= the k-th largest z; ties at the threshold are all kept
+ *   top_p  in (0, 1]       over the top-k survivors: keep z >= z*, the largest value with mass{z > z*} < top_p * mass(survivors) <=
+ *                          mass{z >= z*}.  A tie on the cut is kept whole (TopPLogitsWarper keeps an order-dependent part of it).
+ *   min_p  in [0, 1)       keep z >= z_max + log(min_p)
+ * and with p_i = exp(z_i - z_max) / Z over the kept set the token is the first kept id, ascending, whose inclusive cumulative
+ * probability exceeds u.  u = uniforms[row] when uniforms != NULL; otherwise Philox4x32-10 with key = (low, high) half of *seed (one
+ * word in DEVICE memory, read by the kernel: a captured launch sees the value the word holds at replay) and counter = (row, step, 0,
+ * 0), u = ((x0 >> 8) + 0.5) * 2^-24 evaluated in fp32.  Masses are 64-bit integers (floor(exp(z - z_max) * 2^47)), so a row's result is the same bits
+ * on every run and does not depend on R or on the other rows.
+ * unfinished (may be NULL; int64 [R], read and written): a row whose flag is 0 emits `pad` (logprob 0, kept 0); a drawn `eos`
+ * (eos < 0: none) clears the row's flag.  token int64 [R]; logprob (may be NULL) fp32 [R], the log-probability of the drawn token under
+ * the kept, renormalised distribution; kept (may be NULL) int32 [R], the size of the kept set. */
+int mafed_sample_token(const void* logits, mafed_dtype dtype, int64_t ldl, int R, int V, float temperature, int top_k, float top_p,
+                       float min_p, const uint64_t* seed, int step, const float* uniforms, int64_t* unfinished, int eos, int pad,
+                       int64_t* token, float* logprob, int* kept, void* stream);
+
 /* ---- online EWC penalty (mafed/methods/ewc.py:105-127) -------------------------------------
  * The reference's compute_regularization over named_parameters(), on the flat fp32 buffers:
  *   fwd: out[0] = beta * out[0] + half_lambda * sum_i fisher[i] * (p[i] - p_old[i])^2     (half_lambda = 0.5 * reg_lambda;

@@ -1,4 +1,4 @@
-"""Generation for ``VLPythiaForCausalLM``: greedy and beam search, the KV-cached decode step, its cache and the captured-graph decode.
+"""Generation for ``VLPythiaForCausalLM``: greedy search, beam search and sampling, the KV-cached decode step, its cache and the captured-graph decode.
 ``GenerationMixin`` is a base class of the model (mafed_amd/model.py, which this module does not import): it uses the model's engine
 forward, parameter records and rotary tables, and the state ``fused_decode`` / ``beam_trace`` / ``_decode_graphs`` its ``__init__`` declares."""
 from __future__ import annotations
@@ -30,6 +30,15 @@ def _greedy_pick(last_logits: torch.Tensor, unfinished: torch.Tensor, eos_token_
     return nxt, unfinished
 
 
+def _sample_pick(last_logits: torch.Tensor, warp, seed: torch.Tensor, step: int, unfinished: Optional[torch.Tensor], eos_token_id, pad_token_id,
+                 logprob: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The sampled counterpart of ``_greedy_pick`` as one launch: ``warp`` = (temperature, top_k, top_p, min_p); ``unfinished`` is
+    updated in place.  Shared by the eager loops and the captured graph's body."""
+    temperature, top_k, top_p, min_p = warp
+    return ops.sample_token(last_logits, temperature, top_k, top_p, min_p, seed=seed, step=step, unfinished=unfinished,
+                            eos_token_id=eos_token_id, pad_token_id=0 if pad_token_id is None else pad_token_id, logprob=logprob)
+
+
 class GenerationMixin:
     """``generate`` and what it runs on, as methods of the model."""
 
@@ -58,7 +67,7 @@ class GenerationMixin:
         with ``pad_token_id`` up to the longest returned hypothesis; ``return_dict_in_generate`` adds the length-normalised
         ``sequences_scores`` (a beam-search option: the greedy path returns its tensor as before).  ``use_cache=False`` recomputes the B * k beams' full sequences every step; ``use_cache=True`` prefills
         each sample once and decodes its k beams over the shared prefix (``_beam_search``).  Not implemented: sampling (beam-sample
-        included), graph capture of the beam loop, diverse / constrained beam search."""
+        included), graph capture of the beam loop, diverse / constrained beam search.  Sampled decoding is a method of its own, ``sample``."""
         if do_sample:
             raise NotImplementedError("sampling (do_sample=True, beam-sample included) is not implemented: greedy or beam search only")
         if kwargs.get("num_beam_groups") not in (None, 1) or kwargs.get("constraints") is not None or kwargs.get("force_words_ids") is not None:
@@ -129,6 +138,106 @@ class GenerationMixin:
         if return_step_logits:
             return out, torch.stack(step_logits, dim=0)
         return out
+
+    # ---- sampled decode (DESIGN.md section 4c'') -----------------------------------------------------------------------
+    @torch.no_grad()
+    def sample(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
+               patch_embeddings: Optional[torch.Tensor] = None, max_new_tokens: int = 10, use_cache: bool = True,
+               pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = 0, temperature: float = 1.0, top_k: int = 0,
+               top_p: float = 1.0, min_p: float = 0.0, num_return_sequences: int = 1, seed: int = 0, use_graph: bool = False,
+               return_step_logits: bool = False, return_logprobs: bool = False):
+        """Multinomial sampling with HF ``GenerationMixin.sample`` semantics (temperature, then top-k, top-p and min-p warping, one draw
+        per row and step; finished rows emit ``pad_token_id``), every pick one launch of ``ops.sample_token`` (csrc/sample.hip) and
+        deterministic under ``seed``: the uniform number of row r at step t is Philox4x32-10 of (seed, r, t), whichever path runs.
+
+        -> [B * n, T + n_generated] with n = ``num_return_sequences`` (1 .. 8): row b * n + j is sample j of prompt b (HF's
+        ``expand_inputs_for_generation`` order), cut like the greedy output at the slowest row's first eos.  ``return_step_logits`` adds
+        the fp32 last-position logits of every step [n_generated, B * n, V], ``return_logprobs`` the drawn tokens' log-probabilities under
+        the warped distribution [B * n, n_generated] (0 where a finished row emitted pad); both follow the sequences in that order.
+
+        ``use_cache=False`` repeats the inputs n times and recomputes the whole sequence per token.  ``use_cache=True`` with n = 1 is the
+        greedy cached loop with the pick replaced (``use_graph=True``: the steps replayed from one hipGraph that reads the seed from a
+        device word, so a new seed needs no new capture); with n > 1 every prompt is prefilled ONCE and its n samples decode over the
+        shared prefix (``ops.attn_decode_beam`` under an identity ancestry table), step 0 drawing all n tokens from the prompt's one
+        logits row.  No host synchronisation inside the loop."""
+        n = num_return_sequences
+        if not temperature > 0.0:
+            raise ValueError(f"temperature must be > 0, got {temperature!r}")
+        if not isinstance(top_k, int) or top_k < 0:
+            raise ValueError(f"top_k must be an int >= 0 (0 = off), got {top_k!r}")
+        if not 0.0 < top_p <= 1.0:
+            raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
+        if not 0.0 <= min_p < 1.0:
+            raise ValueError(f"min_p must be in [0, 1), got {min_p!r}")
+        if not isinstance(n, int) or n < 1 or n > 8:
+            raise ValueError(f"num_return_sequences must be an int in 1 .. 8, got {n!r}")
+        if not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+            raise ValueError(f"seed must be an int that fits a uint64, got {seed!r}")
+        if max_new_tokens < 1:
+            raise ValueError(f"sample needs max_new_tokens >= 1, got {max_new_tokens}")
+        if input_ids is None or (pixel_values is None and patch_embeddings is None):
+            raise ValueError("sample needs input_ids and pixel_values / patch_embeddings")
+        if use_graph and (n > 1 or not use_cache or return_step_logits):
+            raise NotImplementedError("use_graph=True serves the cached n = 1 path without return_step_logits")
+        feats, ids, am, pad_token_id = self._generate_inputs(input_ids, attention_mask, pixel_values, patch_embeddings, pad_token_id, eos_token_id)
+        dev = ids.device
+        B, T = ids.shape
+        R = B * n
+        warp = (float(temperature), int(top_k), float(top_p), float(min_p))
+        if use_graph and max_new_tokens > 1:
+            key = (B, T, max_new_tokens, eos_token_id, pad_token_id, "sample") + warp
+            gd = self._decode_graphs.get(key)
+            if gd is None:
+                gd = self._decode_graphs[key] = _GraphedDecode(self, B, T, max_new_tokens, eos_token_id, pad_token_id, sample=warp)
+            gen, logprobs = gd.run(feats, ids, am, seed=seed)
+            step_logits = []
+        else:
+            seed_dev = ops.seed_word(seed, dev)
+            unfinished = torch.ones(R, dtype=torch.int64, device=dev) if eos_token_id is not None else None
+            new_tokens, new_logprobs, step_logits = [], [], []
+
+            def pick(last_logits, t):
+                lp = torch.empty(R, dtype=torch.float32, device=dev) if return_logprobs else None
+                nxt = _sample_pick(last_logits, warp, seed_dev, t, unfinished, eos_token_id, pad_token_id, lp)
+                new_tokens.append(nxt)
+                new_logprobs.append(lp)
+                if return_step_logits:
+                    step_logits.append(last_logits.float())
+                return nxt
+
+            if not use_cache:
+                feats_n, cur_ids, cur_am = feats.repeat_interleave(n, 0), ids.repeat_interleave(n, 0), am.repeat_interleave(n, 0)
+                for t in range(max_new_tokens):
+                    st = self._engine_forward(feats_n, cur_ids, cur_am, None, False, train=False)
+                    nxt = pick(st["logits"][:, -1, :], t)
+                    cur_ids = torch.cat([cur_ids, nxt[:, None]], dim=1)
+                    cur_am = torch.cat([cur_am, torch.ones_like(nxt)[:, None]], dim=1)
+            else:
+                cache, first_logits = self._prefill(feats, ids, am, max_new_tokens, beams=n)
+                if n > 1:
+                    if not cache.prerot:
+                        raise NotImplementedError("sampling n > 1 over the shared prefix needs the pre-rotated cache (rotary dims % 16 == 0, head size 64 / 128 / 256)")
+                    # every sample keeps its own slot for good: the ancestry table of the beam attention is the identity
+                    cache.anc = torch.arange(R, dtype=torch.int32, device=dev)[:, None].expand(R, cache.cap).contiguous()
+                    first_logits = first_logits.repeat_interleave(n, 0)   # the prompt's one row, named n times (counters b * n + j)
+                nxt = pick(first_logits, 0)
+                for t in range(max_new_tokens - 1):
+                    nxt = pick(self._engine_decode_step(nxt, t, cache), t + 1)
+            gen = torch.stack(new_tokens, dim=1)
+            logprobs = torch.stack(new_logprobs, dim=1) if return_logprobs else None
+        if eos_token_id is not None:
+            done = (gen == eos_token_id).to(torch.int64).cumsum(1).clamp_(max=1)       # 1 from the first eos on
+            first = (done.shape[1] - done.sum(1)) + done[:, -1]                        # tokens up to and including the first eos
+            n_keep = int(first.max().clamp_(max=gen.shape[1]))                         # the one host synchronisation
+            gen = gen[:, :n_keep]
+            step_logits = step_logits[:n_keep]
+            logprobs = logprobs[:, :n_keep] if logprobs is not None else None
+        out = (torch.cat([ids.repeat_interleave(n, 0) if n > 1 else ids, gen], dim=1),)
+        if return_step_logits:
+            out += (torch.stack(step_logits, dim=0),)
+        if return_logprobs:
+            out += (logprobs,)
+        return out[0] if len(out) == 1 else out
 
     def _generate_inputs(self, input_ids, attention_mask, pixel_values, patch_embeddings, pad_token_id, eos_token_id):
         """-> (vision features, token ids, attention mask) on the model's device and the effective ``pad_token_id``."""
@@ -304,9 +413,11 @@ class _DecodeCache:
 class _GraphedDecode:
     """Greedy decode steps 1 .. max_new-1 for one (B, T, max_new) shape as a single hipGraph.  Static buffers: the per-layer
     K/V cache (prefix written by the prefill's QKV GEMMs through ``qkv_out``, plus the per-token rows), the prompt mask, the
-    prefill's last-position logits, the ``unfinished`` flags and the generated tokens."""
+    prefill's last-position logits, the ``unfinished`` flags and the generated tokens.
+    ``sample`` = (temperature, top_k, top_p, min_p): the captured pick is ``_sample_pick`` instead; it reads the seed from the static
+    device word ``self.seed``, which ``run`` rewrites before the replay, and fills ``self.logprobs`` beside the tokens."""
 
-    def __init__(self, model, B: int, T: int, max_new: int, eos_token_id, pad_token_id):
+    def __init__(self, model, B: int, T: int, max_new: int, eos_token_id, pad_token_id, sample=None):
         cfg = model.config
         dev, cd = model.flat_params.device, model.compute_dtype
         S0 = cfg.num_vision_tokens + T
@@ -315,15 +426,27 @@ class _GraphedDecode:
         self.am = torch.ones((B, T), dtype=torch.int64, device=dev)
         self.first_logits = torch.zeros((B, cfg.vocab_size), dtype=cd if cd != torch.float32 else torch.float32, device=dev)
         self.tokens = torch.zeros((B, max_new), dtype=torch.int64, device=dev)
+        self.sample = sample
+        if sample is not None:
+            self.seed = ops.seed_word(0, dev)
+            self.logprobs = torch.zeros((B, max_new), dtype=torch.float32, device=dev)
+            self.unfinished = torch.ones(B, dtype=torch.int64, device=dev) if eos_token_id is not None else None
         model.rotary_tables(S0 + max(1, max_new))  # built (host -> device copy) before the capture, not inside it
         self.cache = _DecodeCache(model, list(store.unbind(0)), B, S0, max_new, self.am, fused=model.fused_decode,
                                   prefix_storage=store)   # (rotates the still-empty prefix once: harmless)
 
         def body():
-            unfinished = torch.ones(B, dtype=torch.int64, device=dev)
+            if sample is not None and self.unfinished is not None:
+                self.unfinished.fill_(1)
+            unfinished = torch.ones(B, dtype=torch.int64, device=dev) if sample is None else self.unfinished
             logits = self.first_logits
             for t in range(max_new):
-                nxt, unfinished = _greedy_pick(logits, unfinished, eos_token_id, pad_token_id)
+                if sample is None:
+                    nxt, unfinished = _greedy_pick(logits, unfinished, eos_token_id, pad_token_id)
+                else:
+                    lp = torch.empty(B, dtype=torch.float32, device=dev)
+                    nxt = _sample_pick(logits, sample, self.seed, t, unfinished, eos_token_id, pad_token_id, lp)
+                    self.logprobs[:, t] = lp
                 self.tokens[:, t] = nxt
                 if t + 1 < max_new:
                     logits = model._engine_decode_step(nxt, t, self.cache)
@@ -338,12 +461,17 @@ class _GraphedDecode:
         with torch.cuda.graph(self.graph):
             body()
 
-    def run(self, feats, ids, am) -> torch.Tensor:
+    def run(self, feats, ids, am, seed: Optional[int] = None):
+        """-> the generated tokens [B, max_new]; with a sampling pick (``seed`` given) -> (tokens, log-probabilities)."""
         m = self.model
+        if self.sample is not None:
+            self.seed.copy_(ops.seed_word(seed, self.seed.device))
         st = m._engine_forward(feats, ids, am, None, False, train=False, qkv_out=self.cache.prefix, last_only=True)
         if self.cache.prerot:
             self.cache.rotate_prefix()   # this prefill's keys, rotated in place for the captured steps
         self.am.copy_(am)
         self.first_logits.copy_(st["logits"][:, -1, :])
         self.graph.replay()
+        if self.sample is not None:
+            return self.tokens.clone(), self.logprobs.clone()
         return self.tokens.clone()

@@ -418,6 +418,40 @@ def beam_update(cand, B: int, k: int, step: int, cap: int, eos: int, pad: int, e
                                         _stream()), "mafed_beam_update")
 
 
+def seed_word(seed: int, device) -> torch.Tensor:
+    """The sampler's seed as one 64-bit word in device memory (int64 storage of the uint64 bit pattern)."""
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must fit a uint64, got {seed}")
+    return torch.tensor([seed - (1 << 64) if seed >= 1 << 63 else seed], dtype=torch.int64, device=device)
+
+
+def sample_token(logits: torch.Tensor, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, min_p: float = 0.0, *,
+                 seed: Optional[torch.Tensor] = None, step: int = 0, uniforms: Optional[torch.Tensor] = None,
+                 unfinished: Optional[torch.Tensor] = None, eos_token_id: Optional[int] = None, pad_token_id: int = 0,
+                 token: Optional[torch.Tensor] = None, logprob: Optional[torch.Tensor] = None, kept: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One drawn token per row of ``logits`` [R, V] (fp32 / bf16, unit column stride): temperature, top-k, top-p and min-p in HF's order,
+    then the inverse CDF in ascending token id (mafed_sample_token).  The uniform numbers are ``uniforms`` (fp32 [R]) when given, else
+    Philox4x32-10 of (``seed``: the device word of ``seed_word``, row, ``step``).  ``unfinished`` (int64 [R], updated in place): finished
+    rows emit ``pad_token_id``, a drawn ``eos_token_id`` clears the flag.  ``logprob`` (fp32 [R]) and ``kept`` (int32 [R]) are optional
+    outputs, filled when passed.  Returns ``token`` (int64 [R])."""
+    R, V = logits.shape
+    assert logits.stride(1) == 1 and (seed is not None or uniforms is not None)
+    assert seed is None or (seed.dtype == torch.int64 and seed.numel() == 1)
+    assert uniforms is None or (uniforms.dtype == torch.float32 and uniforms.numel() == R and uniforms.is_contiguous())
+    assert unfinished is None or (unfinished.dtype == torch.int64 and unfinished.numel() == R and unfinished.is_contiguous())
+    assert logprob is None or (logprob.dtype == torch.float32 and logprob.numel() == R and logprob.is_contiguous())
+    assert kept is None or (kept.dtype == torch.int32 and kept.numel() == R and kept.is_contiguous())
+    if token is None:
+        token = torch.empty(R, dtype=torch.int64, device=logits.device)
+    assert token.dtype == torch.int64 and token.numel() == R and token.is_contiguous()
+    check(_lib.load().mafed_sample_token(_ptr(logits), _dt(logits), logits.stride(0), R, V, float(temperature), int(top_k), float(top_p),
+                                         float(min_p), _ptr(seed), int(step), _ptr(uniforms), _ptr(unfinished),
+                                         -1 if eos_token_id is None else int(eos_token_id), int(pad_token_id), _ptr(token), _ptr(logprob),
+                                         _ptr(kept), _stream()), "mafed_sample_token")
+    return token
+
+
 def gemm_grouped_fuses_sumsq(shapes: Sequence[Tuple[int, int, int]], transA: bool, transB: bool) -> bool:
     """Would ``gemm_grouped`` run these (M, N, K) bf16 -> fp32 products as one persistent launch with the squares of C fused into its
     epilogue?  (host-side query, no launch)"""
