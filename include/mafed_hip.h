@@ -270,6 +270,25 @@ int mafed_attn_decode_beam(const void* qkv_prefix, int S0, void* qkv_new, int ca
                            const int* anc, int H, int D, int rot, const float* rot_cos, const float* rot_sin,
                            const int64_t* attention_mask, int T, void* out, void* stream);
 
+/* ---- shared-image prefill (generate / sample with image_index; DESIGN.md section 4c''') ------------------------------------------
+ * B prompts over N distinct images.  The prompt is [P image | T text], fully causal with arange positions, so the image rows' K / V
+ * depend on the image alone: they are computed once per image into qkv_img [N,P,H,3,D] (k un-rotated, as the QKV GEMM wrote it) and
+ * the text rows qkv_txt [B,T,H,3,D] attend them through image_index [B] (int64, values in [0, N); NULL = identity, N == B).
+ * mafed_attn_suffix_fwd computes exactly rows P .. P+T-1 of mafed_attn_fwd on the assembled [B, P+T] sequence: query j of prompt b
+ * sits at position P + j and sees the P keys of its image and text keys 0 .. j of its own prompt, minus the left-padding range of
+ * attention_mask [B,T]; partial rotary on load (position = key index, rot_cos / rot_sin cover >= P + T positions); softmax in fp32,
+ * scale D^-0.5.  A query at a padded position, or of a prompt whose text is all padding, still attends the image keys.
+ * F32: exact kernel, D <= 256.  BF16: MFMA kernel over 64-key tiles for D in {64, 128, 256} with rot in {0, 16, 32, 64} (16-byte
+ * aligned tensors), the exact kernel on bf16 data otherwise.  out [B,T,H*D] in dtype.  Index values are clamped into [0, N). */
+int mafed_attn_suffix_fwd(const void* qkv_img, const int64_t* image_index, int N, int P, const void* qkv_txt, int T, mafed_dtype dtype,
+                          int B, int H, int D, int rot, const float* rot_cos, const float* rot_sin, const int64_t* attention_mask,
+                          void* out, void* stream);
+/* The decode cache's prefix from the two stores, every layer in one launch: out [L, B*(P+T), W] = per prompt the P rows of image
+ * image_index[b] from qkv_img [L, N*P, W], then its own T rows from qkv_txt [L, B*T, W].  A plain 16-byte-per-lane copy: the row
+ * size (W elements of dtype) is a multiple of 16 bytes, the tensors are 16-byte aligned. */
+int mafed_prefix_gather(const void* qkv_img, const void* qkv_txt, const int64_t* image_index, int L, int N, int B, int P, int T, int64_t W,
+                        mafed_dtype dtype, void* out, void* stream);
+
 /* ---- sampled decoding (model.sample) -------------------------------------------------------------------------------------------
  * One launch draws one token per row: what transformers.GenerationMixin._sample does per step with TemperatureLogitsWarper,
  * TopKLogitsWarper, TopPLogitsWarper and MinPLogitsWarper (in that order), softmax and torch.multinomial, plus the eos / pad tail of

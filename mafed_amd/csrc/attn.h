@@ -1,5 +1,5 @@
-// Shared declarations of the attention kernels: exact-fp32 parity kernels (attn_ref.hip), bf16 MFMA kernels (attn_mfma.hip) and the
-// KV-cached decode kernels (attn_decode.hip).
+// Shared declarations of the attention kernels: exact-fp32 parity kernels (attn_ref.hip), bf16 MFMA kernels (attn_mfma.hip), the
+// KV-cached decode kernels (attn_decode.hip) and the shared-image prefill's suffix attention and prefix gather (attn_suffix.hip).
 #pragma once
 #include "common.h"
 
@@ -42,6 +42,25 @@ int attn_mfma_fwd_launch(const void* qkv, const AttnShape& sh, const float* rc, 
                          hipStream_t st);
 int attn_mfma_bwd_launch(const void* qkv, const void* out, const void* dout, const float* lse, const AttnShape& sh, const float* rc,
                          const float* rs, const int64_t* am, void* dqkv, float* delta, float* colsum, bool* colsum_done, hipStream_t st);
+
+// Suffix attention (attn_suffix.hip, attn_mfma.hip): the T text queries of prompt b against the P keys of image image_index[b] (NULL:
+// image b) followed by the prompt's own text keys = rows P .. P+T-1 of the forward above on the assembled [B, P+T] sequence.
+struct SuffixShape {
+  int B, N, P, T, H, D, rot;
+};
+// image of prompt b, clamped into [0, N): the host validates the index, a stray value must still not leave the image store
+__device__ __forceinline__ int64_t suffix_image(const int64_t* __restrict__ image_index, int b, int N) {
+  const int64_t n = image_index ? image_index[b] : (int64_t)b;
+  return n < 0 ? 0 : (n >= N ? N - 1 : n);
+}
+template <typename T>
+int attn_suffix_ref_launch(const void* qkv_img, const int64_t* image_index, const void* qkv_txt, const SuffixShape& sh, const float* rc,
+                           const float* rs, const int64_t* am, void* out, hipStream_t st);
+int attn_suffix_mfma_launch(const void* qkv_img, const int64_t* image_index, const void* qkv_txt, const SuffixShape& sh, const float* rc,
+                            const float* rs, const int64_t* am, void* out, hipStream_t st);
+// out [L, B*(P+T), W] = per prompt the P rows of its image from img [L, N*P, W], then its T rows from txt [L, B*T, W]
+int prefix_gather_launch(const void* img, const void* txt, const int64_t* image_index, int L, int N, int B, int P, int T, int64_t row_bytes,
+                         void* out, hipStream_t st);
 
 void attn_mfma_set_variant(int v);  // 0 automatic (resident kernels when K/V fit in LDS), 1 tiled kernels only
 

@@ -36,6 +36,44 @@ extern "C" int mafed_attn_fwd(const void* qkv, mafed_dtype dtype, int B, int S, 
   return MAFED_OK;
 }
 
+// Suffix attention of the shared-image prefill: rows P .. P+T-1 of mafed_attn_fwd on the assembled [image of image_index[b] | text b].
+extern "C" int mafed_attn_suffix_fwd(const void* qkv_img, const int64_t* image_index, int N, int P, const void* qkv_txt, int T,
+                                     mafed_dtype dtype, int B, int H, int D, int rot, const float* rot_cos, const float* rot_sin,
+                                     const int64_t* attention_mask, void* out, void* stream) {
+  MAFED_CHECK_ARG(qkv_img && qkv_txt && attention_mask && out, "attn_suffix_fwd: null pointer");
+  MAFED_CHECK_ARG(B > 0 && N > 0 && P > 0 && T > 0 && H > 0 && D > 0 && D <= 256, "attn_suffix_fwd: bad shape B=%d N=%d P=%d T=%d H=%d D=%d", B, N,
+                  P, T, H, D);
+  MAFED_CHECK_ARG(image_index || N == B, "attn_suffix_fwd: no image_index needs N == B (N=%d B=%d)", N, B);
+  MAFED_CHECK_ARG(rot >= 0 && rot <= D && rot % 2 == 0 && (rot == 0 || (rot_cos && rot_sin)), "attn_suffix_fwd: rotary arguments invalid");
+  SuffixShape sh{B, N, P, T, H, D, rot};
+  hipStream_t st = as_stream(stream);
+  int rc;
+  if (dtype == MAFED_F32) {
+    rc = attn_suffix_ref_launch<float>(qkv_img, image_index, qkv_txt, sh, rot_cos, rot_sin, attention_mask, out, st);
+  } else if (mfma_ok(D, rot)) {
+    MAFED_CHECK_ARG((((uintptr_t)qkv_img | (uintptr_t)qkv_txt | (uintptr_t)out) & 15) == 0, "attn_suffix_fwd(bf16): qkv/out must be 16-byte aligned");
+    rc = attn_suffix_mfma_launch(qkv_img, image_index, qkv_txt, sh, rot_cos, rot_sin, attention_mask, out, st);
+  } else {
+    rc = attn_suffix_ref_launch<bf16_t>(qkv_img, image_index, qkv_txt, sh, rot_cos, rot_sin, attention_mask, out, st);
+  }
+  if (rc) return rc;
+  MAFED_CHECK_LAUNCH("attn_suffix_fwd");
+  return MAFED_OK;
+}
+
+// Prefix assembly of the shared-image prefill: out [L, B*(P+T), W] from the image store [L, N*P, W] and the text store [L, B*T, W].
+extern "C" int mafed_prefix_gather(const void* qkv_img, const void* qkv_txt, const int64_t* image_index, int L, int N, int B, int P, int T,
+                                   int64_t W, mafed_dtype dtype, void* out, void* stream) {
+  MAFED_CHECK_ARG(qkv_img && qkv_txt && out, "prefix_gather: null pointer");
+  MAFED_CHECK_ARG(L > 0 && N > 0 && B > 0 && P > 0 && T > 0 && W > 0, "prefix_gather: bad shape L=%d N=%d B=%d P=%d T=%d", L, N, B, P, T);
+  MAFED_CHECK_ARG(image_index || N == B, "prefix_gather: no image_index needs N == B (N=%d B=%d)", N, B);
+  MAFED_CHECK_ARG((((uintptr_t)qkv_img | (uintptr_t)qkv_txt | (uintptr_t)out) & 15) == 0, "prefix_gather: tensors must be 16-byte aligned");
+  int rc = prefix_gather_launch(qkv_img, qkv_txt, image_index, L, N, B, P, T, W * (dtype == MAFED_F32 ? 4 : 2), out, as_stream(stream));
+  if (rc) return rc;
+  MAFED_CHECK_LAUNCH("prefix_gather");
+  return MAFED_OK;
+}
+
 // Bidirectional attention of the frozen CLIP vision tower (clip:259-277): no mask, no rotary, forward only.
 extern "C" int mafed_attn_fwd_bidir(const void* qkv, mafed_dtype dtype, int B, int S, int H, int D, void* out, float* lse, void* stream) {
   MAFED_CHECK_ARG(qkv && out && lse, "attn_fwd_bidir: null pointer");

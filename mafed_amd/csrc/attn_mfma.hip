@@ -320,6 +320,126 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(const bf16_t* __rest
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// suffix forward (shared-image prefill, attn.h SuffixShape): the tiled forward above for the T text queries of a prompt only.
+// Key j of the assembled sequence is row j of the prompt's image (store qkv_img, through image_index) for j < P and row j - P
+// of the prompt's own text (qkv_txt) behind it; query row q of the text sits at position P + q.  Block = 64 text rows of one
+// (b, h), 4 waves x 16 rows, 64-key tiles of the assembled sequence up to the block's diagonal; a wave whose rows lie past T
+// or wholly before a tile only helps staging it.  The last query tile and the last key tile are ragged: rows >= T / keys >=
+// P + T are staged as zeros and masked.  Every query sees key 0 (an image key: P >= 1), so no row is empty.
+// ------------------------------------------------------------------------------------------------------------
+namespace {
+template <int D, bool ROT>
+__device__ __forceinline__ void stage_rows_split(char* __restrict__ img, const bf16_t* __restrict__ ibase, const bf16_t* __restrict__ tbase,
+                                                 int64_t rstride, int r0, int P, int S, int rot, const float* __restrict__ rc,
+                                                 const float* __restrict__ rs, int tid) {
+  constexpr int CPR = D / 8;
+#pragma unroll
+  for (int c = tid; c < 64 * CPR; c += 256) {
+    const int row = c / CPR, ch = c % CPR;
+    const int gr = r0 + row;
+    const bf16_t* rowp = gr < P ? ibase + (int64_t)gr * rstride : tbase + (int64_t)(gr - P) * rstride;
+    uint4 v;
+    if (ROT) v = load_chunk_rot(rowp, ch, rot, rc, rs, gr, gr < S);
+    else v = gr < S ? *reinterpret_cast<const uint4*>(rowp + ch * 8) : make_uint4(0u, 0u, 0u, 0u);
+    *reinterpret_cast<uint4*>(img + tile_off<D>(row, ch)) = v;
+  }
+}
+}  // namespace
+
+template <int D>
+__global__ __launch_bounds__(256) void attn_suffix_mfma_kernel(const bf16_t* __restrict__ qkv_img, const int64_t* __restrict__ image_index,
+                                                               const bf16_t* __restrict__ qkv_txt, SuffixShape sh, const float* __restrict__ rc,
+                                                               const float* __restrict__ rs, const int64_t* __restrict__ am,
+                                                               bf16_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];  // 2 * 64 * D * 2 bytes
+  char* kimg = lds;
+  char* vimg = lds + 64 * D * 2;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int P = sh.P, T = sh.T, S = sh.P + sh.T, H = sh.H, rot = sh.rot;
+  const int qt = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+  const int64_t rstride = (int64_t)H * 3 * D;
+  const bf16_t* ib = qkv_img + (suffix_image(image_index, b, sh.N) * P * H + h) * 3 * D;
+  const bf16_t* tb = qkv_txt + ((int64_t)b * T * H + h) * 3 * D;
+  const int q0 = qt * 64 + wave * 16;  // text rows q0 .. q0 + 15, positions P + q0 ..
+  const int myq = q0 + (lane & 15), mypos = P + myq;
+  const int g = lane >> 4;
+  const bool active = q0 < T;
+
+  bf16x8 qf[D / 32];
+#pragma unroll
+  for (int ks = 0; ks < D / 32; ++ks)
+    qf[ks] = __builtin_bit_cast(bf16x8, load_chunk_rot(tb + (int64_t)myq * rstride, ks * 4 + g, rot, rc, rs, mypos, myq < T));
+
+  f32x4 o[D / 16];
+#pragma unroll
+  for (int i = 0; i < D / 16; ++i) o[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, l = 0.f;
+  const float scale = rsqrtf((float)D);
+  const int last_q = min(qt * 64 + 63, T - 1);
+  const int nkt = (P + last_q) / 64 + 1;
+
+  for (int kt = 0; kt < nkt; ++kt) {
+    __syncthreads();
+    stage_rows_split<D, true>(kimg, ib + D, tb + D, rstride, kt * 64, P, S, rot, rc, rs, tid);
+    stage_rows_split<D, false>(vimg, ib + 2 * D, tb + 2 * D, rstride, kt * 64, P, S, rot, rc, rs, tid);
+    __syncthreads();
+    if (!active || kt * 64 > P + q0 + 15) continue;  // wave-uniform: no row of this wave sees the tile
+    f32x4 s[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      s[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < D / 32; ++ks) s[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_row<D>(kimg, j, ks, lane), qf[ks], s[j], 0, 0, 0);
+    }
+    const bool need_mask = kt * 64 + 63 >= P;  // a tile of image keys only lies before every query and has no padding
+    float tmax = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float v = s[j][r] * scale;
+        if (need_mask) {
+          const int key = kt * 64 + j * 16 + 4 * g + r;
+          if (key > mypos || !key_ok(am, b, key, P, T, S)) v = -INFINITY;
+        }
+        s[j][r] = v;
+        tmax = fmaxf(tmax, v);
+      }
+    tmax = col_max(tmax);
+    const float mn = fmaxf(m, tmax);
+    const float alpha = __expf(m - mn);  // m = -inf on the first tile -> 0
+    m = mn;
+    float ps = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float p = __expf(s[j][r] - mn);
+        s[j][r] = p;
+        ps += p;
+      }
+    l = l * alpha + ps;
+#pragma unroll
+    for (int i = 0; i < D / 16; ++i) o[i] *= alpha;
+    const bf16x8 p0 = pack_acc(s[0], s[1]), p1 = pack_acc(s[2], s[3]);
+#pragma unroll
+    for (int dt = 0; dt < D / 16; ++dt) {
+      o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr<D>(vimg, dt, 0, lane), p0, o[dt], 0, 0, 0);
+      o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr<D>(vimg, dt, 1, lane), p1, o[dt], 0, 0, 0);
+    }
+  }
+  l = col_sum(l);
+  if (myq < T) {
+    const float inv = 1.0f / l;
+    bf16_t* op = out + ((int64_t)b * T + myq) * H * D + (int64_t)h * D;
+#pragma unroll
+    for (int dt = 0; dt < D / 16; ++dt)
+      store4(op + dt * 16 + 4 * g, make_float4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv));
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // backward, query-owned: delta = rowsum(dO * O) and dQ
 // ------------------------------------------------------------------------------------------------------------
 template <int D>
@@ -1129,6 +1249,24 @@ int attn_mfma_fwd_launch(const void* qkv, const AttnShape& sh, const float* rc, 
   else if (sh.D == 128) MAFED_FWD_TILED(128);
   else MAFED_FWD_TILED(256);
 #undef MAFED_FWD_TILED
+  return MAFED_OK;
+}
+
+int attn_suffix_mfma_launch(const void* qkv_img, const int64_t* image_index, const void* qkv_txt, const SuffixShape& sh, const float* rc,
+                            const float* rs, const int64_t* am, void* out, hipStream_t st) {
+  dim3 grid((sh.T + 63) / 64, sh.H, sh.B), block(256);
+  const size_t tb = (size_t)2 * 64 * sh.D * 2;
+  const double flops = 4.0 * sh.D * ((double)sh.T * sh.P + (double)sh.T * (sh.T + 1) / 2.0) * sh.H * sh.B;
+#define MAFED_SUFFIX_TILED(DD)                                                                                                    \
+  do {                                                                                                                            \
+    set_lds_attr(attn_suffix_mfma_kernel<DD>, tb);                                                                                \
+    launch(K_ATTN_FWD, flops, attn_suffix_mfma_kernel<DD>, grid, block, tb, st, (const bf16_t*)qkv_img, image_index, (const bf16_t*)qkv_txt, sh, rc, rs, am, \
+           (bf16_t*)out);                                                                                                         \
+  } while (0)
+  if (sh.D == 64) MAFED_SUFFIX_TILED(64);
+  else if (sh.D == 128) MAFED_SUFFIX_TILED(128);
+  else MAFED_SUFFIX_TILED(256);
+#undef MAFED_SUFFIX_TILED
   return MAFED_OK;
 }
 

@@ -48,7 +48,8 @@ class GenerationMixin:
                  patch_embeddings: Optional[torch.Tensor] = None, max_new_tokens: int = 10, use_cache: bool = True,
                  pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = 0, do_sample: bool = False,
                  return_step_logits: bool = False, use_graph: bool = False, num_beams: int = 1, length_penalty: float = 1.0,
-                 early_stopping: Any = False, num_return_sequences: int = 1, return_dict_in_generate: bool = False, **kwargs):
+                 early_stopping: Any = False, num_return_sequences: int = 1, return_dict_in_generate: bool = False,
+                 image_index: Optional[torch.Tensor] = None, **kwargs):
         """Greedy search with the call signature the reference validation uses (mafed/model/vqa_cont_learner.py:260-267,
         mafed/utils/eval_utils.py:170-177: ``generate(input_ids=, attention_mask=, pixel_values=, max_new_tokens=10,
         use_cache=False, pad_token_id=eos)``) and HF ``greedy_search`` semantics (transformers 4.37.1): next token = argmax of
@@ -67,7 +68,12 @@ class GenerationMixin:
         with ``pad_token_id`` up to the longest returned hypothesis; ``return_dict_in_generate`` adds the length-normalised
         ``sequences_scores`` (a beam-search option: the greedy path returns its tensor as before).  ``use_cache=False`` recomputes the B * k beams' full sequences every step; ``use_cache=True`` prefills
         each sample once and decodes its k beams over the shared prefix (``_beam_search``).  Not implemented: sampling (beam-sample
-        included), graph capture of the beam loop, diverse / constrained beam search.  Sampled decoding is a method of its own, ``sample``."""
+        included), graph capture of the beam loop, diverse / constrained beam search.  Sampled decoding is a method of its own, ``sample``.
+
+        ``image_index`` (int64 [B], any device): several prompts about one image.  ``patch_embeddings`` is then [N, P, Dv] (or
+        ``pixel_values`` holds N images) and prompt b looks at image ``image_index[b]``; N need not equal B.  ``use_cache=False`` recomputes
+        on ``feats.index_select(0, image_index)``; ``use_cache=True`` (greedy and beam) runs the image rows through the stack once per
+        image and the text rows once per prompt (``_prefill_shared``, DESIGN.md section 4c''').  Not with ``use_graph``."""
         if do_sample:
             raise NotImplementedError("sampling (do_sample=True, beam-sample included) is not implemented: greedy or beam search only")
         if kwargs.get("num_beam_groups") not in (None, 1) or kwargs.get("constraints") is not None or kwargs.get("force_words_ids") is not None:
@@ -78,6 +84,8 @@ class GenerationMixin:
             raise ValueError(f"num_return_sequences ({num_return_sequences}) must be in 1 .. num_beams ({num_beams})")
         if input_ids is None or (pixel_values is None and patch_embeddings is None):
             raise ValueError("generate needs input_ids and pixel_values / patch_embeddings")
+        if use_graph and image_index is not None:
+            raise NotImplementedError("use_graph=True (hipGraph capture) is not implemented with image_index")
         inputs = (input_ids, attention_mask, pixel_values, patch_embeddings, pad_token_id, eos_token_id)
         if num_beams > 1:
             if use_graph:
@@ -88,9 +96,12 @@ class GenerationMixin:
                 raise ValueError(f"beam search needs max_new_tokens >= 1, got {max_new_tokens}")
             if early_stopping not in (False, True, "never"):
                 raise ValueError(f"early_stopping must be True, False or 'never', got {early_stopping!r}")
-            return self._beam_search(*self._generate_inputs(*inputs), eos_token_id, num_beams, max_new_tokens, use_cache, float(length_penalty),
-                                     early_stopping, num_return_sequences, return_dict_in_generate)
+            feats, ids, am, pad_token_id = self._generate_inputs(*inputs)
+            feats, image_index = self._pair_images(feats, image_index, ids.shape[0], use_cache)
+            return self._beam_search(feats, ids, am, pad_token_id, eos_token_id, num_beams, max_new_tokens, use_cache, float(length_penalty),
+                                     early_stopping, num_return_sequences, return_dict_in_generate, image_index=image_index)
         feats, ids, am, pad_token_id = self._generate_inputs(*inputs)
+        feats, image_index = self._pair_images(feats, image_index, ids.shape[0], use_cache)
         B, T = ids.shape
         unfinished = torch.ones(B, dtype=torch.int64, device=ids.device)
         new_tokens, step_logits = [], []
@@ -122,7 +133,7 @@ class GenerationMixin:
             gen_all = gd.run(feats, ids, am)
             new_tokens = list(gen_all.unbind(1))
         else:
-            cache, first_logits = self._prefill(feats, ids, am, max_new_tokens)
+            cache, first_logits = self._prefill(feats, ids, am, max_new_tokens, image_index=image_index)
             nxt = pick(first_logits)
             for t in range(max_new_tokens - 1):
                 nxt = pick(self._engine_decode_step(nxt, t, cache))
@@ -145,7 +156,7 @@ class GenerationMixin:
                patch_embeddings: Optional[torch.Tensor] = None, max_new_tokens: int = 10, use_cache: bool = True,
                pad_token_id: Optional[int] = None, eos_token_id: Optional[int] = 0, temperature: float = 1.0, top_k: int = 0,
                top_p: float = 1.0, min_p: float = 0.0, num_return_sequences: int = 1, seed: int = 0, use_graph: bool = False,
-               return_step_logits: bool = False, return_logprobs: bool = False):
+               return_step_logits: bool = False, return_logprobs: bool = False, image_index: Optional[torch.Tensor] = None):
         """Multinomial sampling with HF ``GenerationMixin.sample`` semantics (temperature, then top-k, top-p and min-p warping, one draw
         per row and step; finished rows emit ``pad_token_id``), every pick one launch of ``ops.sample_token`` (csrc/sample.hip) and
         deterministic under ``seed``: the uniform number of row r at step t is Philox4x32-10 of (seed, r, t), whichever path runs.
@@ -159,7 +170,10 @@ class GenerationMixin:
         greedy cached loop with the pick replaced (``use_graph=True``: the steps replayed from one hipGraph that reads the seed from a
         device word, so a new seed needs no new capture); with n > 1 every prompt is prefilled ONCE and its n samples decode over the
         shared prefix (``ops.attn_decode_beam`` under an identity ancestry table), step 0 drawing all n tokens from the prompt's one
-        logits row.  No host synchronisation inside the loop."""
+        logits row.  No host synchronisation inside the loop.
+
+        ``image_index`` (int64 [B]): as in ``generate`` -- N images for B prompts, the image rows prefilled once per image (one host read of
+        the index's range before the loop)."""
         n = num_return_sequences
         if not temperature > 0.0:
             raise ValueError(f"temperature must be > 0, got {temperature!r}")
@@ -179,7 +193,10 @@ class GenerationMixin:
             raise ValueError("sample needs input_ids and pixel_values / patch_embeddings")
         if use_graph and (n > 1 or not use_cache or return_step_logits):
             raise NotImplementedError("use_graph=True serves the cached n = 1 path without return_step_logits")
+        if use_graph and image_index is not None:
+            raise NotImplementedError("use_graph=True (hipGraph capture) is not implemented with image_index")
         feats, ids, am, pad_token_id = self._generate_inputs(input_ids, attention_mask, pixel_values, patch_embeddings, pad_token_id, eos_token_id)
+        feats, image_index = self._pair_images(feats, image_index, ids.shape[0], use_cache)
         dev = ids.device
         B, T = ids.shape
         R = B * n
@@ -213,7 +230,7 @@ class GenerationMixin:
                     cur_ids = torch.cat([cur_ids, nxt[:, None]], dim=1)
                     cur_am = torch.cat([cur_am, torch.ones_like(nxt)[:, None]], dim=1)
             else:
-                cache, first_logits = self._prefill(feats, ids, am, max_new_tokens, beams=n)
+                cache, first_logits = self._prefill(feats, ids, am, max_new_tokens, beams=n, image_index=image_index)
                 if n > 1:
                     if not cache.prerot:
                         raise NotImplementedError("sampling n > 1 over the shared prefix needs the pre-rotated cache (rotary dims % 16 == 0, head size 64 / 128 / 256)")
@@ -256,17 +273,109 @@ class GenerationMixin:
         return torch.empty((cfg.num_hidden_layers, B * S0, 3 * cfg.num_attention_heads * cfg.head_dim), dtype=self.compute_dtype,
                            device=self.flat_params.device)
 
-    def _prefill(self, feats, ids, am, cap: int, beams: int = 1) -> Tuple["_DecodeCache", torch.Tensor]:
+    def _pair_images(self, feats, image_index, B: int, use_cache: bool):
+        """Check ``image_index`` against the N feature rows and the B prompts -> (features, index on the device or None).  Without an index
+        the features must be one per prompt.  With one and ``use_cache=False`` the features come back expanded (the reference's literal
+        recompute on ``feats.index_select(0, image_index)``) and the index is dropped.  One host read: the index's min and max."""
+        N = feats.shape[0]
+        if image_index is None:
+            if N != B:
+                raise ValueError(f"{N} images for {B} prompts: pass image_index (int64 [B]) to pair them")
+            return feats, None
+        if not isinstance(image_index, torch.Tensor) or image_index.dtype != torch.int64 or tuple(image_index.shape) != (B,):
+            got = (tuple(image_index.shape), image_index.dtype) if isinstance(image_index, torch.Tensor) else type(image_index).__name__
+            raise ValueError(f"image_index must be an int64 tensor of shape [{B}], got {got}")
+        idx = image_index.to(feats.device).contiguous()
+        lo, hi = torch.stack(idx.aminmax()).tolist() if B else (0, -1)
+        if lo < 0 or hi >= N:
+            raise ValueError(f"image_index values must lie in [0, {N}), got {lo} .. {hi}")
+        if not use_cache:
+            return feats.index_select(0, idx), None
+        return feats, idx
+
+    def _prefill(self, feats, ids, am, cap: int, beams: int = 1, image_index: Optional[torch.Tensor] = None) -> Tuple["_DecodeCache", torch.Tensor]:
         """Run the prompt once, its QKV GEMMs writing straight into a fresh prefix store -> (the decode cache over it, the last
-        position's logits [B, V])."""
+        position's logits [B, V]).  With ``image_index``: the shared-image form, ``_prefill_shared``."""
+        if image_index is not None:
+            return self._prefill_shared(feats, image_index, ids, am, cap, beams)
         B, T = ids.shape
         store = self._prefix_store(B, T)
         st = self._engine_forward(feats, ids, am, None, False, train=False, qkv_out=list(store.unbind(0)), last_only=True)
         cache = _DecodeCache(self, list(store.unbind(0)), B, st["S"], cap, am, fused=self.fused_decode, prefix_storage=store, beams=beams)
         return cache, st["logits"][:, -1, :]
 
+    def _prefill_shared(self, feats, image_index, ids, am, cap: int, beams: int = 1) -> Tuple["_DecodeCache", torch.Tensor]:
+        """``_prefill`` for B prompts over the N images of ``feats`` (DESIGN.md section 4c'''): the prompt is [image | text], fully causal with
+        arange positions, so the image rows of every layer depend on the image alone.  They go through the stack once per image (their
+        fused-QKV rows into an image store [L, N*P, 3h]; the last layer stops there, nothing reads its image rows), the text rows once
+        per prompt (text store [L, B*T, 3h]), attending [image image_index[b] | own text] through ``ops.attn_suffix_fwd``; one gather then
+        lays the two stores out as the [L, B*S0, 3h] prefix the decode cache takes.  The layer body is ``_engine_forward``'s, inference only."""
+        if not self.flat_params.is_cuda:
+            raise RuntimeError("mafed_amd runs on the GPU only (no CPU fallback); move the model with .cuda()")
+        cfg, cd = self.config, self.compute_dtype
+        P, h, H, D, L = cfg.num_vision_tokens, cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim, cfg.num_hidden_layers
+        pe = self._param_events
+        if pe is not None:   # behind every chunk of a pipelined optimiser update, as the engine forward orders itself layer by layer
+            main_st = torch.cuda.current_stream()
+            for key in ["pre"] + [("layer", i) for i in range(L)] + ["head"]:
+                main_st.wait_event(pe[key])
+            self._param_events = None
+        if self._shadow_dirty:
+            self.sync_shadow()
+        (B, T), N = ids.shape, feats.shape[0]
+        S0, rot, eps, dev = P + T, cfg.rotary_ndims, cfg.layer_norm_eps, ids.device
+        cos, sin = self.rotary_tables(S0)
+        wts, pars = self._tensors(0), self._tensors(1)
+        Wo, Po = wts.outer, pars.outer
+        img_store = torch.empty((L, N * P, 3 * h), dtype=cd, device=dev)
+        txt_store = torch.empty((L, B * T, 3 * h), dtype=cd, device=dev)
+
+        def mlp_and_residuals(i, x, ao, ln2):
+            w, p = wts.layers[i], pars.layers[i]
+            attn = ops.gemm(ao, w.dense_w, False, True, bias=p.dense_b, out_dtype=cd)
+            a = ops.gemm(ln2, w.fc1_w, False, True, bias=p.fc1_b, epilogue=EPI_GELU)
+            return ops.gemm(a, w.fc2_w, False, True, bias=p.fc2_b, out_dtype=torch.float32, res1=attn, res2=x)
+
+        # image pass, N * P rows: projector, then the layers over the image alone (S = P; the one-column mask of ones makes the last image
+        # key a valid "text" key of the full attention kernels, which take T >= 1 through this wrapper)
+        f2 = feats.reshape(N * P, cfg.vision_hidden_size)
+        if f2.dtype not in (torch.float32, torch.bfloat16):
+            f2 = f2.float()
+        fc = f2.contiguous() if f2.dtype == cd else ops.cast(f2.contiguous(), cd)
+        a0 = ops.gemm(fc, Wo.proj0_w, False, True, bias=Po.proj0_b, epilogue=EPI_GELU)
+        img = ops.gemm(a0, Wo.proj2_w, False, True, bias=Po.proj2_b)
+        x = img if img.dtype == torch.float32 else ops.cast(img, torch.float32)   # fp32 residual stream
+        ones = torch.ones((N, 1), dtype=torch.int64, device=dev)
+        for i in range(L):
+            w, p = wts.layers[i], pars.layers[i]
+            if i == L - 1:
+                ln1, _, _, _ = ops.layernorm_fwd(x, p.ln1_w, p.ln1_b, None, None, eps, cd, save_stats=False)
+                ops.gemm(ln1, w.qkv_w, False, True, bias=p.qkv_b, out=img_store[i])
+                break
+            ln1, ln2, _, _ = ops.layernorm_fwd(x, p.ln1_w, p.ln1_b, p.ln2_w, p.ln2_b, eps, cd, save_stats=False)
+            qkv = ops.gemm(ln1, w.qkv_w, False, True, bias=p.qkv_b, out=img_store[i])
+            ao, _ = ops.attn_fwd(qkv, N, P, H, D, rot, cos, sin, ones)
+            x = mlp_and_residuals(i, x, ao, ln2)
+        # text pass, B * T rows
+        x = Po.embed_in.index_select(0, ids.reshape(-1))
+        for i in range(L):
+            w, p = wts.layers[i], pars.layers[i]
+            ln1, ln2, _, _ = ops.layernorm_fwd(x, p.ln1_w, p.ln1_b, p.ln2_w, p.ln2_b, eps, cd, save_stats=False)
+            qkv = ops.gemm(ln1, w.qkv_w, False, True, bias=p.qkv_b, out=txt_store[i])
+            ao = ops.attn_suffix_fwd(img_store[i], image_index, N, P, qkv, T, B, H, D, rot, cos, sin, am)
+            x = mlp_and_residuals(i, x, ao, ln2)
+        xl = x.view(B, T, h)[:, -1, :].contiguous()
+        lnl, _, _, _ = ops.layernorm_fwd(xl, Po.final_ln_w, Po.final_ln_b, None, None, eps, cd, save_stats=False)
+        logits = ops.gemm(lnl, Wo.embed_out, False, True)
+        # prefix assembly: [image of the prompt | its text] per layer, one launch for all of them; the cache rotates the keys as ever
+        store = ops.prefix_gather(img_store, txt_store, image_index, B, P, T, out=self._prefix_store(B, T))
+        if self.prefill_trace is not None:   # tests / tools: the row counts that went through the stack
+            self.prefill_trace.append({"image_store": tuple(img_store.shape), "text_store": tuple(txt_store.shape), "prefix": tuple(store.shape)})
+        cache = _DecodeCache(self, list(store.unbind(0)), B, S0, cap, am, fused=self.fused_decode, prefix_storage=store, beams=beams)
+        return cache, logits
+
     def _beam_search(self, feats, ids, am, pad_token_id, eos_token_id, k: int, max_new: int, use_cache: bool, length_penalty: float,
-                     early_stopping, nrs: int, return_dict: bool):
+                     early_stopping, nrs: int, return_dict: bool, image_index: Optional[torch.Tensor] = None):
         """Beam search (generate(num_beams=k)); every decision on the device (csrc/beam.hip; the beams' attention is
         csrc/attn_decode_beam.hip), one host synchronisation at the end.
         Per step: mafed_beam_candidates (top 2k of log_softmax + running score per sample) and mafed_beam_update (finished set,
@@ -316,7 +425,7 @@ class GenerationMixin:
         else:
             # one prefill per sample: its last-position logits are the first step's (only beam 0 is live there), its K/V the prefix
             # that the sample's k beams share
-            cache, first_logits = self._prefill(feats, ids, am, max_new, beams=k)
+            cache, first_logits = self._prefill(feats, ids, am, max_new, beams=k, image_index=image_index)
             if not cache.prerot:
                 raise NotImplementedError("the cached beam search needs the pre-rotated cache (rotary dims % 16 == 0, head size 64 / 128 / 256)")
             beam_step(first_logits, torch.zeros(B, dtype=f32, device=dev), 0)

@@ -289,6 +289,7 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
         self.defer_ln_param_reduce = True   # LayerNorm parameter-gradient reduction on a side stream (needs overlap_param_grads)
         # generation (mafed_amd/generation.py)
         self.beam_trace: Optional[List[Any]] = None   # a list: generate(num_beams > 1) appends every step's candidate lists to it
+        self.prefill_trace: Optional[List[Any]] = None   # a list: a shared-image prefill (image_index) appends the shapes of its three stores to it
         self.fused_decode = True    # written by callers (tests, tools/decode_bench.py): False = the six-launch decode layer; read when a decode cache is built
         self._decode_graphs: Dict[Tuple, Any] = {}   # written and read by generate(use_graph=True): (B, T, max_new, eos, pad) -> _GraphedDecode
         # The hand-over of a backward sweep (_engine_backward_impl).  Its inputs are the attributes below, written by Trainer._device_step and

@@ -391,6 +391,46 @@ def attn_decode_beam(qkv_prefix: torch.Tensor, S0: int, qkv_new: torch.Tensor, t
     return out
 
 
+def _image_index(image_index: Optional[torch.Tensor], N: int, B: int, device) -> Optional[torch.Tensor]:
+    if image_index is None:
+        assert N == B, f"no image_index: N ({N}) must equal B ({B})"
+        return None
+    assert image_index.dtype == torch.int64 and image_index.shape == (B,) and image_index.is_contiguous() and image_index.device == device
+    return image_index
+
+
+def attn_suffix_fwd(qkv_img: torch.Tensor, image_index: Optional[torch.Tensor], N: int, P: int, qkv_txt: torch.Tensor, T: int, B: int, H: int,
+                    D: int, rot: int, cos, sin, attention_mask: torch.Tensor) -> torch.Tensor:
+    """Attention of the T text rows of B prompts over [image image_index[b] | own text] (mafed_attn_suffix_fwd) = rows P .. P+T-1 of
+    ``attn_fwd`` on the assembled sequence.  ``qkv_img`` [N*P, 3*H*D], ``qkv_txt`` [B*T, 3*H*D], ``image_index`` int64 [B] on the device
+    with values in [0, N) (the caller checks them; None = identity, N == B), ``attention_mask`` [B, T].  -> [B*T, H*D]"""
+    assert qkv_img.is_contiguous() and qkv_txt.is_contiguous() and qkv_img.dtype == qkv_txt.dtype
+    assert qkv_img.numel() == N * P * 3 * H * D and qkv_txt.numel() == B * T * 3 * H * D
+    assert attention_mask.shape == (B, T) and attention_mask.dtype == torch.int64 and attention_mask.is_contiguous()
+    assert cos.shape[0] >= P + T
+    image_index = _image_index(image_index, N, B, qkv_txt.device)
+    out = torch.empty((B * T, H * D), dtype=qkv_txt.dtype, device=qkv_txt.device)
+    check(_lib.load().mafed_attn_suffix_fwd(_ptr(qkv_img), _ptr(image_index), N, P, _ptr(qkv_txt), T, _dt(qkv_txt), B, H, D, rot, _ptr(cos),
+                                            _ptr(sin), _ptr(attention_mask), _ptr(out), _stream()), "mafed_attn_suffix_fwd")
+    return out
+
+
+def prefix_gather(qkv_img: torch.Tensor, qkv_txt: torch.Tensor, image_index: Optional[torch.Tensor], B: int, P: int, T: int,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The decode cache's prefix of every layer in one launch (mafed_prefix_gather): ``qkv_img`` [L, N*P, W] and ``qkv_txt`` [L, B*T, W]
+    -> [L, B*(P+T), W], per prompt the rows of image ``image_index[b]`` followed by its own text rows."""
+    L, NP, W = qkv_img.shape
+    N = NP // P
+    assert NP == N * P and qkv_txt.shape == (L, B * T, W) and qkv_img.dtype == qkv_txt.dtype and qkv_img.is_contiguous() and qkv_txt.is_contiguous()
+    image_index = _image_index(image_index, N, B, qkv_txt.device)
+    if out is None:
+        out = torch.empty((L, B * (P + T), W), dtype=qkv_txt.dtype, device=qkv_txt.device)
+    assert out.shape == (L, B * (P + T), W) and out.dtype == qkv_txt.dtype and out.is_contiguous()
+    check(_lib.load().mafed_prefix_gather(_ptr(qkv_img), _ptr(qkv_txt), _ptr(image_index), L, N, B, P, T, W, _dt(qkv_txt), _ptr(out), _stream()),
+          "mafed_prefix_gather")
+    return out
+
+
 def beam_candidates(logits: torch.Tensor, score: torch.Tensor, B: int, k: int, out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None):
     """Per sample, the top 2k of ``log_softmax(logits[row]) + score[row]`` over its kin = rows / B rows (mafed_beam_candidates).
     logits [B*kin, V] fp32 / bf16 (unit column stride), score fp32 [B*kin] -> (score fp32 [B,2k], token int64 [B,2k], parent int32 [B,2k]),
