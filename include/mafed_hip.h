@@ -289,6 +289,28 @@ int mafed_attn_suffix_fwd(const void* qkv_img, const int64_t* image_index, int N
 int mafed_prefix_gather(const void* qkv_img, const void* qkv_txt, const int64_t* image_index, int L, int N, int B, int P, int T, int64_t W,
                         mafed_dtype dtype, void* out, void* stream);
 
+/* ---- candidate scoring (model.score; DESIGN.md section 4c'''') -------------------------------------------------------------------
+ * C candidate answers of A tokens each behind one prefilled prompt.  qkv_prefix [B,S0,H,3,D] holds the prompt's fused-QKV rows (S0 =
+ * P image + T text positions, k un-rotated, as the QKV GEMM wrote them), qkv_cand [B,C,A,H,3,D] the candidates' rows.
+ * mafed_attn_cand_fwd: out[b,c,j] = row S0 + j of mafed_attn_fwd on the assembled [prefix b | candidate (b,c)] sequence of length
+ * S0 + A under the mask [attention_mask[b] | ones(A)]: the query sits at position S0 + j and sees the P = S0 - T image keys, the prefix
+ * text keys that the left-padding mask [B,T] leaves and keys 0 .. j of its own candidate, nothing of another candidate; partial rotary
+ * on load (position = key index: candidate key j is at S0 + j for every c; rot_cos / rot_sin cover >= S0 + A positions); softmax in
+ * fp32, scale D^-0.5.  T < S0: key 0 is an image key, so a prompt whose text is all padding still attends its image and no row is
+ * empty.  F32: exact kernel, D <= 256.  BF16: MFMA kernel for D in {64, 128, 256} with rot in {0, 16, 32, 64} on 16-byte aligned
+ * tensors -- the C*A rows of one (b,h) are one query axis cut into 64-row tiles, each prefix key tile staged once per query tile --
+ * the exact kernel on bf16 data otherwise.  out [B,C,A,H*D] in dtype. */
+int mafed_attn_cand_fwd(const void* qkv_prefix, int S0, const void* qkv_cand, int C, int A, mafed_dtype dtype, int B, int H, int D, int rot,
+                        const float* rot_cos, const float* rot_sin, const int64_t* attention_mask, int T, void* out, void* stream);
+/* out[r] = logits[row(r), target[r]] - logsumexp(logits[row(r), :]) in fp32, row(r) = logits_row[r] (NULL: r): several outputs may
+ * read one logits row (the C candidates' first token from the prompt's last position).  logits fp32 or bf16, row stride ldl elements;
+ * target [R] int64: < 0 gives 0 (a masked position), >= V gives NaN.  Fixed reduction order: the same bits on every call, whatever R. */
+int mafed_token_logprob(const void* logits, mafed_dtype dtype, int64_t ldl, const int* logits_row, const int64_t* target, int R, int64_t V,
+                        float* out, void* stream);
+/* out[r] = sum over the j with mask[r,j] != 0 (mask NULL: all) of token_logprob[r,j], in ascending j; mean != 0 divides by their
+ * number; a row without a token gives -inf.  token_logprob fp32 [R,A], mask int64 [R,A]. */
+int mafed_score_reduce(const float* token_logprob, const int64_t* mask, int R, int A, int mean, float* out, void* stream);
+
 /* ---- sampled decoding (model.sample) -------------------------------------------------------------------------------------------
  * One launch draws one token per row: what transformers.GenerationMixin._sample does per step with TemperatureLogitsWarper,
  * TopKLogitsWarper, TopPLogitsWarper and MinPLogitsWarper (in that order), softmax and torch.multinomial, plus the eos / pad tail of

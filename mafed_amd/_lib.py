@@ -46,6 +46,9 @@ SIGNATURES = {
     "mafed_attn_decode_beam": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
     "mafed_attn_suffix_fwd": (_i, [_p, _p, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
     "mafed_prefix_gather": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _l, _i, _p, _p]),
+    "mafed_attn_cand_fwd": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p]),
+    "mafed_token_logprob": (_i, [_p, _i, _l, _p, _p, _i, _l, _p, _p]),
+    "mafed_score_reduce": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "mafed_sample_token": (_i, [_p, _i, _l, _i, _i, _f, _i, _f, _f, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p]),
     "mafed_ewc_workspace_bytes": (_z, [_l]),
     "mafed_ewc_penalty_fwd": (_i, [_p, _p, _p, _l, _f, _f, _p, _p, _z, _p]),

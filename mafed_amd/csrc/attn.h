@@ -1,5 +1,6 @@
 // Shared declarations of the attention kernels: exact-fp32 parity kernels (attn_ref.hip), bf16 MFMA kernels (attn_mfma.hip), the
-// KV-cached decode kernels (attn_decode.hip) and the shared-image prefill's suffix attention and prefix gather (attn_suffix.hip).
+// KV-cached decode kernels (attn_decode.hip), the shared-image prefill's suffix attention and prefix gather (attn_suffix.hip) and the
+// candidate attention of model.score (attn_cand.hip).
 #pragma once
 #include "common.h"
 
@@ -61,6 +62,18 @@ int attn_suffix_mfma_launch(const void* qkv_img, const int64_t* image_index, con
 // out [L, B*(P+T), W] = per prompt the P rows of its image from img [L, N*P, W], then its T rows from txt [L, B*T, W]
 int prefix_gather_launch(const void* img, const void* txt, const int64_t* image_index, int L, int N, int B, int P, int T, int64_t row_bytes,
                          void* out, hipStream_t st);
+
+// Candidate attention (attn_cand.hip, attn_mfma.hip): the A rows of each of the C candidates of prompt b against the prompt's S0 prefix
+// keys (P = S0 - T image keys, T left-padded text keys) followed by the candidate's own earlier rows = rows S0 .. S0+A-1 of the forward
+// above on every assembled [prefix b | candidate (b, c)] sequence.
+struct CandShape {
+  int B, C, A, S0, T, H, D, rot;
+};
+template <typename T>
+int attn_cand_ref_launch(const void* qkv_pre, const void* qkv_cand, const CandShape& sh, const float* rc, const float* rs, const int64_t* am,
+                         void* out, hipStream_t st);
+int attn_cand_mfma_launch(const void* qkv_pre, const void* qkv_cand, const CandShape& sh, const float* rc, const float* rs, const int64_t* am,
+                          void* out, hipStream_t st);
 
 void attn_mfma_set_variant(int v);  // 0 automatic (resident kernels when K/V fit in LDS), 1 tiled kernels only
 

@@ -61,6 +61,31 @@ extern "C" int mafed_attn_suffix_fwd(const void* qkv_img, const int64_t* image_i
   return MAFED_OK;
 }
 
+// Candidate attention of model.score: rows S0 .. S0+A-1 of mafed_attn_fwd on every assembled [prefix b | candidate (b, c)].
+extern "C" int mafed_attn_cand_fwd(const void* qkv_prefix, int S0, const void* qkv_cand, int C, int A, mafed_dtype dtype, int B, int H, int D,
+                                   int rot, const float* rot_cos, const float* rot_sin, const int64_t* attention_mask, int T, void* out,
+                                   void* stream) {
+  MAFED_CHECK_ARG(qkv_prefix && qkv_cand && out, "attn_cand_fwd: null pointer");
+  MAFED_CHECK_ARG(B > 0 && C > 0 && A > 0 && H > 0 && D > 0 && D <= 256 && (int64_t)C * A <= 0x7fffffffLL,
+                  "attn_cand_fwd: bad shape B=%d C=%d A=%d H=%d D=%d", B, C, A, H, D);
+  MAFED_CHECK_ARG(S0 > 0 && T >= 0 && T < S0, "attn_cand_fwd: the prefix needs an image key in front of its text (S0=%d T=%d)", S0, T);
+  MAFED_CHECK_ARG(attention_mask || T == 0, "attn_cand_fwd: attention_mask missing (T=%d)", T);
+  MAFED_CHECK_ARG(rot >= 0 && rot <= D && rot % 2 == 0 && (rot == 0 || (rot_cos && rot_sin)), "attn_cand_fwd: rotary arguments invalid");
+  CandShape sh{B, C, A, S0, T, H, D, rot};
+  hipStream_t st = as_stream(stream);
+  int rc;
+  if (dtype == MAFED_F32) {
+    rc = attn_cand_ref_launch<float>(qkv_prefix, qkv_cand, sh, rot_cos, rot_sin, attention_mask, out, st);
+  } else if (mfma_ok(D, rot) && (((uintptr_t)qkv_prefix | (uintptr_t)qkv_cand | (uintptr_t)out) & 15) == 0) {
+    rc = attn_cand_mfma_launch(qkv_prefix, qkv_cand, sh, rot_cos, rot_sin, attention_mask, out, st);
+  } else {
+    rc = attn_cand_ref_launch<bf16_t>(qkv_prefix, qkv_cand, sh, rot_cos, rot_sin, attention_mask, out, st);
+  }
+  if (rc) return rc;
+  MAFED_CHECK_LAUNCH("attn_cand_fwd");
+  return MAFED_OK;
+}
+
 // Prefix assembly of the shared-image prefill: out [L, B*(P+T), W] from the image store [L, N*P, W] and the text store [L, B*T, W].
 extern "C" int mafed_prefix_gather(const void* qkv_img, const void* qkv_txt, const int64_t* image_index, int L, int N, int B, int P, int T,
                                    int64_t W, mafed_dtype dtype, void* out, void* stream) {

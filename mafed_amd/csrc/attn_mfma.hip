@@ -440,6 +440,136 @@ __global__ __launch_bounds__(256) void attn_suffix_mfma_kernel(const bf16_t* __r
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// candidate forward (model.score, attn.h CandShape): many short suffixes behind one masked prefix.  The C * A candidate rows of one
+// (b, h) are ONE flattened query axis r = c * A + j (position S0 + j); block = 64 of them, 4 waves x 16 rows, so a query tile spans
+// several candidates of the prompt.  Keys, in two runs of 64-row tiles:
+//   prefix tiles 0 .. ceil(S0 / 64) - 1: staged once per query tile for every candidate in it.  Every query lies behind the prefix: no
+//     causal test, only the pad test (tiles that reach the text range or run past S0);
+//   candidate tiles: the same flattened axis as keys, block-diagonal causal: key r' is visible to query r iff r' / A == r / A and
+//     r' <= r.  Only rows k0 = (first row of the tile's first candidate) .. the tile's last query can be visible, so the run starts at
+//     k0 (not tile-aligned) and is 1 or 2 tiles long for A <= 64; a candidate may straddle two query tiles, and A may exceed 64.
+// Rows >= C * A and keys >= S0 are staged as zeros and masked.  Key 0 is an image key (P >= 1): after the first tile no row is empty.
+// ------------------------------------------------------------------------------------------------------------
+namespace {
+template <int D, bool ROT>
+__device__ __forceinline__ void stage_rows_cand(char* __restrict__ img, const bf16_t* __restrict__ base, int64_t rstride, int r0, int CA, int A,
+                                                int S0, int rot, const float* __restrict__ rc, const float* __restrict__ rs, int tid) {
+  constexpr int CPR = D / 8;
+#pragma unroll
+  for (int c = tid; c < 64 * CPR; c += 256) {
+    const int row = c / CPR, ch = c % CPR;
+    const int gr = r0 + row;
+    uint4 v;
+    if (ROT) v = load_chunk_rot(base + (int64_t)gr * rstride, ch, rot, rc, rs, S0 + gr % A, gr < CA);
+    else v = gr < CA ? *reinterpret_cast<const uint4*>(base + (int64_t)gr * rstride + ch * 8) : make_uint4(0u, 0u, 0u, 0u);
+    *reinterpret_cast<uint4*>(img + tile_off<D>(row, ch)) = v;
+  }
+}
+}  // namespace
+
+template <int D>
+__global__ __launch_bounds__(256) void attn_cand_mfma_kernel(const bf16_t* __restrict__ qkv_pre, const bf16_t* __restrict__ qkv_cand, CandShape sh,
+                                                             const float* __restrict__ rc, const float* __restrict__ rs,
+                                                             const int64_t* __restrict__ am, bf16_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];  // 2 * 64 * D * 2 bytes
+  char* kimg = lds;
+  char* vimg = lds + 64 * D * 2;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int S0 = sh.S0, T = sh.T, P = sh.S0 - sh.T, A = sh.A, CA = sh.C * sh.A, H = sh.H, rot = sh.rot;
+  const int qt = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+  const int64_t rstride = (int64_t)H * 3 * D;
+  const bf16_t* pb = qkv_pre + ((int64_t)b * S0 * H + h) * 3 * D;
+  const bf16_t* cb = qkv_cand + ((int64_t)b * CA * H + h) * 3 * D;
+  const int q0 = qt * 64 + wave * 16;  // flattened candidate rows q0 .. q0 + 15
+  const int myq = q0 + (lane & 15);
+  const int mystart = myq / A * A;     // row 0 of this query's candidate: it sees candidate keys mystart .. myq
+  const int g = lane >> 4;
+  const bool active = q0 < CA;
+
+  bf16x8 qf[D / 32];
+#pragma unroll
+  for (int ks = 0; ks < D / 32; ++ks)
+    qf[ks] = __builtin_bit_cast(bf16x8, load_chunk_rot(cb + (int64_t)myq * rstride, ks * 4 + g, rot, rc, rs, S0 + myq % A, myq < CA));
+
+  f32x4 o[D / 16];
+#pragma unroll
+  for (int i = 0; i < D / 16; ++i) o[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  float m = -INFINITY, l = 0.f;
+  const float scale = rsqrtf((float)D);
+  const int nkp = (S0 + 63) / 64;                               // prefix tiles
+  const int k0 = qt * 64 / A * A;                               // first candidate key row any query of this tile can see
+  const int nkc = (min(qt * 64 + 63, CA - 1) - k0) / 64 + 1;    // candidate tiles k0 + 64 i .. up to the tile's last query
+  const int wlo = q0 / A * A, whi = q0 + 15;                    // candidate keys the rows of this wave can see
+
+  for (int kt = 0; kt < nkp + nkc; ++kt) {
+    const bool pre = kt < nkp;              // block-uniform
+    const int t0 = pre ? kt * 64 : k0 + (kt - nkp) * 64;
+    __syncthreads();
+    if (pre) {
+      stage_rows<D, 64, true>(kimg, pb + D, rstride, t0, S0, rot, rc, rs, tid);
+      stage_rows<D, 64, false>(vimg, pb + 2 * D, rstride, t0, S0, rot, rc, rs, tid);
+    } else {
+      stage_rows_cand<D, true>(kimg, cb + D, rstride, t0, CA, A, S0, rot, rc, rs, tid);
+      stage_rows_cand<D, false>(vimg, cb + 2 * D, rstride, t0, CA, A, S0, rot, rc, rs, tid);
+    }
+    __syncthreads();
+    if (!active || (!pre && (t0 > whi || t0 + 63 < wlo))) continue;  // wave-uniform: no row of this wave sees the tile
+    f32x4 s[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      s[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < D / 32; ++ks) s[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_row<D>(kimg, j, ks, lane), qf[ks], s[j], 0, 0, 0);
+    }
+    const bool need_mask = !pre || t0 + 63 >= P;  // a tile of image keys only has no padding
+    float tmax = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float v = s[j][r] * scale;
+        if (need_mask) {
+          const int key = t0 + j * 16 + 4 * g + r;
+          if (pre ? !key_ok(am, b, key, P, T, S0) : (key < mystart || key > myq)) v = -INFINITY;
+        }
+        s[j][r] = v;
+        tmax = fmaxf(tmax, v);
+      }
+    tmax = col_max(tmax);
+    const float mn = fmaxf(m, tmax);
+    const float alpha = __expf(m - mn);  // m = -inf on the first tile -> 0
+    m = mn;
+    float ps = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float p = __expf(s[j][r] - mn);
+        s[j][r] = p;
+        ps += p;
+      }
+    l = l * alpha + ps;
+#pragma unroll
+    for (int i = 0; i < D / 16; ++i) o[i] *= alpha;
+    const bf16x8 p0 = pack_acc(s[0], s[1]), p1 = pack_acc(s[2], s[3]);
+#pragma unroll
+    for (int dt = 0; dt < D / 16; ++dt) {
+      o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr<D>(vimg, dt, 0, lane), p0, o[dt], 0, 0, 0);
+      o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr<D>(vimg, dt, 1, lane), p1, o[dt], 0, 0, 0);
+    }
+  }
+  l = col_sum(l);
+  if (myq < CA) {
+    const float inv = 1.0f / l;
+    bf16_t* op = out + ((int64_t)b * CA + myq) * H * D + (int64_t)h * D;
+#pragma unroll
+    for (int dt = 0; dt < D / 16; ++dt)
+      store4(op + dt * 16 + 4 * g, make_float4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv));
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // backward, query-owned: delta = rowsum(dO * O) and dQ
 // ------------------------------------------------------------------------------------------------------------
 template <int D>
@@ -1267,6 +1397,25 @@ int attn_suffix_mfma_launch(const void* qkv_img, const int64_t* image_index, con
   else if (sh.D == 128) MAFED_SUFFIX_TILED(128);
   else MAFED_SUFFIX_TILED(256);
 #undef MAFED_SUFFIX_TILED
+  return MAFED_OK;
+}
+
+int attn_cand_mfma_launch(const void* qkv_pre, const void* qkv_cand, const CandShape& sh, const float* rc, const float* rs, const int64_t* am,
+                          void* out, hipStream_t st) {
+  const int CA = sh.C * sh.A;
+  dim3 grid((CA + 63) / 64, sh.H, sh.B), block(256);
+  const size_t tb = (size_t)2 * 64 * sh.D * 2;
+  const double flops = 4.0 * sh.D * ((double)CA * sh.S0 + (double)CA * (sh.A + 1) / 2.0) * sh.H * sh.B;
+#define MAFED_CAND_TILED(DD)                                                                                                      \
+  do {                                                                                                                            \
+    set_lds_attr(attn_cand_mfma_kernel<DD>, tb);                                                                                  \
+    launch(K_ATTN_FWD, flops, attn_cand_mfma_kernel<DD>, grid, block, tb, st, (const bf16_t*)qkv_pre, (const bf16_t*)qkv_cand, sh, rc, rs, am, \
+           (bf16_t*)out);                                                                                                         \
+  } while (0)
+  if (sh.D == 64) MAFED_CAND_TILED(64);
+  else if (sh.D == 128) MAFED_CAND_TILED(128);
+  else MAFED_CAND_TILED(256);
+#undef MAFED_CAND_TILED
   return MAFED_OK;
 }
 

@@ -1,4 +1,5 @@
-"""Generation for ``VLPythiaForCausalLM``: greedy search, beam search and sampling, the KV-cached decode step, its cache and the captured-graph decode.
+"""Generation for ``VLPythiaForCausalLM``: greedy search, beam search, sampling and candidate scoring, the KV-cached decode step, its cache and the
+captured-graph decode.
 ``GenerationMixin`` is a base class of the model (mafed_amd/model.py, which this module does not import): it uses the model's engine
 forward, parameter records and rotary tables, and the state ``fused_decode`` / ``beam_trace`` / ``_decode_graphs`` its ``__init__`` declares."""
 from __future__ import annotations
@@ -256,6 +257,114 @@ class GenerationMixin:
             out += (logprobs,)
         return out[0] if len(out) == 1 else out
 
+    # ---- candidate scoring (DESIGN.md section 4c'''') -------------------------------------------------------------------
+    @torch.no_grad()
+    def score(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
+              patch_embeddings: Optional[torch.Tensor] = None, candidate_ids: Optional[torch.Tensor] = None,
+              candidate_mask: Optional[torch.Tensor] = None, normalize: str = "sum", use_cache: bool = True,
+              image_index: Optional[torch.Tensor] = None, return_token_logprobs: bool = False):
+        """Log-likelihood of given answers: ``candidate_ids`` int64 [B, C, A] holds C candidate continuations of A tokens for each of the B
+        prompts, ``candidate_mask`` int64 [B, C, A] their RIGHT-padded lengths (ones then zeros; None = all ones).
+
+            score[b, c] = sum_j mask[b, c, j] * log p(cand[b, c, j] | image b, prompt b, cand[b, c, :j])
+
+        -> fp32 [B, C]; ``normalize="mean"`` divides by the candidate's token count; a candidate without a token scores -inf, so it loses
+        every ranking.  ``return_token_logprobs`` adds the fp32 [B, C, A] terms of the sum (0 at masked positions).  Token 0 is scored
+        from the prompt's last position, token j >= 1 from candidate row j - 1.
+
+        For a sample whose text is [question | answer] with the answer labelled, ``-score(normalize="mean")`` of (question, answer) is the
+        reference's per-sample masked-mean cross-entropy, and its batch mean is ``compute_loss`` (mafed/model/vl_pythia.py:64-96) =
+        ``model(**batch).loss`` -- without a training forward, and per sample (the forgetting signal of a replay memory).
+
+        ``use_cache=False`` is the literal computation: the B * C sequences [image | prompt | candidate] through the engine forward, the
+        image rows and the prompt C times over.  ``use_cache=True`` (default) prefills each prompt ONCE (``image_index``: each image once,
+        ``_prefill_shared_rows``), keeps every layer's fused-QKV rows as the prefix, and moves only the B * C * A candidate rows through the
+        stack; they attend [prefix of their prompt | own earlier tokens] through ``ops.attn_cand_fwd``.  A is right-padded internally to
+        ``padded_candidate_len`` (exact: padded rows come last in their candidate and no other candidate sees them), and the last row of
+        a candidate, which predicts nothing, skips the final LayerNorm and the head.  Log-probabilities are ``ops.token_logprob``, sums
+        ``ops.score_reduce``.  One host read checks the mask and the token range (one more for ``image_index``); none after that.
+        ``model.prefill_trace`` (a list) receives {"prefix_rows", "candidate_rows"}: the rows that went through the stack."""
+        if normalize not in ("sum", "mean"):
+            raise ValueError(f"normalize must be 'sum' or 'mean', got {normalize!r}")
+        if input_ids is None or (pixel_values is None and patch_embeddings is None):
+            raise ValueError("score needs input_ids and pixel_values / patch_embeddings")
+        feats, ids, am, _ = self._generate_inputs(input_ids, attention_mask, pixel_values, patch_embeddings, None, None)
+        cfg, dev = self.config, ids.device
+        B, T = ids.shape
+        cand = candidate_ids
+        if not isinstance(cand, torch.Tensor) or cand.dtype != torch.int64 or cand.dim() != 3 or cand.shape[0] != B or cand.shape[1] < 1 or cand.shape[2] < 1:
+            got = (tuple(cand.shape), cand.dtype) if isinstance(cand, torch.Tensor) else type(cand).__name__
+            raise ValueError(f"candidate_ids must be an int64 tensor of shape [{B}, C >= 1, A >= 1], got {got}")
+        if T < 1:
+            raise ValueError("score needs at least one prompt position (token 0 is scored from the prompt's last position)")
+        _, C, A = cand.shape
+        cand = cand.to(dev).contiguous()
+        mask = candidate_mask
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype != torch.int64 or tuple(mask.shape) != (B, C, A):
+                got = (tuple(mask.shape), mask.dtype) if isinstance(mask, torch.Tensor) else type(mask).__name__
+                raise ValueError(f"candidate_mask must be an int64 tensor of shape [{B}, {C}, {A}], got {got}")
+            mask = mask.to(dev).contiguous()
+            keep = mask != 0
+            tok, tgt = cand * keep, torch.where(keep, cand, -1)   # embedding ids (masked: any valid id) and targets (masked: < 0 -> 0)
+            not_right_padded = ((mask != 0) & (mask != 1)).any() | (mask[..., 1:] > mask[..., :-1]).any()
+        else:
+            tok = tgt = cand
+            not_right_padded = torch.zeros((), dtype=torch.bool, device=dev)
+        bad = torch.stack([not_right_padded, ((tok < 0) | (tok >= cfg.vocab_size)).any()]).tolist()   # the one host read
+        if bad[0]:
+            raise ValueError("candidate_mask must be right-padded: ones, then zeros, along the last dimension")
+        if bad[1]:
+            raise ValueError(f"candidate_ids must lie in [0, {cfg.vocab_size}) wherever candidate_mask is set")
+        feats, image_index = self._pair_images(feats, image_index, B, use_cache)
+        BC, V = B * C, cfg.vocab_size
+        if not use_cache:
+            ids_x = torch.cat([ids.repeat_interleave(C, 0), tok.view(BC, A)], dim=1)
+            am_x = torch.cat([am.repeat_interleave(C, 0), torch.ones((BC, A), dtype=torch.int64, device=dev)], dim=1)
+            st = self._engine_forward(feats.repeat_interleave(C, 0), ids_x, am_x, None, False, train=False)
+            # text row T - 1 + j of sequence (b, c) predicts candidate token j
+            rows = torch.arange(BC, device=dev)[:, None] * (T + A) + (T - 1) + torch.arange(A, device=dev)[None, :]
+            tlp = ops.token_logprob(st["logits"].view(BC * (T + A), V), tgt, rows.to(torch.int32).contiguous())
+        else:
+            tlp, trace = self._score_shared(feats, image_index, ids, am, tok, tgt)
+            if self.prefill_trace is not None:
+                self.prefill_trace.append(trace)
+        scores = ops.score_reduce(tlp, mask, normalize == "mean")
+        return (scores, tlp) if return_token_logprobs else scores
+
+    def _score_shared(self, feats, image_index, ids, am, tok, tgt) -> Tuple[torch.Tensor, dict]:
+        """``score``'s shared path -> (token log-probabilities fp32 [B, C, A], the trace record)."""
+        cfg, cd = self.config, self.compute_dtype
+        P, h, H, D, L = cfg.num_vision_tokens, cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim, cfg.num_hidden_layers
+        (B, T), (_, C, A), dev = ids.shape, tok.shape, ids.device
+        S0, BC, rot = P + T, B * C, cfg.rotary_ndims
+        if image_index is None:
+            store = self._prefix_store(B, T)
+            first = self._engine_forward(feats, ids, am, None, False, train=False, qkv_out=list(store.unbind(0)), last_only=True)["logits"][:, -1, :]
+            prefix_rows = B * S0
+        else:
+            store, first, _ = self._prefill_shared_rows(feats, image_index, ids, am)
+            prefix_rows = feats.shape[0] * P + B * T
+        # token 0 of all C candidates of a prompt reads the prompt's one logits row
+        row0 = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(C)
+        lp0 = ops.token_logprob(first, tgt[:, :, 0].contiguous(), row0)
+        if A == 1:   # nothing to condition on: no candidate row enters the stack
+            return lp0.view(B, C, 1), {"prefix_rows": prefix_rows, "candidate_rows": 0}
+        A_run = self.padded_candidate_len(BC, A)
+        if A_run != A:
+            tok = torch.cat([tok, torch.zeros((B, C, A_run - A), dtype=torch.int64, device=dev)], dim=2)
+        cos, sin = self.rotary_tables(S0 + A_run)
+        wts, pars = self._tensors(0), self._tensors(1)
+        Wo, Po = wts.outer, pars.outer
+        x = Po.embed_in.index_select(0, tok.reshape(-1))   # fp32 residual rows [B*C*A_run, h]
+        for i in range(L):
+            x = self._infer_layer(wts, pars, i, x, lambda qkv: ops.attn_cand_fwd(store[i], S0, qkv, C, A_run, B, H, D, rot, cos, sin, am))
+        # candidate row j predicts token j + 1: rows 0 .. A - 2 of every candidate go through the final LayerNorm and the head
+        xh = x.view(BC, A_run, h)[:, :A - 1, :].reshape(BC * (A - 1), h)
+        lnf, _, _, _ = ops.layernorm_fwd(xh, Po.final_ln_w, Po.final_ln_b, None, None, cfg.layer_norm_eps, cd, save_stats=False)
+        lp1 = ops.token_logprob(ops.gemm(lnf, Wo.embed_out, False, True), tgt[:, :, 1:].contiguous())
+        return torch.cat([lp0.view(B, C, 1), lp1], dim=2), {"prefix_rows": prefix_rows, "candidate_rows": BC * A_run}
+
     def _generate_inputs(self, input_ids, attention_mask, pixel_values, patch_embeddings, pad_token_id, eos_token_id):
         """-> (vision features, token ids, attention mask) on the model's device and the effective ``pad_token_id``."""
         dev = self.flat_params.device
@@ -304,12 +413,36 @@ class GenerationMixin:
         cache = _DecodeCache(self, list(store.unbind(0)), B, st["S"], cap, am, fused=self.fused_decode, prefix_storage=store, beams=beams)
         return cache, st["logits"][:, -1, :]
 
+    def _infer_layer(self, wts, pars, i: int, x: torch.Tensor, attend, qkv_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Layer i over inference-only rows, ``_engine_forward``'s body without its records: LN pair, fused-QKV product (into ``qkv_out`` when
+        given), ``attend(qkv)`` -> the attention output of these rows, dense, MLP and the parallel residual -> the next fp32 residual rows.
+        Shared by the image, text and candidate passes of ``_prefill_shared_rows`` and ``score``."""
+        cfg, cd = self.config, self.compute_dtype
+        w, p = wts.layers[i], pars.layers[i]
+        ln1, ln2, _, _ = ops.layernorm_fwd(x, p.ln1_w, p.ln1_b, p.ln2_w, p.ln2_b, cfg.layer_norm_eps, cd, save_stats=False)
+        qkv = ops.gemm(ln1, w.qkv_w, False, True, bias=p.qkv_b, out=qkv_out)
+        attn = ops.gemm(attend(qkv), w.dense_w, False, True, bias=p.dense_b, out_dtype=cd)
+        a = ops.gemm(ln2, w.fc1_w, False, True, bias=p.fc1_b, epilogue=EPI_GELU)
+        return ops.gemm(a, w.fc2_w, False, True, bias=p.fc2_b, out_dtype=torch.float32, res1=attn, res2=x)
+
     def _prefill_shared(self, feats, image_index, ids, am, cap: int, beams: int = 1) -> Tuple["_DecodeCache", torch.Tensor]:
-        """``_prefill`` for B prompts over the N images of ``feats`` (DESIGN.md section 4c'''): the prompt is [image | text], fully causal with
+        """``_prefill`` for B prompts over the N images of ``feats`` (DESIGN.md section 4c'''): ``_prefill_shared_rows``, then the decode cache over
+        the assembled prefix (which rotates the prefix keys as ever)."""
+        store, logits, record = self._prefill_shared_rows(feats, image_index, ids, am)
+        if self.prefill_trace is not None:   # tests / tools: the row counts that went through the stack
+            self.prefill_trace.append(record)
+        B, T = ids.shape
+        cache = _DecodeCache(self, list(store.unbind(0)), B, self.config.num_vision_tokens + T, cap, am, fused=self.fused_decode,
+                             prefix_storage=store, beams=beams)
+        return cache, logits
+
+    def _prefill_shared_rows(self, feats, image_index, ids, am) -> Tuple[torch.Tensor, torch.Tensor, dict]:
+        """The prompt rows of B prompts over the N images of ``feats`` -> (prefix store [L, B*S0, 3h] with un-rotated keys, the last position's
+        logits [B, V], the trace record).  The prompt is [image | text], fully causal with
         arange positions, so the image rows of every layer depend on the image alone.  They go through the stack once per image (their
         fused-QKV rows into an image store [L, N*P, 3h]; the last layer stops there, nothing reads its image rows), the text rows once
         per prompt (text store [L, B*T, 3h]), attending [image image_index[b] | own text] through ``ops.attn_suffix_fwd``; one gather then
-        lays the two stores out as the [L, B*S0, 3h] prefix the decode cache takes.  The layer body is ``_engine_forward``'s, inference only."""
+        lays the two stores out as the [L, B*S0, 3h] prefix the decode cache takes.  The layer body is ``_infer_layer``."""
         if not self.flat_params.is_cuda:
             raise RuntimeError("mafed_amd runs on the GPU only (no CPU fallback); move the model with .cuda()")
         cfg, cd = self.config, self.compute_dtype
@@ -330,12 +463,6 @@ class GenerationMixin:
         img_store = torch.empty((L, N * P, 3 * h), dtype=cd, device=dev)
         txt_store = torch.empty((L, B * T, 3 * h), dtype=cd, device=dev)
 
-        def mlp_and_residuals(i, x, ao, ln2):
-            w, p = wts.layers[i], pars.layers[i]
-            attn = ops.gemm(ao, w.dense_w, False, True, bias=p.dense_b, out_dtype=cd)
-            a = ops.gemm(ln2, w.fc1_w, False, True, bias=p.fc1_b, epilogue=EPI_GELU)
-            return ops.gemm(a, w.fc2_w, False, True, bias=p.fc2_b, out_dtype=torch.float32, res1=attn, res2=x)
-
         # image pass, N * P rows: projector, then the layers over the image alone (S = P; the one-column mask of ones makes the last image
         # key a valid "text" key of the full attention kernels, which take T >= 1 through this wrapper)
         f2 = feats.reshape(N * P, cfg.vision_hidden_size)
@@ -347,32 +474,23 @@ class GenerationMixin:
         x = img if img.dtype == torch.float32 else ops.cast(img, torch.float32)   # fp32 residual stream
         ones = torch.ones((N, 1), dtype=torch.int64, device=dev)
         for i in range(L):
-            w, p = wts.layers[i], pars.layers[i]
             if i == L - 1:
+                w, p = wts.layers[i], pars.layers[i]
                 ln1, _, _, _ = ops.layernorm_fwd(x, p.ln1_w, p.ln1_b, None, None, eps, cd, save_stats=False)
                 ops.gemm(ln1, w.qkv_w, False, True, bias=p.qkv_b, out=img_store[i])
                 break
-            ln1, ln2, _, _ = ops.layernorm_fwd(x, p.ln1_w, p.ln1_b, p.ln2_w, p.ln2_b, eps, cd, save_stats=False)
-            qkv = ops.gemm(ln1, w.qkv_w, False, True, bias=p.qkv_b, out=img_store[i])
-            ao, _ = ops.attn_fwd(qkv, N, P, H, D, rot, cos, sin, ones)
-            x = mlp_and_residuals(i, x, ao, ln2)
+            x = self._infer_layer(wts, pars, i, x, lambda qkv: ops.attn_fwd(qkv, N, P, H, D, rot, cos, sin, ones)[0], qkv_out=img_store[i])
         # text pass, B * T rows
         x = Po.embed_in.index_select(0, ids.reshape(-1))
         for i in range(L):
-            w, p = wts.layers[i], pars.layers[i]
-            ln1, ln2, _, _ = ops.layernorm_fwd(x, p.ln1_w, p.ln1_b, p.ln2_w, p.ln2_b, eps, cd, save_stats=False)
-            qkv = ops.gemm(ln1, w.qkv_w, False, True, bias=p.qkv_b, out=txt_store[i])
-            ao = ops.attn_suffix_fwd(img_store[i], image_index, N, P, qkv, T, B, H, D, rot, cos, sin, am)
-            x = mlp_and_residuals(i, x, ao, ln2)
+            x = self._infer_layer(wts, pars, i, x, lambda qkv: ops.attn_suffix_fwd(img_store[i], image_index, N, P, qkv, T, B, H, D, rot, cos, sin, am),
+                                  qkv_out=txt_store[i])
         xl = x.view(B, T, h)[:, -1, :].contiguous()
         lnl, _, _, _ = ops.layernorm_fwd(xl, Po.final_ln_w, Po.final_ln_b, None, None, eps, cd, save_stats=False)
         logits = ops.gemm(lnl, Wo.embed_out, False, True)
-        # prefix assembly: [image of the prompt | its text] per layer, one launch for all of them; the cache rotates the keys as ever
+        # prefix assembly: [image of the prompt | its text] per layer, one launch for all of them
         store = ops.prefix_gather(img_store, txt_store, image_index, B, P, T, out=self._prefix_store(B, T))
-        if self.prefill_trace is not None:   # tests / tools: the row counts that went through the stack
-            self.prefill_trace.append({"image_store": tuple(img_store.shape), "text_store": tuple(txt_store.shape), "prefix": tuple(store.shape)})
-        cache = _DecodeCache(self, list(store.unbind(0)), B, S0, cap, am, fused=self.fused_decode, prefix_storage=store, beams=beams)
-        return cache, logits
+        return store, logits, {"image_store": tuple(img_store.shape), "text_store": tuple(txt_store.shape), "prefix": tuple(store.shape)}
 
     def _beam_search(self, feats, ids, am, pad_token_id, eos_token_id, k: int, max_new: int, use_cache: bool, length_penalty: float,
                      early_stopping, nrs: int, return_dict: bool, image_index: Optional[torch.Tensor] = None):

@@ -552,6 +552,11 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
         """The text length a [B, T] batch runs at under this model's ``text_bucket`` (bucket_text_len)."""
         return bucket_text_len(self.text_bucket, int(B), self.config.num_vision_tokens, int(T))
 
+    def padded_candidate_len(self, n: int, A: int) -> int:
+        """The length n candidates of A tokens run at in ``score`` under ``text_bucket``: the policy of ``padded_text_len`` on rows without an
+        image part (``"auto"``: n * A' a multiple of TEXT_BUCKET_ROWS when that takes at most TEXT_BUCKET_MAX_PAD positions)."""
+        return bucket_text_len(self.text_bucket, int(n), 0, int(A))
+
     def pad_text_batch(self, input_ids, attention_mask, labels=None):
         """(ids, mask, labels) of a [B, T] batch on this model's device at ``padded_text_len(B, T)``: one launch, or the tensors themselves
         when nothing is appended.  What every engine entry does with its batch; a caller that feeds the same batch to two models (student

@@ -431,6 +431,47 @@ def prefix_gather(qkv_img: torch.Tensor, qkv_txt: torch.Tensor, image_index: Opt
     return out
 
 
+def attn_cand_fwd(qkv_prefix: torch.Tensor, S0: int, qkv_cand: torch.Tensor, C: int, A: int, B: int, H: int, D: int, rot: int, cos, sin,
+                  attention_mask: torch.Tensor) -> torch.Tensor:
+    """Attention of the A rows of each of the C candidates of B prompts over [prefix b | own earlier rows] (mafed_attn_cand_fwd) = rows
+    S0 .. S0+A-1 of ``attn_fwd`` on every assembled [prefix b | candidate (b, c)].  ``qkv_prefix`` [B*S0, 3*H*D] (keys un-rotated),
+    ``qkv_cand`` [B*C*A, 3*H*D], ``attention_mask`` [B, T] of the prefix text.  -> [B*C*A, H*D]"""
+    assert qkv_prefix.is_contiguous() and qkv_cand.is_contiguous() and qkv_prefix.dtype == qkv_cand.dtype
+    assert qkv_prefix.numel() == B * S0 * 3 * H * D and qkv_cand.numel() == B * C * A * 3 * H * D
+    assert attention_mask.dim() == 2 and attention_mask.shape[0] == B and attention_mask.dtype == torch.int64 and attention_mask.is_contiguous()
+    assert cos.shape[0] >= S0 + A
+    out = torch.empty((B * C * A, H * D), dtype=qkv_cand.dtype, device=qkv_cand.device)
+    check(_lib.load().mafed_attn_cand_fwd(_ptr(qkv_prefix), S0, _ptr(qkv_cand), C, A, _dt(qkv_cand), B, H, D, rot, _ptr(cos), _ptr(sin),
+                                          _ptr(attention_mask), attention_mask.shape[1], _ptr(out), _stream()), "mafed_attn_cand_fwd")
+    return out
+
+
+def token_logprob(logits: torch.Tensor, target: torch.Tensor, logits_row: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``logits[row(r), target[r]] - logsumexp(logits[row(r)])`` in fp32 (mafed_token_logprob).  ``logits`` [N, V] fp32 / bf16 with unit
+    column stride (any row stride), ``target`` int64 of any shape (R elements; < 0 gives 0), ``logits_row`` int32 [R] with values in
+    [0, N) naming the logits row of every output (None: row r, R <= N).  -> fp32, the shape of ``target``"""
+    N, V = logits.shape
+    R = target.numel()
+    assert logits.stride(1) == 1 and target.dtype == torch.int64 and target.is_contiguous()
+    assert (R <= N) if logits_row is None else (logits_row.dtype == torch.int32 and logits_row.numel() == R and logits_row.is_contiguous())
+    out = torch.empty(target.shape, dtype=torch.float32, device=logits.device)
+    check(_lib.load().mafed_token_logprob(_ptr(logits), _dt(logits), logits.stride(0), _ptr(logits_row), _ptr(target), R, V, _ptr(out), _stream()),
+          "mafed_token_logprob")
+    return out
+
+
+def score_reduce(token_logprobs: torch.Tensor, mask: Optional[torch.Tensor], mean: bool) -> torch.Tensor:
+    """Per candidate, the sum (``mean``: the mean) of its tokens' log-probabilities over ``mask`` != 0; -inf without a token
+    (mafed_score_reduce).  ``token_logprobs`` fp32 [..., A], ``mask`` int64 of the same shape or None.  -> fp32 [...]"""
+    A = token_logprobs.shape[-1]
+    R = token_logprobs.numel() // A
+    assert token_logprobs.dtype == torch.float32 and token_logprobs.is_contiguous()
+    assert mask is None or (mask.dtype == torch.int64 and mask.shape == token_logprobs.shape and mask.is_contiguous())
+    out = torch.empty(token_logprobs.shape[:-1], dtype=torch.float32, device=token_logprobs.device)
+    check(_lib.load().mafed_score_reduce(_ptr(token_logprobs), _ptr(mask), R, A, int(bool(mean)), _ptr(out), _stream()), "mafed_score_reduce")
+    return out
+
+
 def beam_candidates(logits: torch.Tensor, score: torch.Tensor, B: int, k: int, out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None):
     """Per sample, the top 2k of ``log_softmax(logits[row]) + score[row]`` over its kin = rows / B rows (mafed_beam_candidates).
     logits [B*kin, V] fp32 / bf16 (unit column stride), score fp32 [B*kin] -> (score fp32 [B,2k], token int64 [B,2k], parent int32 [B,2k]),
