@@ -293,3 +293,171 @@ def distill_combine_fp64(sums, layer_coeff, mode, lang_weight=0.5, lang_vec=None
     per_layer = lw * lang + vw * vis
     inject = torch.stack([c * lw / s[:, 2], c * vw / s[:, 3], torch.zeros_like(c), torch.zeros_like(c)], dim=1)
     return (c * per_layer).sum(), per_layer, torch.stack([lang, vis], dim=1), inject
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# fp64 oracle of the whole training step and of the optimiser sequence (cross-entropy path, backward sweep, AdamW)
+# ---------------------------------------------------------------------------------------------------------------
+# Bounds of the whole-step parity checks (tests/test_gpu_model.py), each the worst native-against-float64 relative error per tensor
+# over all of its cases, measured on an MI355X, times 3 to 10, and guarded on the CPU by tests/test_step_guard.py: a mutated fp64
+# oracle (tanh GELU, rotary base 10500, LayerNorm eps 1e-6, key padding ignored, one label dropped, rotary_pct 0.5; for the updates
+# AdamW eps 1e-8, beta2 0.999, clip at 2.2, weight decay 0.02) must fail the same comparator by GUARD_MARGIN times the bound.
+# (measured worst case on gfx950 in brackets)
+STEP_RTOL = 1e-5              # fp32 native forward + backward vs fp64 oracle: loss, text logits, hidden states, every gradient
+#                               [1.7e-6: ev, grad layers.0.mlp.dense_h_to_4h.bias; guard ceiling 4.4e-5: rotary base 10500 on t64 and ev]
+STEP_RTOL_BF16 = 5e-2         # bf16 step vs fp64 oracle: loss, hidden states, every gradient
+#                               [1.2e-2: t256, grad final_layer_norm.weight; guard ceiling 8.4e-2: key padding ignored on m64]
+UPDATE_RTOL = 1e-3            # fp32 Trainer, 8 optimiser steps, vs fp64 RefTrainer: final - initial per parameter tensor
+#                               [2.4e-4: embed_in.weight, rows of rare tokens; next 7.6e-5; guard ceiling 4.7e-3: weight decay 0.02]
+
+STEP_EDGE = {
+    # S = 83 crosses the 64-row attention tile and is no multiple of 16; sample 2 has no label at all (0 / clamp(0, 1e-13))
+    "e83": dict(h=128, H=2, L=2, V=384, P=70, T=13, B=3, Dv=48, seed=83),
+    # head size 128; V a multiple of 4 and of nothing larger that matters
+    "e128": dict(h=256, H=2, L=2, V=260, P=40, T=24, B=2, Dv=32, seed=128),
+    # three trips of the CE kernels' 1024-column loop with a short last one: the online log-sum-exp rescale
+    "ev": dict(h=128, H=2, L=2, V=2052, P=8, T=6, B=2, Dv=32, seed=2052),
+}
+STEP_CASES = list(TINY) + list(STEP_EDGE)
+
+
+def step_case(name):
+    """(cfg, weights, batch) of a whole-step parity case: the golden inputs of a TINY config, or a STEP_EDGE config built from the
+    oracle's deterministic generators (left padding from make_batch)."""
+    if name in TINY:
+        cfg, sd, _, batch, _ = golden_setup(name)
+        return cfg, sd, batch
+    t = STEP_EDGE[name]
+    cfg = R.RefConfig(vocab_size=t["V"], hidden_size=t["h"], num_hidden_layers=t["L"], num_attention_heads=t["H"],
+                      intermediate_size=4 * t["h"], vision_hidden_size=t["Dv"], num_vision_tokens=t["P"])
+    sd = R.init_weights(cfg, seed=t["seed"], bias_std=0.02, ln_jitter=0.05)
+    batch = R.make_batch(cfg, t["B"], t["T"], seed=t["seed"] + 1, pad=True, n_answer=3)
+    if name == "e83":
+        batch["labels"][2] = -100
+    return cfg, sd, batch
+
+
+def step_fp64(cfg, sd, batch):
+    """fp64 oracle of one forward + backward: {"loss", "logits" [B, T, V] (text positions), "hidden" (all L + 1), "grads" {name:
+    tensor}, "num_heads" (layout of the fused biases)}.  A parameter that the loss does not reach gets exact zeros.  (The oracle keeps the reference's fp32 softmax and
+    cross-entropy, and fp32 rotary tables: its own floor is near 1e-7.)"""
+    params = {k: v.double().clone().requires_grad_(True) for k, v in sd.items()}
+    b64 = dict(batch)
+    b64["patch_embeddings"] = batch["patch_embeddings"].double()
+    out = R.forward(params, b64, cfg)
+    out.loss.backward()
+    T = batch["input_ids"].shape[1]
+    grads = {k: (p.grad.detach().clone() if p.grad is not None else torch.zeros_like(p.detach())) for k, p in params.items()}
+    return {"loss": float(out.loss.detach()), "logits": out.logits[:, -T:].detach().clone(),
+            "hidden": [x.detach().clone() for x in out.hidden_states], "grads": grads, "num_heads": cfg.num_attention_heads}
+
+
+_STEP_REF = {}
+
+
+def step_ref(name):
+    """step_fp64 of step_case(name), computed once and shared (read only)."""
+    if name not in _STEP_REF:
+        _STEP_REF[name] = step_fp64(*step_case(name))
+    return _STEP_REF[name]
+
+
+def key_bias_mask(n, num_heads):
+    """The K third of a fused query_key_value bias [3 h] (rows interleaved per head as [H, {q, k, v}, D]) as a boolean mask."""
+    m = np.zeros((num_heads, 3, n // (3 * num_heads)), bool)
+    m[:, 1] = True
+    return m.reshape(-1)
+
+
+def step_parity_errors(got, ref, grad_mul=1.0):
+    """{quantity: relative error (rel_err)} of ``got`` (layout of step_fp64; "logits" may be absent) against ``ref``: the loss, the
+    text logits, every hidden state and every parameter gradient tensor against ``grad_mul`` times the reference's.  The key third
+    of a query_key_value bias gradient is mathematically zero (softmax does not see a shift of its row) and rounding noise near 1e-8
+    in any implementation: it is judged against the scale of the whole bias gradient, the rest of the bias against its own."""
+    errs = {"loss": rel_err(got["loss"], ref["loss"])}
+    if "logits" in got:
+        errs["logits"] = rel_err(got["logits"], ref["logits"])
+    assert len(got["hidden"]) == len(ref["hidden"]), (len(got["hidden"]), len(ref["hidden"]))
+    for i, (a, b) in enumerate(zip(got["hidden"], ref["hidden"])):
+        errs[f"hidden {i}"] = rel_err(a, b)
+    assert set(got["grads"]) == set(ref["grads"])
+    for k, r in ref["grads"].items():
+        a, r = _f64(got["grads"][k]), grad_mul * _f64(r)
+        if k.endswith("query_key_value.bias"):
+            km = key_bias_mask(r.size, ref["num_heads"])
+            errs[f"grad {k} [q, v]"] = rel_err(a[~km], r[~km])
+            errs[f"grad {k} [k]"] = rel_err(a[km], r[km], scale=r)
+        else:
+            errs[f"grad {k}"] = rel_err(a, r)
+    return errs
+
+
+def check_step_parity(got, ref, rtol, what="", grad_mul=1.0):
+    """Every quantity of step_parity_errors within rtol (exact zeros where the reference is exactly zero); the failure names each
+    quantity above the bound.  Returns the largest."""
+    errs = step_parity_errors(got, ref, grad_mul)
+    worst = max(errs, key=errs.get)
+    print(f"[rel] {what}: worst {worst} {errs[worst]:.3e} (bound {rtol:.1e}); loss {errs['loss']:.3e}")
+    bad = {k: v for k, v in errs.items() if not v <= rtol}
+    assert not bad, f"{what}: relative errors above {rtol:.1e}: " + ", ".join(f"{k} {v:.3e}" for k, v in bad.items())
+    return errs[worst]
+
+
+# the optimiser-sequence case: t64, task 1, 16 micro-batches = 8 optimiser steps, the first at lr 0 (warm-up 1)
+TRAINER_CASE = dict(name="t64", seed=23, n_batches=16, accumulate=2, replay_interval=4, warmup=1, total_steps=20, lr=1e-3,
+                    betas=(0.9, 0.98), eps=1e-6, weight_decay=0.01, grad_clip=2.0, gamma=0.5)
+
+
+def trainer_case():
+    """(cfg, student weights, teacher weights, [(batch, memory batch)] per micro-batch) of TRAINER_CASE."""
+    c = TRAINER_CASE
+    cfg, t = tiny_cfg(c["name"]), TINY[c["name"]]
+    sd = R.init_weights(cfg, seed=c["seed"], bias_std=0.02, ln_jitter=0.05)
+    tsd = R.perturb(sd, seed=c["seed"] + 100, std=5e-3)
+    batches = [(R.make_batch(cfg, t["B"], t["T"], seed=c["seed"] + 10 + i, pad=True, n_answer=3),
+                R.make_batch(cfg, t["B"], t["T"], seed=c["seed"] + 50 + i, pad=True, n_answer=3)) for i in range(c["n_batches"])]
+    return cfg, sd, tsd, batches
+
+
+def trainer_fp64(**overrides):
+    """TRAINER_CASE through the oracle's RefTrainer in float64 (MAFED balanced / discounted, both coefficients 1): {"loss" per
+    micro-batch, "grad_norm", "lr" per optimiser step, "update" {name: final - initial}}.  ``overrides`` replace RefTrainer fields
+    (the guard's mutations)."""
+    c = TRAINER_CASE
+    cfg, sd, tsd, batches = trainer_case()
+    kw = dict(lr=c["lr"], betas=c["betas"], eps=c["eps"], weight_decay=c["weight_decay"], grad_clip=c["grad_clip"],
+              accumulate=c["accumulate"], replay_interval=c["replay_interval"], warmup_steps=c["warmup"], total_steps=c["total_steps"],
+              task_id=1, teacher_sd={k: v.double() for k, v in tsd.items()},
+              spec=R.DistillSpec(modality="balanced", layer_strategy="discounted", gamma=c["gamma"], distillation_coeff=1.0, replay_coeff=1.0))
+    kw.update(overrides)
+    tr = R.RefTrainer(cfg, {k: v.double() for k, v in sd.items()}, **kw)
+    f64 = lambda b: dict(b, patch_embeddings=b["patch_embeddings"].double())
+    recs = [tr.step(f64(b), i, f64(m)) for i, (b, m) in enumerate(batches)]
+    return {"loss": np.array([r["loss"] for r in recs]), "grad_norm": np.array([r["grad_norm"] for r in recs if "grad_norm" in r]),
+            "lr": np.array([r["lr"] for r in recs if "lr" in r]),
+            "update": {k: tr.params[k].detach() - sd[k].double() for k in sd}}
+
+
+def update_errors(got, ref, num_heads):
+    """{parameter: rel_err of the update final - initial} of ``got`` against ``ref`` ({name: tensor}; every name of ``ref``).  The
+    key third of each query_key_value bias is left out: its gradient is rounding noise (step_parity_errors) that Adam divides by
+    eps.  That is H D of each 3 H D bias, below 0.1 % of the parameters; no other element is left out."""
+    errs = {}
+    for k, r in ref.items():
+        a, r = _f64(got[k]), _f64(r)
+        assert a.shape == r.shape, (k, a.shape, r.shape)
+        if k.endswith("query_key_value.bias"):
+            keep = ~key_bias_mask(r.size, num_heads)
+            a, r = a[keep], r[keep]
+        errs[k] = rel_err(a, r)
+    return errs
+
+
+def check_updates(got, ref, rtol, num_heads, what=""):
+    """Every update of update_errors within rtol; the failure names each parameter above the bound.  Returns the largest."""
+    errs = update_errors(got, ref, num_heads)
+    worst = max(errs, key=errs.get)
+    print(f"[rel] {what}: worst update {worst} {errs[worst]:.3e} (bound {rtol:.1e})")
+    bad = {k: v for k, v in errs.items() if not v <= rtol}
+    assert not bad, f"{what}: update errors above {rtol:.1e}: " + ", ".join(f"{k} {v:.3e}" for k, v in bad.items())
+    return errs[worst]

@@ -7,8 +7,10 @@ import pytest
 import torch
 
 from oracle import vlpythia_ref as R
-from tests.helpers import (DISTILL_RTOL, DISTILL_RTOL_BF16, DISTILL_RTOL_INJECT, G3_VARIANTS, TINY, check_distill_parity,
-                           distill_only_fp64, distill_variant_cases, g3_spec, golden_setup, load_golden, prod_case, tiny_cfg)
+from tests.helpers import (DISTILL_RTOL, DISTILL_RTOL_BF16, DISTILL_RTOL_INJECT, G3_VARIANTS, STEP_CASES, STEP_RTOL, STEP_RTOL_BF16,
+                           TINY, TRAINER_CASE, UPDATE_RTOL, assert_rel_close, check_distill_parity, check_step_parity, check_updates,
+                           distill_only_fp64, distill_variant_cases, g3_spec, golden_setup, load_golden, prod_case, step_case,
+                           step_ref, tiny_cfg, trainer_case, trainer_fp64)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -80,6 +82,41 @@ def test_forward_backward_vs_reference_golden(name):
     out2.loss.backward()
     _, norms2 = grad_norms(model, cfg)
     close(norms2, 2 * g["g2/grad_norms"], TOL, "accumulated grads")
+
+
+def native_step(model, batch, cfg, logits=True):
+    """One forward + backward on top of whatever the gradient buffer holds -> the layout of tests.helpers.step_fp64."""
+    out = model(**to_dev(batch), output_hidden_states=True, return_dict=True)
+    out.loss.backward()
+    got = {"loss": float(out.loss.detach()), "hidden": [x.detach().double().cpu() for x in out.hidden_states],
+           "grads": {k: model._g(k).detach().double().cpu() for k, _ in R.param_shapes(cfg)}}
+    if logits:
+        got["logits"] = out.logits.detach().double().cpu()
+    return got
+
+
+@pytest.mark.parametrize("name", STEP_CASES)
+def test_forward_backward_vs_fp64_oracle(name):
+    """The fp32 step against the oracle in float64, every quantity relative to its own scale (tests.helpers.check_step_parity): the
+    loss, the text logits, all L + 1 hidden states and every parameter gradient tensor; then a second forward + backward into the
+    same buffer, whose gradients must be twice the oracle's.  The four golden configs and the STEP_EDGE shapes (S = 83 with a
+    sample without labels, head size 128 with V = 260, V = 2052)."""
+    cfg, sd, batch = step_case(name)
+    ref = step_ref(name)
+    model = build_model(cfg, sd)
+    model.zero_grad()
+    check_step_parity(native_step(model, batch, cfg), ref, STEP_RTOL, f"{name}/fp32")
+    check_step_parity(native_step(model, batch, cfg), ref, STEP_RTOL, f"{name}/fp32 accumulated", grad_mul=2.0)
+
+
+@pytest.mark.parametrize("name", list(TINY))
+def test_bf16_step_vs_fp64_oracle(name):
+    """The bf16 step (bf16 MFMA GEMMs and attention, fp32 residual stream) against the oracle in float64: the loss, every hidden
+    state and every parameter gradient tensor, each relative to its own scale, at the measured STEP_RTOL_BF16."""
+    cfg, sd, batch = step_case(name)
+    model = build_model(cfg, sd, torch.bfloat16)
+    model.zero_grad()
+    check_step_parity(native_step(model, batch, cfg, logits=False), step_ref(name), STEP_RTOL_BF16, f"{name}/bf16")
 
 
 def make_fd(cfg, vname, g, teacher_model, batch, B):
@@ -306,6 +343,60 @@ def test_trainer_sequence_vs_reference_golden(pipeline):
     close(np.array(sums), g["seq/checksum"][-len(sums):], 1e-5, "parameter checksum after each optimiser step")
     tr.join()
     close(model._p("gpt_neox.final_layer_norm.weight"), g["final/gpt_neox.final_layer_norm.weight"], 1e-4, "final LN weight")
+    # the other saved tensors, as updates from the initial weights (one optimiser step at lr 0, one at lr 5e-4)
+    got, ref = {}, {}
+    for key in ("gpt_neox.layers.0.attention.query_key_value.bias", "gpt_neox.layers.1.attention.dense.weight/rows4",
+                "vision_embed_tokens.2.weight/rows4"):
+        pname, rows = (key[:-6], slice(0, 4)) if key.endswith("/rows4") else (key, slice(None))
+        got[pname] = model._p(pname)[rows].detach().cpu().double() - sd[pname][rows].double()
+        ref[pname] = torch.from_numpy(g["final/" + key]).double() - sd[pname][rows].double()
+    check_updates(got, ref, UPDATE_RTOL, cfg.num_attention_heads, "golden trainer, final - initial")
+
+
+_TRAINER_FP64 = {}
+
+
+@pytest.mark.parametrize("pipeline", [False, True])
+def test_trainer_updates_vs_fp64_oracle(pipeline):
+    """tests.helpers.TRAINER_CASE: 16 micro-batches on t64, task 1, accumulate 2, replay every 4th = 8 optimiser steps, 7 of them
+    at a non-zero lr, MAFED balanced / discounted (gamma 0.5, both coefficients 1), against the oracle's RefTrainer in float64: the
+    update final - initial of every parameter tensor (tests.helpers.check_updates), and the loss, grad-norm and lr sequences."""
+    from mafed_amd import FeatureDistillation, Trainer
+    c = TRAINER_CASE
+    if not _TRAINER_FP64:
+        _TRAINER_FP64.update(trainer_fp64())
+    ref = _TRAINER_FP64
+    cfg, sd, tsd, batches = trainer_case()
+    B = batches[0][0]["input_ids"].shape[0]
+    model, teacher = build_model(cfg, sd), build_model(cfg, tsd)
+    opts = types.SimpleNamespace(tasks=["a", "b", "c"], batch_size=B, seed=42, pin_mem=False, accumulate_grad_batches=c["accumulate"])
+    fd = FeatureDistillation(memory_size=100, opts=opts, model_type="vlpythia", num_hidden_layers=cfg.num_hidden_layers - 1,
+                             distillation_modality_weighing_strategy="balanced", distillation_layer_weighing_strategy="discounted",
+                             gamma=c["gamma"], distillation_layer=None, distillation_coeff=1.0, replay_coeff=1.0)
+    fd._update_model(teacher)
+    fd.task_id = 1
+    fd.num_vision_tokens = cfg.num_vision_tokens
+    conf = types.SimpleNamespace(accumulate_grad_batches=c["accumulate"], replay_interval=c["replay_interval"], grad_norm=c["grad_clip"],
+                                 learning_rate=c["lr"], betas=c["betas"], eps=c["eps"], weight_decay=c["weight_decay"], optim="adamw",
+                                 warmup_steps=c["warmup"], total_steps=c["total_steps"])
+    tr = Trainer(model, fd, conf, task_id=1, pipeline_optimizer=pipeline)
+    assert tr.pipeline_optimizer == pipeline
+    losses, gns, lrs = [], [], []
+    for bi, (batch, mem) in enumerate(batches):
+        fd.mem_dataloader = [to_dev(mem)]
+        rec = tr.step(to_dev(batch), bi)
+        assert (rec["branch"] == "replay") == ((bi + 1) % c["replay_interval"] == 0)
+        losses.append(float(rec["loss"]))
+        if rec["stepped"]:
+            gns.append(float(rec["grad_norm"]))
+            lrs.append(float(rec["lr"]))
+    tr.join()
+    assert len(lrs) == 8 and lrs[0] == 0.0 and min(lrs[1:]) > 0.0
+    assert_rel_close(np.array(lrs), ref["lr"], 1e-12, "lr sequence")
+    assert_rel_close(np.array(losses), ref["loss"], STEP_RTOL, "loss sequence")
+    assert_rel_close(np.array(gns), ref["grad_norm"], STEP_RTOL, "grad-norm sequence")
+    got = {k: model._p(k).detach().cpu().double() - sd[k].double() for k in sd}
+    check_updates(got, ref["update"], UPDATE_RTOL, cfg.num_attention_heads, f"trainer pipeline={pipeline}")
 
 
 def test_adaptive_weights_pass_vs_reference_golden():
