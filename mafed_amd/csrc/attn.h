@@ -25,6 +25,52 @@ __device__ __forceinline__ bool key_valid(const int64_t* __restrict__ am, int b,
   return j < P || am[(int64_t)b * T + (j - P)] != 0;
 }
 
+// One exact forward row for one wave (the parity kernels: the full forward, the suffix and the candidate attention).  key(k), for
+// k = 0 .. nk - 1 in sequence order, says where the fused q | k | v row of key k is, at which position it rotates and whether the
+// query sees it.  qrow[D] holds the rotated query, sc[nk] is scratch (both LDS of this wave); writes softmax(q K^T / sqrt D) V to
+// op[D] and returns the row's maximum and sum through m, l.
+template <typename T>
+struct AttnKey {
+  const T* row;
+  int pos;
+  bool visible;
+};
+template <typename T, typename Key>
+__device__ __forceinline__ void attn_exact_row(const float* __restrict__ qrow, float* __restrict__ sc, int nk, int D, int rot,
+                                               const float* __restrict__ rc, const float* __restrict__ rs, Key key, T* __restrict__ op,
+                                               int lane, float& m, float& l) {
+  const int half = rot >> 1;
+  const float scale = rsqrtf((float)D);
+  m = -INFINITY;
+  for (int k = lane; k < nk; k += 64) {
+    float s = -INFINITY;
+    const AttnKey<T> kk = key(k);
+    if (kk.visible) {
+      float acc = 0.f;
+      for (int d = 0; d < D; ++d)
+        acc = fmaf(qrow[d], rot_elem(kk.row + D, d, rot, rc + (int64_t)kk.pos * half, rs + (int64_t)kk.pos * half), acc);
+      s = acc * scale;
+    }
+    sc[k] = s;
+    m = fmaxf(m, s);
+  }
+  m = wave_max(m);
+  l = 0.f;
+  for (int k = lane; k < nk; k += 64) {
+    const float p = expf(sc[k] - m);
+    sc[k] = p;
+    l += p;
+  }
+  l = wave_sum(l);
+  __builtin_amdgcn_wave_barrier();
+  const float inv = 1.0f / l;
+  for (int d = lane; d < D; d += 64) {
+    float acc = 0.f;
+    for (int k = 0; k < nk; ++k) acc = fmaf(sc[k], Elem<T>::load(key(k).row + 2 * D + d), acc);
+    Elem<T>::store(op + d, acc * inv);
+  }
+}
+
 template <typename T>
 int attn_ref_fwd_launch(const void* qkv, const AttnShape& sh, const float* rc, const float* rs, const int64_t* am, void* out, float* lse,
                         hipStream_t st);

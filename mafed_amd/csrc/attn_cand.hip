@@ -5,8 +5,9 @@
 // S0 + j and sees the P image keys, the prefix text keys the padding mask leaves and keys 0 .. j of its OWN candidate -- nothing of
 // another candidate; rotary on load with position = key index (candidate key j' is at S0 + j' for every c); softmax in fp32.  Every
 // query sees key 0 (an image key: P >= 1), so no row is empty, whatever the text mask.
-// This file: the exact kernel (fp32 parity mode; bf16 head sizes without an MFMA kernel) in the form of attn_suffix_ref_kernel, one wave
-// per query row.  The bf16 MFMA kernel lives beside the forward it was cut from (attn_mfma.hip, attn_cand_mfma_kernel).
+// This file: the exact kernel (fp32 parity mode; bf16 head sizes without an MFMA kernel) one wave per query row: a shell
+// around the exact forward row it shares with attn_ref.hip (attn.h, attn_exact_row), which it tells where key k lives.  The bf16 MFMA
+// kernel lives beside the tiled forward and shares its tile step (attn_mfma.hip, attn_cand_mfma_kernel).
 #include "attn.h"
 
 namespace mafed {
@@ -30,36 +31,13 @@ __global__ __launch_bounds__(256) void attn_cand_ref_kernel(const T* __restrict_
   const int pos = S0 + j, nk = pos + 1;                                         // keys 0 .. S0 - 1 of the prefix, S0 .. S0 + j of the candidate
   for (int d = lane; d < D; d += 64) qrow[d] = rot_elem(cb + (int64_t)j * rstride, d, rot, rc + (int64_t)pos * half, rs + (int64_t)pos * half);
   __builtin_amdgcn_wave_barrier();
-  const float scale = rsqrtf((float)D);
-  float m = -INFINITY;
-  for (int k = lane; k < nk; k += 64) {
-    float s = -INFINITY;
-    if (k >= S0 || key_valid(am, b, k, P, Tt)) {
-      const T* kp = (k < S0 ? pb + (int64_t)k * rstride : cb + (int64_t)(k - S0) * rstride) + D;
-      float acc = 0.f;
-      for (int d = 0; d < D; ++d) acc = fmaf(qrow[d], rot_elem(kp, d, rot, rc + (int64_t)k * half, rs + (int64_t)k * half), acc);
-      s = acc * scale;
-    }
-    sc[k] = s;
-    m = fmaxf(m, s);
-  }
-  m = wave_max(m);
-  float l = 0.f;
-  for (int k = lane; k < nk; k += 64) {
-    const float p = expf(sc[k] - m);
-    sc[k] = p;
-    l += p;
-  }
-  l = wave_sum(l);
-  __builtin_amdgcn_wave_barrier();
-  const float inv = 1.0f / l;
-  T* op = out + ((int64_t)b * CA + r) * H * D + (int64_t)h * D;
-  for (int d = lane; d < D; d += 64) {
-    float acc = 0.f;
-    for (int k = 0; k < S0; ++k) acc = fmaf(sc[k], Elem<T>::load(pb + (int64_t)k * rstride + 2 * D + d), acc);
-    for (int k = S0; k < nk; ++k) acc = fmaf(sc[k], Elem<T>::load(cb + (int64_t)(k - S0) * rstride + 2 * D + d), acc);
-    Elem<T>::store(op + d, acc * inv);
-  }
+  float m, l;
+  attn_exact_row(qrow, sc, nk, D, rot, rc, rs,
+                 [&](int k) {
+                   return AttnKey<T>{k < S0 ? pb + (int64_t)k * rstride : cb + (int64_t)(k - S0) * rstride, k,
+                                     k >= S0 || key_valid(am, b, k, P, Tt)};
+                 },
+                 out + ((int64_t)b * CA + r) * H * D + (int64_t)h * D, lane, m, l);
 }
 
 template <typename T>

@@ -226,6 +226,87 @@ __device__ __forceinline__ bool key_ok(const int64_t* __restrict__ am, int b, in
   return key < P || (key < S && am[(int64_t)b * T + (key - P)] != 0);
 }
 
+// Stage the 64 rows r0 .. r0 + 63 of a key axis whose rows do not lie in one matrix: row(gr) says where the fused q | k | v row of
+// key gr is, at which position it rotates and whether it exists (else zeros); `off` picks the part (D: k, 2 D: v).
+struct StageRow {
+  const bf16_t* p;
+  int pos;
+  bool valid;
+};
+template <int D, bool ROT, typename Row>
+__device__ __forceinline__ void stage_rows_by(char* __restrict__ img, int tid, int r0, int off, int rot, const float* __restrict__ rc,
+                                              const float* __restrict__ rs, Row row) {
+  constexpr int CPR = D / 8;
+#pragma unroll
+  for (int c = tid; c < 64 * CPR; c += 256) {
+    const int ch = c % CPR;
+    const StageRow r = row(r0 + c / CPR);
+    uint4 v;
+    if (ROT) v = load_chunk_rot(r.p + off, ch, rot, rc, rs, r.pos, r.valid);
+    else v = r.valid ? *reinterpret_cast<const uint4*>(r.p + off + ch * 8) : make_uint4(0u, 0u, 0u, 0u);
+    *reinterpret_cast<uint4*>(img + tile_off<D>(c / CPR, ch)) = v;
+  }
+}
+
+// One 64-key tile (keys t0 .. t0 + 63, staged in kimg / vimg) of a tiled forward for the 16 queries of a wave: S^T = K Q^T, scale,
+// mask, online softmax, O += P V.  hidden(key) says that this lane's query may not see `key`; it is asked only where need_mask
+// (wave-uniform) is set.  m, l are the lane's running maximum and partial sum (l is summed over the four row groups at the end).
+template <int D, typename Hidden>
+__device__ __forceinline__ void fwd_tile_step(const char* __restrict__ kimg, const char* __restrict__ vimg, const bf16x8 (&qf)[D / 32],
+                                              f32x4 (&o)[D / 16], float& m, float& l, float scale, bool need_mask, int t0, int g, int lane,
+                                              Hidden hidden) {
+  f32x4 s[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    s[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < D / 32; ++ks) s[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_row<D>(kimg, j, ks, lane), qf[ks], s[j], 0, 0, 0);
+  }
+  float tmax = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float v = s[j][r] * scale;
+      if (need_mask) {
+        if (hidden(t0 + j * 16 + 4 * g + r)) v = -INFINITY;
+      }
+      s[j][r] = v;
+      tmax = fmaxf(tmax, v);
+    }
+  tmax = col_max(tmax);
+  const float mn = fmaxf(m, tmax);
+  const float alpha = __expf(m - mn);  // m = -inf on the first tile -> 0
+  m = mn;
+  float ps = 0.f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float p = __expf(s[j][r] - mn);
+      s[j][r] = p;
+      ps += p;
+    }
+  l = l * alpha + ps;
+#pragma unroll
+  for (int i = 0; i < D / 16; ++i) o[i] *= alpha;
+  const bf16x8 p0 = pack_acc(s[0], s[1]), p1 = pack_acc(s[2], s[3]);
+#pragma unroll
+  for (int dt = 0; dt < D / 16; ++dt) {
+    o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr<D>(vimg, dt, 0, lane), p0, o[dt], 0, 0, 0);
+    o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr<D>(vimg, dt, 1, lane), p1, o[dt], 0, 0, 0);
+  }
+}
+
+// forward epilogue: o / l (l summed over the row groups), this lane's 4 consecutive elements of every 16 of the output row `op`
+template <int D>
+__device__ __forceinline__ void store_out(bf16_t* __restrict__ op, const f32x4 (&o)[D / 16], float l, int g) {
+  const float inv = 1.0f / l;
+#pragma unroll
+  for (int dt = 0; dt < D / 16; ++dt)
+    store4(op + dt * 16 + 4 * g, make_float4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv));
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------------------
@@ -264,57 +345,13 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(const bf16_t* __rest
     stage_rows<D, 64, true>(kimg, kb, rstride, kt * 64, S, rot, rc, rs, tid);
     stage_rows<D, 64, false>(vimg, vb, rstride, kt * 64, S, rot, rc, rs, tid);
     __syncthreads();
-    f32x4 s[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      s[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < D / 32; ++ks) s[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_row<D>(kimg, j, ks, lane), qf[ks], s[j], 0, 0, 0);
-    }
     const bool need_mask = (kt == qt) || (kt * 64 + 63 >= P);
-    float tmax = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = s[j][r] * scale;
-        if (need_mask) {
-          const int key = kt * 64 + j * 16 + 4 * g + r;
-          if (key > myq || !key_ok(am, b, key, P, T, S)) v = -INFINITY;
-        }
-        s[j][r] = v;
-        tmax = fmaxf(tmax, v);
-      }
-    tmax = col_max(tmax);
-    const float mn = fmaxf(m, tmax);
-    const float alpha = __expf(m - mn);  // m = -inf on the first tile -> 0
-    m = mn;
-    float ps = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float p = __expf(s[j][r] - mn);
-        s[j][r] = p;
-        ps += p;
-      }
-    l = l * alpha + ps;
-#pragma unroll
-    for (int i = 0; i < D / 16; ++i) o[i] *= alpha;
-    const bf16x8 p0 = pack_acc(s[0], s[1]), p1 = pack_acc(s[2], s[3]);
-#pragma unroll
-    for (int dt = 0; dt < D / 16; ++dt) {
-      o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr<D>(vimg, dt, 0, lane), p0, o[dt], 0, 0, 0);
-      o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr<D>(vimg, dt, 1, lane), p1, o[dt], 0, 0, 0);
-    }
+    fwd_tile_step<D>(kimg, vimg, qf, o, m, l, scale, need_mask, kt * 64, g, lane,
+                     [&](int key) { return key > myq || !key_ok(am, b, key, P, T, S); });
   }
   l = col_sum(l);
   if (myq < S) {
-    const float inv = 1.0f / l;
-    bf16_t* op = out + ((int64_t)b * S + myq) * H * D + (int64_t)h * D;
-#pragma unroll
-    for (int dt = 0; dt < D / 16; ++dt)
-      store4(op + dt * 16 + 4 * g, make_float4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv));
+    store_out<D>(out + ((int64_t)b * S + myq) * H * D + (int64_t)h * D, o, l, g);
     if (g == 0) lse[((int64_t)b * H + h) * S + myq] = m + logf(l);
   }
 }
@@ -327,25 +364,6 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(const bf16_t* __rest
 // or wholly before a tile only helps staging it.  The last query tile and the last key tile are ragged: rows >= T / keys >=
 // P + T are staged as zeros and masked.  Every query sees key 0 (an image key: P >= 1), so no row is empty.
 // ------------------------------------------------------------------------------------------------------------
-namespace {
-template <int D, bool ROT>
-__device__ __forceinline__ void stage_rows_split(char* __restrict__ img, const bf16_t* __restrict__ ibase, const bf16_t* __restrict__ tbase,
-                                                 int64_t rstride, int r0, int P, int S, int rot, const float* __restrict__ rc,
-                                                 const float* __restrict__ rs, int tid) {
-  constexpr int CPR = D / 8;
-#pragma unroll
-  for (int c = tid; c < 64 * CPR; c += 256) {
-    const int row = c / CPR, ch = c % CPR;
-    const int gr = r0 + row;
-    const bf16_t* rowp = gr < P ? ibase + (int64_t)gr * rstride : tbase + (int64_t)(gr - P) * rstride;
-    uint4 v;
-    if (ROT) v = load_chunk_rot(rowp, ch, rot, rc, rs, gr, gr < S);
-    else v = gr < S ? *reinterpret_cast<const uint4*>(rowp + ch * 8) : make_uint4(0u, 0u, 0u, 0u);
-    *reinterpret_cast<uint4*>(img + tile_off<D>(row, ch)) = v;
-  }
-}
-}  // namespace
-
 template <int D>
 __global__ __launch_bounds__(256) void attn_suffix_mfma_kernel(const bf16_t* __restrict__ qkv_img, const int64_t* __restrict__ image_index,
                                                                const bf16_t* __restrict__ qkv_txt, SuffixShape sh, const float* __restrict__ rc,
@@ -381,62 +399,18 @@ __global__ __launch_bounds__(256) void attn_suffix_mfma_kernel(const bf16_t* __r
 
   for (int kt = 0; kt < nkt; ++kt) {
     __syncthreads();
-    stage_rows_split<D, true>(kimg, ib + D, tb + D, rstride, kt * 64, P, S, rot, rc, rs, tid);
-    stage_rows_split<D, false>(vimg, ib + 2 * D, tb + 2 * D, rstride, kt * 64, P, S, rot, rc, rs, tid);
+    // key gr of the assembled sequence: a row of the image, then of the prompt's own text
+    const auto row = [&](int gr) { return StageRow{gr < P ? ib + (int64_t)gr * rstride : tb + (int64_t)(gr - P) * rstride, gr, gr < S}; };
+    stage_rows_by<D, true>(kimg, tid, kt * 64, D, rot, rc, rs, row);
+    stage_rows_by<D, false>(vimg, tid, kt * 64, 2 * D, rot, rc, rs, row);
     __syncthreads();
     if (!active || kt * 64 > P + q0 + 15) continue;  // wave-uniform: no row of this wave sees the tile
-    f32x4 s[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      s[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < D / 32; ++ks) s[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_row<D>(kimg, j, ks, lane), qf[ks], s[j], 0, 0, 0);
-    }
     const bool need_mask = kt * 64 + 63 >= P;  // a tile of image keys only lies before every query and has no padding
-    float tmax = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = s[j][r] * scale;
-        if (need_mask) {
-          const int key = kt * 64 + j * 16 + 4 * g + r;
-          if (key > mypos || !key_ok(am, b, key, P, T, S)) v = -INFINITY;
-        }
-        s[j][r] = v;
-        tmax = fmaxf(tmax, v);
-      }
-    tmax = col_max(tmax);
-    const float mn = fmaxf(m, tmax);
-    const float alpha = __expf(m - mn);  // m = -inf on the first tile -> 0
-    m = mn;
-    float ps = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float p = __expf(s[j][r] - mn);
-        s[j][r] = p;
-        ps += p;
-      }
-    l = l * alpha + ps;
-#pragma unroll
-    for (int i = 0; i < D / 16; ++i) o[i] *= alpha;
-    const bf16x8 p0 = pack_acc(s[0], s[1]), p1 = pack_acc(s[2], s[3]);
-#pragma unroll
-    for (int dt = 0; dt < D / 16; ++dt) {
-      o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr<D>(vimg, dt, 0, lane), p0, o[dt], 0, 0, 0);
-      o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr<D>(vimg, dt, 1, lane), p1, o[dt], 0, 0, 0);
-    }
+    fwd_tile_step<D>(kimg, vimg, qf, o, m, l, scale, need_mask, kt * 64, g, lane,
+                     [&](int key) { return key > mypos || !key_ok(am, b, key, P, T, S); });
   }
   l = col_sum(l);
-  if (myq < T) {
-    const float inv = 1.0f / l;
-    bf16_t* op = out + ((int64_t)b * T + myq) * H * D + (int64_t)h * D;
-#pragma unroll
-    for (int dt = 0; dt < D / 16; ++dt)
-      store4(op + dt * 16 + 4 * g, make_float4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv));
-  }
+  if (myq < T) store_out<D>(out + ((int64_t)b * T + myq) * H * D + (int64_t)h * D, o, l, g);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -450,23 +424,6 @@ __global__ __launch_bounds__(256) void attn_suffix_mfma_kernel(const bf16_t* __r
 //     k0 (not tile-aligned) and is 1 or 2 tiles long for A <= 64; a candidate may straddle two query tiles, and A may exceed 64.
 // Rows >= C * A and keys >= S0 are staged as zeros and masked.  Key 0 is an image key (P >= 1): after the first tile no row is empty.
 // ------------------------------------------------------------------------------------------------------------
-namespace {
-template <int D, bool ROT>
-__device__ __forceinline__ void stage_rows_cand(char* __restrict__ img, const bf16_t* __restrict__ base, int64_t rstride, int r0, int CA, int A,
-                                                int S0, int rot, const float* __restrict__ rc, const float* __restrict__ rs, int tid) {
-  constexpr int CPR = D / 8;
-#pragma unroll
-  for (int c = tid; c < 64 * CPR; c += 256) {
-    const int row = c / CPR, ch = c % CPR;
-    const int gr = r0 + row;
-    uint4 v;
-    if (ROT) v = load_chunk_rot(base + (int64_t)gr * rstride, ch, rot, rc, rs, S0 + gr % A, gr < CA);
-    else v = gr < CA ? *reinterpret_cast<const uint4*>(base + (int64_t)gr * rstride + ch * 8) : make_uint4(0u, 0u, 0u, 0u);
-    *reinterpret_cast<uint4*>(img + tile_off<D>(row, ch)) = v;
-  }
-}
-}  // namespace
-
 template <int D>
 __global__ __launch_bounds__(256) void attn_cand_mfma_kernel(const bf16_t* __restrict__ qkv_pre, const bf16_t* __restrict__ qkv_cand, CandShape sh,
                                                              const float* __restrict__ rc, const float* __restrict__ rs,
@@ -510,63 +467,19 @@ __global__ __launch_bounds__(256) void attn_cand_mfma_kernel(const bf16_t* __res
       stage_rows<D, 64, true>(kimg, pb + D, rstride, t0, S0, rot, rc, rs, tid);
       stage_rows<D, 64, false>(vimg, pb + 2 * D, rstride, t0, S0, rot, rc, rs, tid);
     } else {
-      stage_rows_cand<D, true>(kimg, cb + D, rstride, t0, CA, A, S0, rot, rc, rs, tid);
-      stage_rows_cand<D, false>(vimg, cb + 2 * D, rstride, t0, CA, A, S0, rot, rc, rs, tid);
+      // flattened candidate row gr = c * A + j sits at position S0 + j
+      const auto row = [&](int gr) { return StageRow{cb + (int64_t)gr * rstride, S0 + gr % A, gr < CA}; };
+      stage_rows_by<D, true>(kimg, tid, t0, D, rot, rc, rs, row);
+      stage_rows_by<D, false>(vimg, tid, t0, 2 * D, rot, rc, rs, row);
     }
     __syncthreads();
     if (!active || (!pre && (t0 > whi || t0 + 63 < wlo))) continue;  // wave-uniform: no row of this wave sees the tile
-    f32x4 s[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      s[j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int ks = 0; ks < D / 32; ++ks) s[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_row<D>(kimg, j, ks, lane), qf[ks], s[j], 0, 0, 0);
-    }
     const bool need_mask = !pre || t0 + 63 >= P;  // a tile of image keys only has no padding
-    float tmax = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v = s[j][r] * scale;
-        if (need_mask) {
-          const int key = t0 + j * 16 + 4 * g + r;
-          if (pre ? !key_ok(am, b, key, P, T, S0) : (key < mystart || key > myq)) v = -INFINITY;
-        }
-        s[j][r] = v;
-        tmax = fmaxf(tmax, v);
-      }
-    tmax = col_max(tmax);
-    const float mn = fmaxf(m, tmax);
-    const float alpha = __expf(m - mn);  // m = -inf on the first tile -> 0
-    m = mn;
-    float ps = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float p = __expf(s[j][r] - mn);
-        s[j][r] = p;
-        ps += p;
-      }
-    l = l * alpha + ps;
-#pragma unroll
-    for (int i = 0; i < D / 16; ++i) o[i] *= alpha;
-    const bf16x8 p0 = pack_acc(s[0], s[1]), p1 = pack_acc(s[2], s[3]);
-#pragma unroll
-    for (int dt = 0; dt < D / 16; ++dt) {
-      o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr<D>(vimg, dt, 0, lane), p0, o[dt], 0, 0, 0);
-      o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_tr<D>(vimg, dt, 1, lane), p1, o[dt], 0, 0, 0);
-    }
+    fwd_tile_step<D>(kimg, vimg, qf, o, m, l, scale, need_mask, t0, g, lane,
+                     [&](int key) { return pre ? !key_ok(am, b, key, P, T, S0) : (key < mystart || key > myq); });
   }
   l = col_sum(l);
-  if (myq < CA) {
-    const float inv = 1.0f / l;
-    bf16_t* op = out + ((int64_t)b * CA + myq) * H * D + (int64_t)h * D;
-#pragma unroll
-    for (int dt = 0; dt < D / 16; ++dt)
-      store4(op + dt * 16 + 4 * g, make_float4(o[dt][0] * inv, o[dt][1] * inv, o[dt][2] * inv, o[dt][3] * inv));
-  }
+  if (myq < CA) store_out<D>(out + ((int64_t)b * CA + myq) * H * D + (int64_t)h * D, o, l, g);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1346,6 +1259,14 @@ static void set_lds_attr(K kfn, size_t bytes) {
   (void)hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
+// the tiled kernels exist for D = 64, 128, 256 (the launchers' callers have checked D): f(std::integral_constant<int, D>)
+template <typename F>
+static void dispatch_head_dim(int D, F f) {
+  if (D == 64) f(std::integral_constant<int, 64>());
+  else if (D == 128) f(std::integral_constant<int, 128>());
+  else f(std::integral_constant<int, 256>());
+}
+
 int attn_mfma_fwd_launch(const void* qkv, const AttnShape& sh, const float* rc, const float* rs, const int64_t* am, void* out, float* lse,
                          hipStream_t st) {
   size_t bytes;
@@ -1370,15 +1291,11 @@ int attn_mfma_fwd_launch(const void* qkv, const AttnShape& sh, const float* rc, 
   if (!sh.causal) { set_error("attn_fwd (bidirectional, bf16): S=%d D=%d does not fit the resident kernel", sh.S, sh.D); return MAFED_EINVAL; }
   dim3 grid((sh.S + 63) / 64, sh.H, sh.B), block(256);
   const size_t tb = (size_t)2 * 64 * sh.D * 2;
-#define MAFED_FWD_TILED(DD)                                                                                                       \
-  do {                                                                                                                            \
-    set_lds_attr(attn_fwd_mfma_kernel<DD>, tb);                                                                                   \
-    launch(K_ATTN_FWD, attn_fwd_flops(sh), attn_fwd_mfma_kernel<DD>, grid, block, tb, st, (const bf16_t*)qkv, sh, rc, rs, am, (bf16_t*)out, lse);                    \
-  } while (0)
-  if (sh.D == 64) MAFED_FWD_TILED(64);
-  else if (sh.D == 128) MAFED_FWD_TILED(128);
-  else MAFED_FWD_TILED(256);
-#undef MAFED_FWD_TILED
+  dispatch_head_dim(sh.D, [&](auto dd) {
+    constexpr int DD = decltype(dd)::value;
+    set_lds_attr(attn_fwd_mfma_kernel<DD>, tb);
+    launch(K_ATTN_FWD, attn_fwd_flops(sh), attn_fwd_mfma_kernel<DD>, grid, block, tb, st, (const bf16_t*)qkv, sh, rc, rs, am, (bf16_t*)out, lse);
+  });
   return MAFED_OK;
 }
 
@@ -1387,16 +1304,12 @@ int attn_suffix_mfma_launch(const void* qkv_img, const int64_t* image_index, con
   dim3 grid((sh.T + 63) / 64, sh.H, sh.B), block(256);
   const size_t tb = (size_t)2 * 64 * sh.D * 2;
   const double flops = 4.0 * sh.D * ((double)sh.T * sh.P + (double)sh.T * (sh.T + 1) / 2.0) * sh.H * sh.B;
-#define MAFED_SUFFIX_TILED(DD)                                                                                                    \
-  do {                                                                                                                            \
-    set_lds_attr(attn_suffix_mfma_kernel<DD>, tb);                                                                                \
-    launch(K_ATTN_FWD, flops, attn_suffix_mfma_kernel<DD>, grid, block, tb, st, (const bf16_t*)qkv_img, image_index, (const bf16_t*)qkv_txt, sh, rc, rs, am, \
-           (bf16_t*)out);                                                                                                         \
-  } while (0)
-  if (sh.D == 64) MAFED_SUFFIX_TILED(64);
-  else if (sh.D == 128) MAFED_SUFFIX_TILED(128);
-  else MAFED_SUFFIX_TILED(256);
-#undef MAFED_SUFFIX_TILED
+  dispatch_head_dim(sh.D, [&](auto dd) {
+    constexpr int DD = decltype(dd)::value;
+    set_lds_attr(attn_suffix_mfma_kernel<DD>, tb);
+    launch(K_ATTN_FWD, flops, attn_suffix_mfma_kernel<DD>, grid, block, tb, st, (const bf16_t*)qkv_img, image_index, (const bf16_t*)qkv_txt, sh,
+           rc, rs, am, (bf16_t*)out);
+  });
   return MAFED_OK;
 }
 
@@ -1406,16 +1319,12 @@ int attn_cand_mfma_launch(const void* qkv_pre, const void* qkv_cand, const CandS
   dim3 grid((CA + 63) / 64, sh.H, sh.B), block(256);
   const size_t tb = (size_t)2 * 64 * sh.D * 2;
   const double flops = 4.0 * sh.D * ((double)CA * sh.S0 + (double)CA * (sh.A + 1) / 2.0) * sh.H * sh.B;
-#define MAFED_CAND_TILED(DD)                                                                                                      \
-  do {                                                                                                                            \
-    set_lds_attr(attn_cand_mfma_kernel<DD>, tb);                                                                                  \
-    launch(K_ATTN_FWD, flops, attn_cand_mfma_kernel<DD>, grid, block, tb, st, (const bf16_t*)qkv_pre, (const bf16_t*)qkv_cand, sh, rc, rs, am, \
-           (bf16_t*)out);                                                                                                         \
-  } while (0)
-  if (sh.D == 64) MAFED_CAND_TILED(64);
-  else if (sh.D == 128) MAFED_CAND_TILED(128);
-  else MAFED_CAND_TILED(256);
-#undef MAFED_CAND_TILED
+  dispatch_head_dim(sh.D, [&](auto dd) {
+    constexpr int DD = decltype(dd)::value;
+    set_lds_attr(attn_cand_mfma_kernel<DD>, tb);
+    launch(K_ATTN_FWD, flops, attn_cand_mfma_kernel<DD>, grid, block, tb, st, (const bf16_t*)qkv_pre, (const bf16_t*)qkv_cand, sh, rc, rs, am,
+           (bf16_t*)out);
+  });
   return MAFED_OK;
 }
 
@@ -1443,19 +1352,15 @@ int attn_mfma_bwd_launch(const void* qkv, const void* out, const void* dout, con
   }
   dim3 grid((sh.S + 63) / 64, sh.H, sh.B), block(256);
   const size_t tb = (size_t)2 * 64 * sh.D * 2, tb2 = tb + 2 * 64 * 4;
-#define MAFED_BWD_TILED(DD)                                                                                                       \
-  do {                                                                                                                            \
-    set_lds_attr(attn_bwd_dq_mfma_kernel<DD>, tb);                                                                                \
-    set_lds_attr(attn_bwd_dkv_mfma_kernel<DD>, tb2);                                                                              \
-    launch(K_ATTN_BWD_DQ, attn_fwd_flops(sh), attn_bwd_dq_mfma_kernel<DD>, grid, block, tb, st, (const bf16_t*)qkv, (const bf16_t*)out, (const bf16_t*)dout, lse, sh, rc, rs, am, \
-                                                         (bf16_t*)dqkv, delta);                                                  \
-    launch(K_ATTN_BWD_DKV, attn_fwd_flops(sh), attn_bwd_dkv_mfma_kernel<DD>, grid, block, tb2, st, (const bf16_t*)qkv, (const bf16_t*)dout, lse, delta, sh, rc, rs, am,   \
-                                                           (bf16_t*)dqkv);                                                       \
-  } while (0)
-  if (sh.D == 64) MAFED_BWD_TILED(64);
-  else if (sh.D == 128) MAFED_BWD_TILED(128);
-  else MAFED_BWD_TILED(256);
-#undef MAFED_BWD_TILED
+  dispatch_head_dim(sh.D, [&](auto dd) {
+    constexpr int DD = decltype(dd)::value;
+    set_lds_attr(attn_bwd_dq_mfma_kernel<DD>, tb);
+    set_lds_attr(attn_bwd_dkv_mfma_kernel<DD>, tb2);
+    launch(K_ATTN_BWD_DQ, attn_fwd_flops(sh), attn_bwd_dq_mfma_kernel<DD>, grid, block, tb, st, (const bf16_t*)qkv, (const bf16_t*)out,
+           (const bf16_t*)dout, lse, sh, rc, rs, am, (bf16_t*)dqkv, delta);
+    launch(K_ATTN_BWD_DKV, attn_fwd_flops(sh), attn_bwd_dkv_mfma_kernel<DD>, grid, block, tb2, st, (const bf16_t*)qkv, (const bf16_t*)dout, lse,
+           delta, sh, rc, rs, am, (bf16_t*)dqkv);
+  });
   return MAFED_OK;
 }
 

@@ -33,36 +33,10 @@ __global__ __launch_bounds__(256) void attn_ref_fwd_kernel(const T* __restrict__
   const T* qp = base + (int64_t)q * rstride;
   for (int d = lane; d < D; d += 64) qrow[d] = rot_elem(qp, d, rot, rc + (int64_t)q * half, rs + (int64_t)q * half);
   __builtin_amdgcn_wave_barrier();
-  const float scale = rsqrtf((float)D);
-  float m = -INFINITY;
-  const int jlast = sh.causal ? q : S - 1;  // bidirectional: every key
-  for (int j = lane; j <= jlast; j += 64) {
-    float s = -INFINITY;
-    if (key_valid(am, b, j, sh.P, sh.T)) {
-      const T* kp = base + (int64_t)j * rstride + D;
-      float acc = 0.f;
-      for (int d = 0; d < D; ++d) acc = fmaf(qrow[d], rot_elem(kp, d, rot, rc + (int64_t)j * half, rs + (int64_t)j * half), acc);
-      s = acc * scale;
-    }
-    sc[j] = s;
-    m = fmaxf(m, s);
-  }
-  m = wave_max(m);
-  float l = 0.f;
-  for (int j = lane; j <= jlast; j += 64) {
-    const float p = expf(sc[j] - m);
-    sc[j] = p;
-    l += p;
-  }
-  l = wave_sum(l);
-  __builtin_amdgcn_wave_barrier();
-  const float inv = 1.0f / l;
-  T* op = out + ((int64_t)b * S + q) * H * D + (int64_t)h * D;
-  for (int d = lane; d < D; d += 64) {
-    float acc = 0.f;
-    for (int j = 0; j <= jlast; ++j) acc = fmaf(sc[j], Elem<T>::load(base + (int64_t)j * rstride + 2 * D + d), acc);
-    Elem<T>::store(op + d, acc * inv);
-  }
+  float m, l;
+  attn_exact_row(qrow, sc, sh.causal ? q + 1 : S, D, rot, rc, rs,  // bidirectional: every key
+                 [&](int j) { return AttnKey<T>{base + (int64_t)j * rstride, j, key_valid(am, b, j, sh.P, sh.T)}; },
+                 out + ((int64_t)b * S + q) * H * D + (int64_t)h * D, lane, m, l);
   if (lane == 0) lse[((int64_t)b * H + h) * S + q] = m + logf(l);
 }
 

@@ -5,8 +5,9 @@
 // prompt b sits at position P + j and sees the P keys of image image_index[b] and the text keys 0 .. j of its own prompt that the
 // left-padding mask leaves; rotary on load with position = key index; softmax in fp32.  A query at a padded position (or of an
 // all-padding prompt) still sees the image keys, as the full forward's rows do.
-// This file: the exact kernel (fp32 parity mode; bf16 head sizes without an MFMA kernel) in the form of attn_ref.hip, one wave per
-// query row.  The bf16 MFMA kernel lives beside the forward it was cut from (attn_mfma.hip, attn_suffix_mfma_kernel).
+// This file: the exact kernel (fp32 parity mode; bf16 head sizes without an MFMA kernel) one wave per query row: a shell
+// around the exact forward row it shares with attn_ref.hip (attn.h, attn_exact_row), which it tells where key j lives.  The bf16 MFMA
+// kernel lives beside the tiled forward and shares its tile step (attn_mfma.hip, attn_suffix_mfma_kernel).
 #include "attn.h"
 
 namespace mafed {
@@ -30,36 +31,12 @@ __global__ __launch_bounds__(256) void attn_suffix_ref_kernel(const T* __restric
   const int pos = P + q;
   for (int d = lane; d < D; d += 64) qrow[d] = rot_elem(tb + (int64_t)q * rstride, d, rot, rc + (int64_t)pos * half, rs + (int64_t)pos * half);
   __builtin_amdgcn_wave_barrier();
-  const float scale = rsqrtf((float)D);
-  float m = -INFINITY;
-  for (int j = lane; j <= pos; j += 64) {
-    float s = -INFINITY;
-    if (key_valid(am, b, j, P, Tt)) {
-      const T* kp = (j < P ? ib + (int64_t)j * rstride : tb + (int64_t)(j - P) * rstride) + D;
-      float acc = 0.f;
-      for (int d = 0; d < D; ++d) acc = fmaf(qrow[d], rot_elem(kp, d, rot, rc + (int64_t)j * half, rs + (int64_t)j * half), acc);
-      s = acc * scale;
-    }
-    sc[j] = s;
-    m = fmaxf(m, s);
-  }
-  m = wave_max(m);
-  float l = 0.f;
-  for (int j = lane; j <= pos; j += 64) {
-    const float p = expf(sc[j] - m);
-    sc[j] = p;
-    l += p;
-  }
-  l = wave_sum(l);
-  __builtin_amdgcn_wave_barrier();
-  const float inv = 1.0f / l;
-  T* op = out + ((int64_t)b * Tt + q) * H * D + (int64_t)h * D;
-  for (int d = lane; d < D; d += 64) {
-    float acc = 0.f;
-    for (int j = 0; j < P; ++j) acc = fmaf(sc[j], Elem<T>::load(ib + (int64_t)j * rstride + 2 * D + d), acc);
-    for (int j = P; j <= pos; ++j) acc = fmaf(sc[j], Elem<T>::load(tb + (int64_t)(j - P) * rstride + 2 * D + d), acc);
-    Elem<T>::store(op + d, acc * inv);
-  }
+  float m, l;
+  attn_exact_row(qrow, sc, pos + 1, D, rot, rc, rs,
+                 [&](int j) {
+                   return AttnKey<T>{j < P ? ib + (int64_t)j * rstride : tb + (int64_t)(j - P) * rstride, j, key_valid(am, b, j, P, Tt)};
+                 },
+                 out + ((int64_t)b * Tt + q) * H * D + (int64_t)h * D, lane, m, l);
 }
 
 template <typename T>

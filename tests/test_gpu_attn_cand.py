@@ -9,7 +9,7 @@ from tests.test_gpu_model import DEV, close
 pytestmark = pytest.mark.gpu
 
 # (B, P, T, C, A, H, D): one row; several candidates in one tile; 69 rows, candidates straddle a query tile; A > 64; the wider heads;
-# the production geometry
+# the production geometry; two prefix tiles and two query tiles with a candidate straddling them at D = 256
 CASES = [
     (2, 8, 6, 1, 1, 2, 64),
     (3, 40, 13, 5, 3, 2, 64),
@@ -18,6 +18,7 @@ CASES = [
     (2, 8, 6, 3, 4, 1, 128),
     (2, 5, 3, 2, 3, 1, 256),
     (4, 256, 32, 8, 6, 16, 64),
+    (2, 70, 13, 9, 9, 1, 256),
 ]
 
 

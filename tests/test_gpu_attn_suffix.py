@@ -7,7 +7,8 @@ from tests.test_gpu_model import DEV, close
 
 pytestmark = pytest.mark.gpu
 
-# (B, N, P, T, H, D, image_index): unsorted index with image 1 unused; ragged query tile (T = 33); the production geometry
+# (B, N, P, T, H, D, image_index): unsorted index with image 1 unused; ragged query tile (T = 33); the production geometry;
+# T > 64: a second query tile with its own key-tile count, and waves that skip the tiles behind their rows
 CASES = [
     (2, 1, 8, 6, 2, 64, [0, 0]),
     (5, 3, 40, 13, 2, 64, [2, 0, 2, 0, 0]),
@@ -15,6 +16,8 @@ CASES = [
     (2, 1, 5, 3, 1, 256, [0, 0]),
     (3, 2, 40, 33, 2, 64, [1, 0, 1]),
     (4, 2, 256, 32, 16, 64, [0, 1, 1, 0]),
+    (2, 1, 40, 70, 1, 64, [0, 0]),
+    (2, 2, 100, 130, 1, 128, [1, 0]),
 ]
 
 
