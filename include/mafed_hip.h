@@ -401,6 +401,24 @@ int mafed_ce_fwd_guarded(const void* logits, mafed_dtype dtype, const int64_t* l
 int mafed_ce_bwd(const void* logits, mafed_dtype dtype, const int64_t* labels, const float* lse, int B, int T, int64_t V,
                  const float* gloss_dev, void* dlogits, void* stream);
 
+/* ---- LwF head loss: the cross-entropy above + temperature-softened logit distillation, one pass per direction ----
+ * student, teacher: logits [B,T,V] of the same head rows in `dtype` (F32 or BF16; the teacher's are a frozen model's); labels as above.
+ * With p^tau_x = softmax(x / tau), tau > 0, per labelled row (shifted label != -100, never the last position):
+ *   CE = lse(s) - s[lab]
+ *   KD = KL(p^tau_t || p^tau_s) = sum_c p^tau_t[c] (t[c] - s[c]) / tau - lse(t / tau) + lse(s / tau)
+ * each summed per sample / max(count_b, 1e-13) and averaged over B like mafed_ce_fwd; out3 fp32 [3] = { CE + lambda tau^2 KD, CE, KD }.
+ * lse3 fp32 [3, B*T] = { lse(s), lse(s / tau), lse(t / tau) } saved for the backward (0 on unlabelled rows, which are not read);
+ * row_ce, row_kd: fp32 [B*T] scratch.  poison_flag (may be NULL): a non-zero device flag turns out3[0] into NaN (mafed_ce_fwd_guarded).
+ * Every exponential is max-subtracted; student == teacher gives KD == 0.0 exactly; tau == 1 gives lse3[0] == lse3[1] bit for bit.
+ * V % 4 == 0; fp32 logits 16-byte, bf16 logits 8-byte aligned.  No atomics, no workspace: the same bits on every call. */
+int mafed_ce_kd_fwd(const void* student, const void* teacher, mafed_dtype dtype, const int64_t* labels, int B, int T, int64_t V,
+                    float tau, float lambda, float* lse3, float* row_ce, float* row_kd, float* out3, const int* poison_flag,
+                    void* stream);
+/* dlogits[b,t,:] = g_b (softmax(s) - onehot(lab)) + g_b lambda tau (p^tau_s - p^tau_t), g_b = gloss / (B * count_b), for labelled rows;
+ * 0 otherwise (incl. t = T-1).  gloss_dev: device scalar (upstream dL/dloss).  dlogits: `dtype` [B,T,V], a buffer of its own. */
+int mafed_ce_kd_bwd(const void* student, const void* teacher, mafed_dtype dtype, const int64_t* labels, const float* lse3, int B, int T,
+                    int64_t V, float tau, float lambda, const float* gloss_dev, void* dlogits, void* stream);
+
 /* ---- MAFED per-modality masked distillation (mafed/methods/distillation.py:124-166, 226-257) -----------------
  * s, t: fp32 [B,S,h] student / frozen-teacher hidden state of one layer; attention_mask int64 [B,T]; P image tokens.
  * One pass serves both masks: out[4] = { sum_lang d, sum_vision d, n_lang, n_vision } with

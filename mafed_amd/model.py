@@ -286,6 +286,13 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
         self.sparse_lm_head = True          # batches that carry ``max_label_rows`` get the row-sparse LM head in training
         # device flag of the last row-sparse training forward (written there; read by callers / tests): 1 = rows were dropped, the loss is NaN
         self.last_label_overflow: Optional[torch.Tensor] = None
+        # Logit distillation (methods/lwf.py).  A callable (feats, input_ids, attention_mask, rows) -> (teacher logits, tau, lambda):
+        # a training forward with labels hands it the padded batch and the head's row selection (the row-sparse head's ``row_of_slot``
+        # [B * Rc] int32, or None = all T text rows) and gets a frozen model's logits on exactly those rows, in compute dtype.  The head
+        # loss is then CE + lambda tau^2 KL (ops.ce_kd_fwd) instead of CE.  None: nothing changes.  Not copied by deepcopy.
+        self.logit_teacher = None
+        # device [3] = (loss, CE, KD) of the last training forward that had a logit teacher (written there; read by callers, no sync)
+        self.last_head_losses: Optional[torch.Tensor] = None
         self.defer_ln_param_reduce = True   # LayerNorm parameter-gradient reduction on a side stream (needs overlap_param_grads)
         # generation (mafed_amd/generation.py)
         self.beam_trace: Optional[List[Any]] = None   # a list: generate(num_beams > 1) appends every step's candidate lists to it
@@ -604,7 +611,7 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
     # ---- engine ------------------------------------------------------------------------------------------------------
     def _engine_forward(self, feats, input_ids, attention_mask, labels, want_hidden, train, n_hidden: Optional[int] = None,
                         keep_qkv: bool = False, qkv_out: Optional[Sequence[torch.Tensor]] = None, label_rows_hint: Optional[int] = None,
-                        last_only: bool = False, skip_head: bool = False, pad_text: bool = False):
+                        last_only: bool = False, skip_head: bool = False, pad_text: bool = False, head_rows: Optional[torch.Tensor] = None):
         if not self.flat_params.is_cuda:
             raise RuntimeError("mafed_amd runs on the GPU only (no CPU fallback); move the model with .cuda()")
         pe, main_st = self._param_events, torch.cuda.current_stream()
@@ -693,6 +700,13 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
             return sv
         # final LN (fp32 hidden state L only when asked for) + LM head on the T text positions (vl_pythia.py:89,310)
         xt = x.view(B, S, h)[:, P:, :].reshape(B * T, h)
+        if head_rows is not None:
+            # inference (head_logits_rows): final LN + head on the given text rows only -> logits [n, V]; a negative index is a row of zeros
+            assert not train and labels is None
+            lnc, _, _, _ = ops.layernorm_fwd(ops.gather_rows(xt, head_rows), Po.final_ln_w, Po.final_ln_b,
+                                             None, None, cfg.layer_norm_eps, cd, save_stats=False)
+            sv["logits"] = ops.gemm(lnc, Wo.embed_out, False, True)
+            return sv
         lnf, _, fmean, frstd = ops.layernorm_fwd(xt, Po.final_ln_w, Po.final_ln_b,
                                                  None, None, cfg.layer_norm_eps, cd, save_stats=train)
         if want_hidden:
@@ -713,18 +727,25 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
             # device flag: 1 if a sample had more labelled positions than the hint promised -- rows were dropped; the CE below then
             # returns NaN (no host synchronisation: the step fails loudly instead of training on a wrong loss)
             self.last_label_overflow = ov
+            teacher = self._teacher_head_logits(sv, feats, ros) if self.logit_teacher is not None else None
             lnf_c = ops.gather_rows(lnf, ros)
             logits = ops.gemm(lnf_c, Wo.embed_out, False, True).view(B, Rc, cfg.vocab_size)
             sv["logits"] = logits
-            loss, lse_ce = ops.ce_fwd(logits, labels_c, poison=ov)
-            sv["loss"], sv["ce_lse"] = loss, lse_ce
+            if teacher is not None:
+                self._head_kd_loss(sv, logits, labels_c, teacher, ov)
+            else:
+                loss, lse_ce = ops.ce_fwd(logits, labels_c, poison=ov)
+                sv["loss"], sv["ce_lse"] = loss, lse_ce
             sv["sparse_head"] = (sor, labels_c)
             sv["final"] = (xt, lnf_c, fmean, frstd)
             sv["x_last"] = x
             return sv
+        teacher = self._teacher_head_logits(sv, feats, None) if (train and labels is not None and self.logit_teacher is not None) else None
         logits = ops.gemm(lnf, Wo.embed_out, False, True).view(B, T, cfg.vocab_size)
         sv["logits"] = logits
-        if labels is not None:
+        if teacher is not None:
+            self._head_kd_loss(sv, logits, labels, teacher, None)
+        elif labels is not None:
             loss, lse_ce = ops.ce_fwd(logits, labels)
             sv["loss"] = loss
             if train:
@@ -733,6 +754,36 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
             sv["final"] = (xt, lnf, fmean, frstd)
             sv["x_last"] = x
         return sv
+
+    def _teacher_head_logits(self, sv, feats, rows):
+        """``logit_teacher`` on the padded batch of this forward and the head's row selection (``rows``: the row-sparse head's
+        ``row_of_slot``, None = all text rows): (logits, tau, lambda).  Runs on the caller's stream, in front of the student's head."""
+        t_logits, tau, lam = self.logit_teacher(feats, sv["input_ids"], sv["attention_mask"], rows)
+        return t_logits.detach(), float(tau), float(lam)
+
+    def _head_kd_loss(self, sv, logits, labels, teacher, poison) -> None:
+        """Training head loss with a logit teacher: CE + lambda tau^2 KL against the teacher's logits of the same rows, one pass
+        (ops.ce_kd_fwd) -> sv["loss"], sv["kd"], ``last_head_losses``."""
+        t_logits, tau, lam = teacher
+        if t_logits.dtype != logits.dtype or t_logits.numel() != logits.numel():
+            raise ValueError(f"logit_teacher returned {tuple(t_logits.shape)} {t_logits.dtype} for head rows {tuple(logits.shape)} {logits.dtype}")
+        t_logits = t_logits.contiguous().view(logits.shape)
+        out3, lse3 = ops.ce_kd_fwd(logits, t_logits, labels, tau, lam, poison=poison)
+        sv["loss"] = out3[0:1]
+        sv["kd"] = (t_logits, lse3, tau, lam)
+        self.last_head_losses = out3
+
+    @torch.no_grad()
+    def head_logits_rows(self, feats, input_ids, attention_mask, rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Inference logits of a batch that is already at its padded length (pad_text_batch), for a frozen teacher: the stack, the final
+        LayerNorm and the LM head on the text rows ``rows`` only (int32 indices into the [B * T] text rows; a negative one gives a row
+        of zeros) -> [len(rows), V] in compute dtype; ``rows`` None -> [B, T, V].  No activations are kept."""
+        dev = self.flat_params.device
+        if rows is not None:
+            rows = rows.to(dev, torch.int32).contiguous()
+        st = self._engine_forward(feats.to(dev).contiguous(), input_ids.to(dev, torch.int64).contiguous(),
+                                  attention_mask.to(dev, torch.int64).contiguous(), None, False, train=False, head_rows=rows)
+        return st["logits"]
 
     def hidden_grad_taps(self, batch: Dict[str, torch.Tensor], layers: Sequence[int]) -> Dict[int, torch.Tensor]:
         """dL_CE / d hidden_states[l] for every l in ``layers`` from ONE backward sweep (the adaptive-weights pass of
@@ -903,7 +954,12 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
             gl = dloss.reshape(1).to(torch.float32).contiguous()
             sp = sv.get("sparse_head")   # (slot of every text row, compact labels): the head ran on the labelled rows only
             n_head = logits.shape[0] * logits.shape[1]
-            dlog = ops.ce_bwd(logits, sp[1] if sp is not None else sv["labels"], sv["ce_lse"], gl).view(n_head, cfg.vocab_size)
+            head_labels = sp[1] if sp is not None else sv["labels"]
+            kd = sv.pop("kd", None)   # (teacher logits, lse3, tau, lambda): the head loss was CE + lambda tau^2 KL (_head_kd_loss)
+            if kd is not None:
+                dlog = ops.ce_kd_bwd(logits, kd[0], head_labels, kd[1], kd[2], kd[3], gl).view(n_head, cfg.vocab_size)
+            else:
+                dlog = ops.ce_bwd(logits, head_labels, sv["ce_lse"], gl).view(n_head, cfg.vocab_size)
             wgrad(dlog, lnf, Go.embed_out)
             if cd == torch.bfloat16:
                 # [rows, V] . [V, h]: few output tiles with K = 50304 -- accumulate-only fp32 output so that the GEMM splits K

@@ -644,6 +644,44 @@ def ce_bwd(logits: torch.Tensor, labels: torch.Tensor, lse: torch.Tensor, gloss:
     return out
 
 
+def _kd_check(student: torch.Tensor, teacher: torch.Tensor, labels: torch.Tensor) -> Tuple[int, int, int]:
+    B, T, V = student.shape
+    if teacher.shape != student.shape or teacher.dtype != student.dtype:
+        raise ValueError(f"teacher logits {tuple(teacher.shape)} {teacher.dtype} do not match the student's {tuple(student.shape)} {student.dtype}")
+    assert student.is_contiguous() and teacher.is_contiguous() and labels.is_contiguous() and labels.dtype == torch.int64
+    assert labels.shape == (B, T)
+    return B, T, V
+
+
+def ce_kd_fwd(student: torch.Tensor, teacher: torch.Tensor, labels: torch.Tensor, tau: float, lam: float,
+              poison: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """LwF head loss (mafed_ce_kd_fwd): student / teacher logits [B,T,V] of the same rows, labels [B,T] ->
+    (out3 = [CE + lam tau^2 KD, CE, KD], lse3 [3,B,T] = lse(s), lse(s / tau), lse(t / tau)).  ``poison`` as in :func:`ce_fwd`."""
+    B, T, V = _kd_check(student, teacher, labels)
+    dev = student.device
+    lse3 = torch.empty((3, B, T), dtype=torch.float32, device=dev)
+    rows = torch.empty((2, B, T), dtype=torch.float32, device=dev)
+    out3 = torch.empty(3, dtype=torch.float32, device=dev)
+    if poison is not None:
+        assert poison.dtype == torch.int32 and poison.numel() == 1
+    check(_lib.load().mafed_ce_kd_fwd(_ptr(student), _ptr(teacher), _dt(student), _ptr(labels), B, T, V, float(tau), float(lam), _ptr(lse3),
+                                      _ptr(rows[0]), _ptr(rows[1]), _ptr(out3), _ptr(poison), _stream()), "mafed_ce_kd_fwd")
+    return out3, lse3
+
+
+def ce_kd_bwd(student: torch.Tensor, teacher: torch.Tensor, labels: torch.Tensor, lse3: torch.Tensor, tau: float, lam: float,
+              gloss: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dL/d(student logits) of :func:`ce_kd_fwd`: the cross-entropy and the distillation gradient, one pass (``out``: a buffer of its own)."""
+    B, T, V = _kd_check(student, teacher, labels)
+    assert lse3.shape == (3, B, T) and lse3.dtype == torch.float32 and lse3.is_contiguous()
+    if out is None:
+        out = torch.empty_like(student)
+    assert out.data_ptr() != student.data_ptr() and out.data_ptr() != teacher.data_ptr()
+    check(_lib.load().mafed_ce_kd_bwd(_ptr(student), _ptr(teacher), _dt(student), _ptr(labels), _ptr(lse3), B, T, V, float(tau), float(lam),
+                                      _ptr(gloss), _ptr(out), _stream()), "mafed_ce_kd_bwd")
+    return out
+
+
 def distill_fwd(s: torch.Tensor, t, attention_mask: torch.Tensor, P: int, cosine: bool = False,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """-> out[4] = {lang_sum, vision_sum, n_lang, n_vision}; ``t`` a dense fp32 [B, S, h] tensor or ``TeacherRows``"""
