@@ -1,7 +1,7 @@
 """Generation for ``VLPythiaForCausalLM``: greedy search, beam search, sampling and candidate scoring, the KV-cached decode step, its cache and the
 captured-graph decode.
 ``GenerationMixin`` is a base class of the model (mafed_amd/model.py, which this module does not import): it uses the model's engine
-forward, parameter records and rotary tables, and the state ``fused_decode`` / ``beam_trace`` / ``_decode_graphs`` its ``__init__`` declares."""
+forward and its pieces (mafed_amd/engine.py: layer body, projector, parameter readiness, final LayerNorm + head), parameter records and rotary tables, and the state ``fused_decode`` / ``beam_trace`` / ``_decode_graphs`` its ``__init__`` declares."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -10,7 +10,6 @@ from typing import Any, Optional, Tuple
 import torch
 
 from mafed_amd import ops
-from mafed_amd._lib import EPI_GELU
 
 
 @dataclass
@@ -334,7 +333,7 @@ class GenerationMixin:
 
     def _score_shared(self, feats, image_index, ids, am, tok, tgt) -> Tuple[torch.Tensor, dict]:
         """``score``'s shared path -> (token log-probabilities fp32 [B, C, A], the trace record)."""
-        cfg, cd = self.config, self.compute_dtype
+        cfg = self.config
         P, h, H, D, L = cfg.num_vision_tokens, cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim, cfg.num_hidden_layers
         (B, T), (_, C, A), dev = ids.shape, tok.shape, ids.device
         S0, BC, rot = P + T, B * C, cfg.rotary_ndims
@@ -355,14 +354,11 @@ class GenerationMixin:
             tok = torch.cat([tok, torch.zeros((B, C, A_run - A), dtype=torch.int64, device=dev)], dim=2)
         cos, sin = self.rotary_tables(S0 + A_run)
         wts, pars = self._tensors(0), self._tensors(1)
-        Wo, Po = wts.outer, pars.outer
-        x = Po.embed_in.index_select(0, tok.reshape(-1))   # fp32 residual rows [B*C*A_run, h]
+        x = pars.outer.embed_in.index_select(0, tok.reshape(-1))   # fp32 residual rows [B*C*A_run, h]
         for i in range(L):
-            x = self._infer_layer(wts, pars, i, x, lambda qkv: ops.attn_cand_fwd(store[i], S0, qkv, C, A_run, B, H, D, rot, cos, sin, am))
+            x = self._layer_forward(wts, pars, i, x, lambda qkv: (ops.attn_cand_fwd(store[i], S0, qkv, C, A_run, B, H, D, rot, cos, sin, am), None))
         # candidate row j predicts token j + 1: rows 0 .. A - 2 of every candidate go through the final LayerNorm and the head
-        xh = x.view(BC, A_run, h)[:, :A - 1, :].reshape(BC * (A - 1), h)
-        lnf, _, _, _ = ops.layernorm_fwd(xh, Po.final_ln_w, Po.final_ln_b, None, None, cfg.layer_norm_eps, cd, save_stats=False)
-        lp1 = ops.token_logprob(ops.gemm(lnf, Wo.embed_out, False, True), tgt[:, :, 1:].contiguous())
+        lp1 = ops.token_logprob(self._lm_head(x.view(BC, A_run, h)[:, :A - 1, :].reshape(BC * (A - 1), h)), tgt[:, :, 1:].contiguous())
         return torch.cat([lp0.view(B, C, 1), lp1], dim=2), {"prefix_rows": prefix_rows, "candidate_rows": BC * A_run}
 
     def _generate_inputs(self, input_ids, attention_mask, pixel_values, patch_embeddings, pad_token_id, eos_token_id):
@@ -413,18 +409,6 @@ class GenerationMixin:
         cache = _DecodeCache(self, list(store.unbind(0)), B, st["S"], cap, am, fused=self.fused_decode, prefix_storage=store, beams=beams)
         return cache, st["logits"][:, -1, :]
 
-    def _infer_layer(self, wts, pars, i: int, x: torch.Tensor, attend, qkv_out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Layer i over inference-only rows, ``_engine_forward``'s body without its records: LN pair, fused-QKV product (into ``qkv_out`` when
-        given), ``attend(qkv)`` -> the attention output of these rows, dense, MLP and the parallel residual -> the next fp32 residual rows.
-        Shared by the image, text and candidate passes of ``_prefill_shared_rows`` and ``score``."""
-        cfg, cd = self.config, self.compute_dtype
-        w, p = wts.layers[i], pars.layers[i]
-        ln1, ln2, _, _ = ops.layernorm_fwd(x, p.ln1_w, p.ln1_b, p.ln2_w, p.ln2_b, cfg.layer_norm_eps, cd, save_stats=False)
-        qkv = ops.gemm(ln1, w.qkv_w, False, True, bias=p.qkv_b, out=qkv_out)
-        attn = ops.gemm(attend(qkv), w.dense_w, False, True, bias=p.dense_b, out_dtype=cd)
-        a = ops.gemm(ln2, w.fc1_w, False, True, bias=p.fc1_b, epilogue=EPI_GELU)
-        return ops.gemm(a, w.fc2_w, False, True, bias=p.fc2_b, out_dtype=torch.float32, res1=attn, res2=x)
-
     def _prefill_shared(self, feats, image_index, ids, am, cap: int, beams: int = 1) -> Tuple["_DecodeCache", torch.Tensor]:
         """``_prefill`` for B prompts over the N images of ``feats`` (DESIGN.md section 4c'''): ``_prefill_shared_rows``, then the decode cache over
         the assembled prefix (which rotates the prefix keys as ever)."""
@@ -442,35 +426,23 @@ class GenerationMixin:
         arange positions, so the image rows of every layer depend on the image alone.  They go through the stack once per image (their
         fused-QKV rows into an image store [L, N*P, 3h]; the last layer stops there, nothing reads its image rows), the text rows once
         per prompt (text store [L, B*T, 3h]), attending [image image_index[b] | own text] through ``ops.attn_suffix_fwd``; one gather then
-        lays the two stores out as the [L, B*S0, 3h] prefix the decode cache takes.  The layer body is ``_infer_layer``."""
+        lays the two stores out as the [L, B*S0, 3h] prefix the decode cache takes.  The layer body is the engine's ``_layer_forward``."""
         if not self.flat_params.is_cuda:
             raise RuntimeError("mafed_amd runs on the GPU only (no CPU fallback); move the model with .cuda()")
         cfg, cd = self.config, self.compute_dtype
         P, h, H, D, L = cfg.num_vision_tokens, cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim, cfg.num_hidden_layers
-        pe = self._param_events
-        if pe is not None:   # behind every chunk of a pipelined optimiser update, as the engine forward orders itself layer by layer
-            main_st = torch.cuda.current_stream()
-            for key in ["pre"] + [("layer", i) for i in range(L)] + ["head"]:
-                main_st.wait_event(pe[key])
-            self._param_events = None
-        if self._shadow_dirty:
-            self.sync_shadow()
+        # behind every chunk of a pipelined optimiser update at once, where the engine forward orders itself layer by layer
+        self._params_ready(torch.cuda.current_stream(), -1, L + 1)
         (B, T), N = ids.shape, feats.shape[0]
         S0, rot, eps, dev = P + T, cfg.rotary_ndims, cfg.layer_norm_eps, ids.device
         cos, sin = self.rotary_tables(S0)
         wts, pars = self._tensors(0), self._tensors(1)
-        Wo, Po = wts.outer, pars.outer
         img_store = torch.empty((L, N * P, 3 * h), dtype=cd, device=dev)
         txt_store = torch.empty((L, B * T, 3 * h), dtype=cd, device=dev)
 
         # image pass, N * P rows: projector, then the layers over the image alone (S = P; the one-column mask of ones makes the last image
         # key a valid "text" key of the full attention kernels, which take T >= 1 through this wrapper)
-        f2 = feats.reshape(N * P, cfg.vision_hidden_size)
-        if f2.dtype not in (torch.float32, torch.bfloat16):
-            f2 = f2.float()
-        fc = f2.contiguous() if f2.dtype == cd else ops.cast(f2.contiguous(), cd)
-        a0 = ops.gemm(fc, Wo.proj0_w, False, True, bias=Po.proj0_b, epilogue=EPI_GELU)
-        img = ops.gemm(a0, Wo.proj2_w, False, True, bias=Po.proj2_b)
+        img = self._projector_forward(feats, N, False)[3]
         x = img if img.dtype == torch.float32 else ops.cast(img, torch.float32)   # fp32 residual stream
         ones = torch.ones((N, 1), dtype=torch.int64, device=dev)
         for i in range(L):
@@ -479,15 +451,13 @@ class GenerationMixin:
                 ln1, _, _, _ = ops.layernorm_fwd(x, p.ln1_w, p.ln1_b, None, None, eps, cd, save_stats=False)
                 ops.gemm(ln1, w.qkv_w, False, True, bias=p.qkv_b, out=img_store[i])
                 break
-            x = self._infer_layer(wts, pars, i, x, lambda qkv: ops.attn_fwd(qkv, N, P, H, D, rot, cos, sin, ones)[0], qkv_out=img_store[i])
+            x = self._layer_forward(wts, pars, i, x, lambda qkv: ops.attn_fwd(qkv, N, P, H, D, rot, cos, sin, ones), qkv_out=img_store[i])
         # text pass, B * T rows
-        x = Po.embed_in.index_select(0, ids.reshape(-1))
+        x = pars.outer.embed_in.index_select(0, ids.reshape(-1))
         for i in range(L):
-            x = self._infer_layer(wts, pars, i, x, lambda qkv: ops.attn_suffix_fwd(img_store[i], image_index, N, P, qkv, T, B, H, D, rot, cos, sin, am),
-                                  qkv_out=txt_store[i])
-        xl = x.view(B, T, h)[:, -1, :].contiguous()
-        lnl, _, _, _ = ops.layernorm_fwd(xl, Po.final_ln_w, Po.final_ln_b, None, None, eps, cd, save_stats=False)
-        logits = ops.gemm(lnl, Wo.embed_out, False, True)
+            x = self._layer_forward(wts, pars, i, x, lambda qkv: (ops.attn_suffix_fwd(img_store[i], image_index, N, P, qkv, T, B, H, D, rot, cos, sin, am), None),
+                                    qkv_out=txt_store[i])
+        logits = self._lm_head(x.view(B, T, h)[:, -1, :].contiguous())
         # prefix assembly: [image of the prompt | its text] per layer, one launch for all of them
         store = ops.prefix_gather(img_store, txt_store, image_index, B, P, T, out=self._prefix_store(B, T))
         return store, logits, {"image_store": tuple(img_store.shape), "text_store": tuple(txt_store.shape), "prefix": tuple(store.shape)}
@@ -559,7 +529,7 @@ class GenerationMixin:
 
     def _engine_decode_step(self, tokens: torch.Tensor, t: int, cache: "_DecodeCache") -> torch.Tensor:
         """One token per sample through the stack: ``tokens`` [B] sit at position S0 + t; returns the logits [B, V]."""
-        cfg, cd = self.config, self.compute_dtype
+        cfg = self.config
         h, H, D, L = cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim, cfg.num_hidden_layers
         B, S0, rot = cache.B, cache.S0, cfg.rotary_ndims
         cos, sin = self.rotary_tables(S0 + cache.cap)
@@ -583,19 +553,14 @@ class GenerationMixin:
                                           w.fc1_w, p.fc1_b)
                 x = ops.decode_out(x, attend(i), a, w.dense_w, p.dense_b, w.fc2_w, p.fc2_b, cache.workspace, out=x)
                 continue
-            ln1, ln2, _, _ = ops.layernorm_fwd(x, p.ln1_w, p.ln1_b, p.ln2_w, p.ln2_b, cfg.layer_norm_eps, cd, save_stats=False)
             # the new token's q | k | v row goes straight into the cache (row t of the per-layer [B, cap, 3*H*D] tensor)
-            ops.gemm(ln1, w.qkv_w, False, True, bias=p.qkv_b, out=cache.new[i][:, t, :])
-            attn = ops.gemm(attend(i), w.dense_w, False, True, bias=p.dense_b, out_dtype=cd)
-            a = ops.gemm(ln2, w.fc1_w, False, True, bias=p.fc1_b, epilogue=EPI_GELU)
-            x = ops.gemm(a, w.fc2_w, False, True, bias=p.fc2_b, out_dtype=torch.float32, res1=attn, res2=x)
+            x = self._layer_forward(wts, pars, i, x, lambda qkv: (attend(i), None), qkv_out=cache.new[i][:, t, :])
         if cache.fused and B * cache.beams <= 32 and h == 1024 and cfg.vocab_size % 32 == 0 and cfg.vocab_size >= 16384:
             # final LayerNorm + LM head as one persistent launch (decode_head_kernel: rows normalised once per CU, the vocabulary's
             # weight strips streamed through LDS): 24 us against 48 for LayerNorm + the skinny product at V = 50k
             return ops.decode_ln_linear(x, Po.final_ln_w, Po.final_ln_b, cfg.layer_norm_eps, Wo.embed_out)
         # (other shapes: the one-slab-per-block forms of ops.decode_ln_linear are no faster than the two launches below)
-        lnf, _, _, _ = ops.layernorm_fwd(x, Po.final_ln_w, Po.final_ln_b, None, None, cfg.layer_norm_eps, cd, save_stats=False)
-        return ops.gemm(lnf, Wo.embed_out, False, True)
+        return self._lm_head(x)
 
 
 class _DecodeCache:

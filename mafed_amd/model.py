@@ -32,7 +32,7 @@ import torch
 from torch import nn
 
 from mafed_amd import ops
-from mafed_amd._lib import EPI_GELU, EPI_GELU_BWD, EPI_NONE
+from mafed_amd.engine import EngineMixin, SweepRecord, _ModelFn, _trim  # noqa: F401  (SweepRecord re-exported)
 from mafed_amd.generation import BeamSearchOutput, GenerationMixin, _DecodeCache, _GraphedDecode  # noqa: F401  (re-exported)
 
 
@@ -203,20 +203,7 @@ def bucket_text_len(text_bucket, B: int, P: int, T: int) -> int:
     return T if m == 0 else T + (-(P + T)) % m
 
 
-def _trim(x: torch.Tensor, n: int) -> torch.Tensor:
-    """The first n positions of a [B, n', ...] tensor as a contiguous tensor (x itself when nothing was appended)."""
-    return x if x.shape[1] == n else x[:, :n].contiguous()
-
-
-@dataclass
-class SweepRecord:
-    """What a backward sweep reports: left on the model as ``last_sweep`` when the sweep starts, completed as it goes."""
-    serial: int = 0                  # counts the model's sweeps: tells a gradient hook which sweep reported a range
-    filled_squares: bool = False     # its weight-gradient GEMMs leave the squares of the layers' matrix gradients in ``dw_sumsq``
-    dx_chain_event: Optional[torch.cuda.Event] = None   # end of its dX chain; Trainer takes it and resets it to None
-
-
-class VLPythiaForCausalLM(GenerationMixin, nn.Module):
+class VLPythiaForCausalLM(EngineMixin, GenerationMixin, nn.Module):
     """MI355X-native counterpart of ``VLCLIPGPTNeoXForCausalLM`` for the training hot path."""
 
     def __init__(self, config: VLPythiaConfig, compute_dtype: torch.dtype = torch.bfloat16, device: Any = None,
@@ -299,7 +286,7 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
         self.prefill_trace: Optional[List[Any]] = None   # a list: a shared-image prefill (image_index) appends the shapes of its three stores to it
         self.fused_decode = True    # written by callers (tests, tools/decode_bench.py): False = the six-launch decode layer; read when a decode cache is built
         self._decode_graphs: Dict[Tuple, Any] = {}   # written and read by generate(use_graph=True): (B, T, max_new, eos, pad) -> _GraphedDecode
-        # The hand-over of a backward sweep (_engine_backward_impl).  Its inputs are the attributes below, written by Trainer._device_step and
+        # The hand-over of a backward sweep (engine.BackwardSweep).  Its inputs are the attributes below, written by Trainer._device_step and
         # the optimiser before it; what it reports -- its serial, whether its weight-gradient GEMMs fill `dw_sumsq`, the end of its dX chain --
         # is the SweepRecord it leaves in `last_sweep`, which the clip norm (optim.IncrementalNorm) and Trainer read.
         self.contended_backward: Any = False   # Trainer (bench.py, tests) writes: False / None, True / "128x128" or "ticketed" GEMM kernels beside collectives
@@ -449,7 +436,7 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
 
     def _tensors(self, which: int) -> BufferViews:
         """The per-layer / outer records over one flat buffer: 0 = weights in compute dtype (the bf16 shadow, or the parameters in
-        fp32 mode), 1 = fp32 parameters, 2 = gradients.  The engine fetches each once per forward, backward or decode step."""
+        fp32 mode), 1 = fp32 parameters, 2 = gradients.  Cached: a call is an index and an identity check, so the engine's pieces fetch them where they need them."""
         src = (self.flat_shadow if self.compute_dtype == torch.bfloat16 else self.flat_params, self.flat_params, self.flat_grads)[which]
         v = self._views[which]
         if v is None or v.src is not src:
@@ -608,171 +595,6 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
         ops.cka_pool(st["hidden"][1:], attention_mask, cfg.num_vision_tokens, out, rows)
         return out
 
-    # ---- engine ------------------------------------------------------------------------------------------------------
-    def _engine_forward(self, feats, input_ids, attention_mask, labels, want_hidden, train, n_hidden: Optional[int] = None,
-                        keep_qkv: bool = False, qkv_out: Optional[Sequence[torch.Tensor]] = None, label_rows_hint: Optional[int] = None,
-                        last_only: bool = False, skip_head: bool = False, pad_text: bool = False, head_rows: Optional[torch.Tensor] = None):
-        if not self.flat_params.is_cuda:
-            raise RuntimeError("mafed_amd runs on the GPU only (no CPU fallback); move the model with .cuda()")
-        pe, main_st = self._param_events, torch.cuda.current_stream()
-        if pe is not None:
-            main_st.wait_event(pe["pre"])
-        if self._shadow_dirty:
-            self.sync_shadow()
-        cfg, cd = self.config, self.compute_dtype
-        B, T_in = input_ids.shape
-        P, h, H, D, L = cfg.num_vision_tokens, cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim, cfg.num_hidden_layers
-        # ``pad_text`` (training, evaluation and teacher forwards; not the prefill, whose caches index real positions): masked positions
-        # behind the text bring the row count to a tile multiple (text_bucket).  Everything below, the activation record and the
-        # backward run at T; the public entry points trim what they hand out to ``T_in``.
-        T = bucket_text_len(self.text_bucket, B, P, T_in) if pad_text else T_in
-        if T != T_in:
-            input_ids, attention_mask, labels = ops.pad_text_batch(input_ids, attention_mask, labels, T)
-        S = P + T
-        rows = B * S
-        rot = cfg.rotary_ndims
-        cos, sin = self.rotary_tables(S)
-        wts, pars = self._tensors(0), self._tensors(1)   # compute-dtype weights; fp32 LayerNorm parameters, biases and embedding
-        Wo, Po = wts.outer, pars.outer
-        sv: Dict[str, Any] = {"B": B, "T": T, "T_in": T_in, "P": P, "S": S, "input_ids": input_ids, "attention_mask": attention_mask, "labels": labels,
-                              "layers": []}
-        # projector: Linear -> GELU(erf) -> Linear (vl_pythia.py:226-234,270)
-        f2 = feats.reshape(B * P, cfg.vision_hidden_size)
-        if f2.dtype not in (torch.float32, torch.bfloat16):
-            f2 = f2.float()
-        fc = f2.contiguous() if f2.dtype == cd else ops.cast(f2.contiguous(), cd)
-        u0 = torch.empty((B * P, h), dtype=cd, device=fc.device) if train else None
-        a0 = ops.gemm(fc, Wo.proj0_w, False, True, bias=Po.proj0_b, epilogue=EPI_GELU, aux=u0)
-        img = ops.gemm(a0, Wo.proj2_w, False, True, bias=Po.proj2_b)
-        x = ops.embed_concat_fwd(img, Po.embed_in, input_ids, B, P, T)  # fp32 residual stream
-        if train:
-            sv["proj"] = (fc, u0, a0)
-        hidden = [x.view(B, S, h)]
-        hook = self.hidden_ready_hook if train else None
-        if hook is not None:
-            hook(0, x)
-        n_layers = L if n_hidden is None else max(0, min(L, n_hidden - 1))
-        for i in range(n_layers):
-            w, p = wts.layers[i], pars.layers[i]
-            if pe is not None:
-                main_st.wait_event(pe[("layer", i)])
-            ln1, ln2, mean, rstd = ops.layernorm_fwd(x, p.ln1_w, p.ln1_b, p.ln2_w, p.ln2_b, cfg.layer_norm_eps, cd, save_stats=train)
-            qkv = ops.gemm(ln1, w.qkv_w, False, True, bias=p.qkv_b,
-                           out=qkv_out[i] if qkv_out is not None else None)  # (a captured decode graph reads its K/V cache at fixed addresses)
-            ao, lse = ops.attn_fwd(qkv, B, S, H, D, rot, cos, sin, attention_mask)
-            # the attention branch output is a bf16 tensor under the reference's autocast too (it meets the fp32 residual in the add)
-            attn = ops.gemm(ao, w.dense_w, False, True, bias=p.dense_b, out_dtype=cd)
-            u = torch.empty((rows, cfg.intermediate_size), dtype=cd, device=x.device) if train else None
-            a = ops.gemm(ln2, w.fc1_w, False, True, bias=p.fc1_b, epilogue=EPI_GELU, aux=u)
-            # h + attn(LN1(h)) + mlp(LN2(h)) in the last GEMM's epilogue (tf:271-274)
-            xn = ops.gemm(a, w.fc2_w, False, True, bias=p.fc2_b, out_dtype=torch.float32, res1=attn, res2=x)
-            if train:
-                sv["layers"].append({"x": x, "mean": mean, "rstd": rstd, "ln1": ln1, "ln2": ln2, "qkv": qkv, "ao": ao, "lse": lse, "u": u, "a": a})
-            elif keep_qkv:
-                sv["layers"].append({"qkv": qkv})  # the prefill's K/V cache: exactly what the fused QKV GEMM wrote
-            x = xn
-            if i < L - 1:
-                hidden.append(x.view(B, S, h))
-                if hook is not None:
-                    hook(i + 1, x)
-        sv["hidden"] = hidden
-        sv["loss"] = None
-        sv["logits"] = None
-        if pe is not None:  # from here on the caller's stream is ordered behind every chunk of the pipelined update
-            for k in range(n_layers, L):
-                main_st.wait_event(pe[("layer", k)])
-            main_st.wait_event(pe["head"])
-            self._param_events = None
-        if n_hidden is not None:
-            return sv
-        if last_only:
-            # a decode prefill only needs the last position's logits: final LN + head on B rows instead of B * T (-> logits [B, 1, V])
-            xl = x.view(B, S, h)[:, -1, :].contiguous()
-            lnl, _, _, _ = ops.layernorm_fwd(xl, Po.final_ln_w, Po.final_ln_b,
-                                             None, None, cfg.layer_norm_eps, cd, save_stats=False)
-            sv["logits"] = ops.gemm(lnl, Wo.embed_out, False, True).view(B, 1, cfg.vocab_size)
-            return sv
-        if skip_head:
-            # representation analysis: hidden_states[L] (the fp32 final-LN state) is the last thing anyone reads; no LM head, no loss
-            full, _, _, _ = ops.layernorm_fwd(x, Po.final_ln_w, Po.final_ln_b,
-                                              None, None, cfg.layer_norm_eps, torch.float32, save_stats=False)
-            hidden.append(full.view(B, S, h))
-            return sv
-        # final LN (fp32 hidden state L only when asked for) + LM head on the T text positions (vl_pythia.py:89,310)
-        xt = x.view(B, S, h)[:, P:, :].reshape(B * T, h)
-        if head_rows is not None:
-            # inference (head_logits_rows): final LN + head on the given text rows only -> logits [n, V]; a negative index is a row of zeros
-            assert not train and labels is None
-            lnc, _, _, _ = ops.layernorm_fwd(ops.gather_rows(xt, head_rows), Po.final_ln_w, Po.final_ln_b,
-                                             None, None, cfg.layer_norm_eps, cd, save_stats=False)
-            sv["logits"] = ops.gemm(lnc, Wo.embed_out, False, True)
-            return sv
-        lnf, _, fmean, frstd = ops.layernorm_fwd(xt, Po.final_ln_w, Po.final_ln_b,
-                                                 None, None, cfg.layer_norm_eps, cd, save_stats=train)
-        if want_hidden:
-            full, _, _, _ = ops.layernorm_fwd(x, Po.final_ln_w, Po.final_ln_b,
-                                              None, None, cfg.layer_norm_eps, torch.float32, save_stats=False)
-            hidden.append(full.view(B, S, h))
-        # Row-sparse head (training, with the caller's bound on labelled positions per sample): only rows whose shifted label is a token
-        # enter the head GEMM, the CE and -- in the backward -- the head's two gradient GEMMs: 4 answer tokens of 32 text positions in
-        # the VQA batches, i.e. 256 of 1024 rows at B = 32 (Rc = slots per sample incl. the unlabelled last one, B * Rc a tile multiple)
-        Rc = None
-        if train and labels is not None and label_rows_hint is not None:
-            need = max(2, int(label_rows_hint) + 1)   # (slots per sample incl. the unlabelled last one; a hint of 0 still gets two)
-            Rc = need if cd == torch.float32 else next((r for r in range(need, T + 1) if (B * r) % 128 == 0), None)  # (the MFMA tiles want whole 128-row tiles)
-            if Rc is not None and Rc * 2 > T:
-                Rc = None   # not worth it
-        if Rc is not None:
-            ros, sor, labels_c, ov = ops.label_rows(labels, Rc)
-            # device flag: 1 if a sample had more labelled positions than the hint promised -- rows were dropped; the CE below then
-            # returns NaN (no host synchronisation: the step fails loudly instead of training on a wrong loss)
-            self.last_label_overflow = ov
-            teacher = self._teacher_head_logits(sv, feats, ros) if self.logit_teacher is not None else None
-            lnf_c = ops.gather_rows(lnf, ros)
-            logits = ops.gemm(lnf_c, Wo.embed_out, False, True).view(B, Rc, cfg.vocab_size)
-            sv["logits"] = logits
-            if teacher is not None:
-                self._head_kd_loss(sv, logits, labels_c, teacher, ov)
-            else:
-                loss, lse_ce = ops.ce_fwd(logits, labels_c, poison=ov)
-                sv["loss"], sv["ce_lse"] = loss, lse_ce
-            sv["sparse_head"] = (sor, labels_c)
-            sv["final"] = (xt, lnf_c, fmean, frstd)
-            sv["x_last"] = x
-            return sv
-        teacher = self._teacher_head_logits(sv, feats, None) if (train and labels is not None and self.logit_teacher is not None) else None
-        logits = ops.gemm(lnf, Wo.embed_out, False, True).view(B, T, cfg.vocab_size)
-        sv["logits"] = logits
-        if teacher is not None:
-            self._head_kd_loss(sv, logits, labels, teacher, None)
-        elif labels is not None:
-            loss, lse_ce = ops.ce_fwd(logits, labels)
-            sv["loss"] = loss
-            if train:
-                sv["ce_lse"] = lse_ce
-        if train:
-            sv["final"] = (xt, lnf, fmean, frstd)
-            sv["x_last"] = x
-        return sv
-
-    def _teacher_head_logits(self, sv, feats, rows):
-        """``logit_teacher`` on the padded batch of this forward and the head's row selection (``rows``: the row-sparse head's
-        ``row_of_slot``, None = all text rows): (logits, tau, lambda).  Runs on the caller's stream, in front of the student's head."""
-        t_logits, tau, lam = self.logit_teacher(feats, sv["input_ids"], sv["attention_mask"], rows)
-        return t_logits.detach(), float(tau), float(lam)
-
-    def _head_kd_loss(self, sv, logits, labels, teacher, poison) -> None:
-        """Training head loss with a logit teacher: CE + lambda tau^2 KL against the teacher's logits of the same rows, one pass
-        (ops.ce_kd_fwd) -> sv["loss"], sv["kd"], ``last_head_losses``."""
-        t_logits, tau, lam = teacher
-        if t_logits.dtype != logits.dtype or t_logits.numel() != logits.numel():
-            raise ValueError(f"logit_teacher returned {tuple(t_logits.shape)} {t_logits.dtype} for head rows {tuple(logits.shape)} {logits.dtype}")
-        t_logits = t_logits.contiguous().view(logits.shape)
-        out3, lse3 = ops.ce_kd_fwd(logits, t_logits, labels, tau, lam, poison=poison)
-        sv["loss"] = out3[0:1]
-        sv["kd"] = (t_logits, lse3, tau, lam)
-        self.last_head_losses = out3
-
     @torch.no_grad()
     def head_logits_rows(self, feats, input_ids, attention_mask, rows: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Inference logits of a batch that is already at its padded length (pad_text_batch), for a frozen teacher: the stack, the final
@@ -797,321 +619,6 @@ class VLPythiaForCausalLM(GenerationMixin, nn.Module):
         self._engine_backward(sv, torch.ones(1, device=dev), [], taps=taps)
         S = sv["S"]
         return {l: _trim(t.view(sv["B"], S, -1), sv["P"] + sv["T_in"]) for l, t in taps.items()}
-
-    def _dw_group_fuses_squares(self, rows: int) -> bool:
-        """Will a grouped weight-gradient launch of this model (``dw_group_layers`` layers x four matrices, K = rows) emit the squares of
-        its outputs from the epilogue?  Asked of the library once per (rows, group size)."""
-        cache = self._dw_fuse_cache
-        key = (int(rows), int(self.dw_group_layers or 0))
-        if key not in cache:
-            cfg = self.config
-            h, f = cfg.hidden_size, cfg.intermediate_size
-            per_layer = [(3 * h, h, rows), (h, h, rows), (f, h, rows), (h, f, rows)]
-            n_layers = max(1, min(4, key[1]))
-            cache[key] = bool(key[1]) and ops.gemm_grouped_fuses_sumsq(per_layer * n_layers, True, False)
-        return cache[key]
-
-    def _engine_backward(self, sv, dloss: Optional[torch.Tensor], dhidden: Sequence[Optional[torch.Tensor]], taps=None):
-        # Data parallel, last micro-batch of a window: RCCL's all-reduce kernels hold a workgroup per channel for milliseconds while this
-        # backward runs.  The persistent GEMMs assume all 256 of their blocks are resident at once -- with 8 CUs taken the late blocks run
-        # a second wave and a launch takes 1.7x as long (tools/contention_bench.py: qkv 61.8 -> 105 us, grouped dW 440 -> 785), where the
-        # 128 x 128 kernels' many small blocks lose 1.1 - 1.45x.  So this backward runs on those (Trainer sets the flag).
-        # (per call: every GEMM this thread issues inside the block carries MAFED_EPI_NO_PERSISTENT; no process-wide switch is touched, a
-        #  forced tuning variant or another thread's / model's launches are unaffected)
-        cb = self.contended_backward
-        if cb and self.flat_params.is_cuda:
-            # "ticketed": the persistent kernels stay, their blocks draw tiles from per-XCD queues (MAFED_EPI_TICKETED) -- a launch then
-            # tolerates the CUs the collective holds (1.2 - 1.3x instead of 1.7 - 1.9x with 8 - 32 CUs taken, tools/contention_bench.py);
-            # True / "128x128": every GEMM of this backward on the 128 x 128 kernels (round 3's choice)
-            ctx = ops.ticketed_gemm() if cb == "ticketed" else ops.no_persistent_gemm()
-            with ctx:
-                return self._engine_backward_impl(sv, dloss, dhidden, taps)
-        return self._engine_backward_impl(sv, dloss, dhidden, taps)
-
-    def _engine_backward_impl(self, sv, dloss: Optional[torch.Tensor], dhidden: Sequence[Optional[torch.Tensor]], taps=None):
-        sweep = self.last_sweep = SweepRecord(self.last_sweep.serial + 1)
-        cfg, cd = self.config, self.compute_dtype
-        B, T, P, S = sv["B"], sv["T"], sv["P"], sv["S"]
-        h, H, D, L = cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim, cfg.num_hidden_layers
-        rows = B * S
-        rot = cfg.rotary_ndims
-        cos, sin = self.rotary_tables(S)
-        wts, pars, grads = self._tensors(0), self._tensors(1), self._tensors(2)   # compute-dtype weights, fp32 parameters, gradients
-        Wo, Po, Go = wts.outer, pars.outer, grads.outer
-        am = sv["attention_mask"]
-        dev = self.flat_params.device
-        if len(dhidden) > L and dhidden[L] is not None:
-            raise NotImplementedError("gradient w.r.t. the post-final-LayerNorm hidden state is not on the MAFED path")
-        inject = sv.get("inject")  # {layer: (teacher hidden state, device [4] = d loss / d {sum_lang, sum_vision, ., .})}
-        inj_cos = bool(sv.get("inject_cosine", False))   # the injected loss is the cosine distance, not the MSE
-        main = torch.cuda.current_stream()
-        sides = self.side_streams() if self.overlap_param_grads else None
-        keep: List[torch.Tensor] = []  # temporaries read by the side streams: kept alive until the join at the end
-        rr = [0]
-
-        mark = [None]  # event of the main stream's current position; dropped (main_moved) whenever more work is queued on it
-
-        def main_moved():
-            mark[0] = None
-
-        def on_side(fn, *tensors, k=None):
-            """Run parameter-gradient work after everything queued on the main stream so far, off the dX chain.  Consecutive
-            hand-offs with no main-stream work in between share one event: each record is a marker packet the dX chain's next
-            kernel waits behind (~4 us apiece in the step's timeline)."""
-            if sides is None:
-                fn()
-                return
-            if k is None:
-                k = rr[0] % len(sides)
-                rr[0] += 1
-            if mark[0] is None:
-                mark[0] = main.record_event()
-            ev = mark[0]
-            with torch.cuda.stream(sides[k]):
-                sides[k].wait_event(ev)
-                fn()
-            keep.extend(tensors)
-
-        def wgrad(dY, X, gw, gb=None):
-            """gw += dY^T . X (and gb += column sums of dY) on a side stream."""
-            def run():
-                ops.gemm(dY, X, True, False, out=gw, beta=1.0)
-                if gb is not None:
-                    ops.colsum_(dY, gb)
-            on_side(run, dY, X)
-
-        # layer weight gradients, grouped: (dY, X, gradient) records wait here (the list keeps dY / X alive) until `flush_dw`
-        # (beside collectives the weight gradients go back to one 128 x 128-kernel launch per product on the side streams, as in round 2:
-        #  a grouped call would fall back to eight serial launches on the dX chain's stream)
-        group_dw = (cd == torch.bfloat16 and int(self.dw_group_layers) > 0
-                    and self.contended_backward in (False, None, "ticketed"))
-        # First micro-batch of an accumulation window (Trainer sets ``grad_overwrite``): the grouped weight-gradient GEMMs WRITE the layers'
-        # matrix gradients (beta = 0) instead of adding to a zeroed buffer -- the optimiser pass then does not zero-write those 1.2 GB
-        # (FlatAdamW: ``skip_matrix_zero``) and the GEMM epilogues do not read them back.  ``_dw_stale`` = the last optimiser pass left the
-        # matrices un-zeroed: a sweep that accumulates anyway (another caller, another kernel path) zeroes them first.
-        overwrite = group_dw and bool(self.grad_overwrite) and taps is None
-        if self._dw_stale and not overwrite:
-            self._zero_layer_matrices(range(L))
-        self._dw_stale = False
-        dw_beta = 0.0 if overwrite else 1.0
-        # squares of the final matrix gradients from the weight-gradient epilogues (optim.IncrementalNorm.arm): only a sweep whose
-        # products all go through the grouped call can promise them -- its record says so, the norm hook checks it
-        dw_sq = self.dw_sumsq if (group_dw and taps is None) else None
-        if dw_sq is not None and not self._dw_group_fuses_squares(sv["B"] * sv["S"]):
-            dw_sq = None   # (h = 768 / 2048: the 256 x 256-tile kernel has no fused squares -- the norm hook's range pass is cheaper than a pass per matrix)
-        sweep.filled_squares = dw_sq is not None
-        pending_dw: List[dict] = []
-        pending_layers: List[int] = []
-
-        def wgrad_layer(dY, X, i, slot, with_bias=False):
-            """Weight gradient of layer i's matrix `slot` (0 .. 3 = query_key_value, dense, dense_h_to_4h, dense_4h_to_h: LayerTensors.matrix,
-            the order of ``dw_sumsq``), with its bias gradient if asked for."""
-            gw, gb = grads.layers[i].matrix(slot), grads.layers[i].bias(slot) if with_bias else None
-            if not group_dw:
-                wgrad(dY, X, gw, gb)
-                return
-            q = dict(A=dY, B=X, out=gw, beta=dw_beta)
-            if dw_sq is not None:
-                q["sumsq"] = dw_sq[i, slot]
-            pending_dw.append(q)
-            if gb is not None:
-                on_side(lambda: ops.colsum_(dY, gb), dY)
-
-        def flush_dw():
-            # at most PP_MAXP = 16 products per grouped launch (mafed_gemm_grouped launches larger lists one product at a time, serially on
-            # this stream -- worse than both forms): `dw_group_layers` >= 5 is cut into several launches
-            for c0 in range(0, len(pending_dw), 16):
-                ops.gemm_grouped(pending_dw[c0:c0 + 16], True, False)
-            if pending_dw:
-                pending_dw.clear()
-                main_moved()
-            for li in pending_layers:
-                ready(li)
-            pending_layers.clear()
-
-        def ready(i):
-            """Bucket hook: fires on side stream 0 once every side stream has finished the gradients queued so far."""
-            if self.grad_ready_hook is None:
-                return
-            if sides is None:
-                self.grad_ready_hook(i)
-                return
-            evs = [st.record_event() for st in sides[1:]]
-            def run():
-                for e in evs:
-                    sides[0].wait_event(e)
-                self.grad_ready_hook(i)
-            on_side(run, k=0)
-
-        # deferred LayerNorm parameter reduction: only with side streams and when no external hidden-state gradient adds into the
-        # same bias gradients from the main stream (generic autograd path of the cosine / CLS losses)
-        defer_ln = (sides is not None and self.defer_ln_param_reduce and taps is None
-                    and not any(d is not None for d in dhidden))
-        dx = None  # gradient w.r.t. the residual stream leaving the current layer, fp32 [rows, h]
-        if dloss is not None and sv["loss"] is not None:
-            xt, lnf, fmean, frstd = sv["final"]
-            logits = sv["logits"]
-            gl = dloss.reshape(1).to(torch.float32).contiguous()
-            sp = sv.get("sparse_head")   # (slot of every text row, compact labels): the head ran on the labelled rows only
-            n_head = logits.shape[0] * logits.shape[1]
-            head_labels = sp[1] if sp is not None else sv["labels"]
-            kd = sv.pop("kd", None)   # (teacher logits, lse3, tau, lambda): the head loss was CE + lambda tau^2 KL (_head_kd_loss)
-            if kd is not None:
-                dlog = ops.ce_kd_bwd(logits, kd[0], head_labels, kd[1], kd[2], kd[3], gl).view(n_head, cfg.vocab_size)
-            else:
-                dlog = ops.ce_bwd(logits, head_labels, sv["ce_lse"], gl).view(n_head, cfg.vocab_size)
-            wgrad(dlog, lnf, Go.embed_out)
-            if cd == torch.bfloat16:
-                # [rows, V] . [V, h]: few output tiles with K = 50304 -- accumulate-only fp32 output so that the GEMM splits K
-                dlnf = torch.zeros((n_head, h), dtype=torch.float32, device=dev)
-                ops.gemm(dlog, Wo.embed_out, False, False, out=dlnf, beta=1.0)
-            else:
-                dlnf = ops.gemm(dlog, Wo.embed_out, False, False)
-            if sp is not None:
-                dlnf = ops.gather_rows(dlnf if dlnf.dtype == torch.float32 else dlnf.float(), sp[0])   # back to the [B*T, h] text rows (zeros elsewhere)
-            if defer_ln:
-                dxt, _, fws = ops.layernorm_bwd_rows(dlnf, None, xt, fmean, frstd, Po.final_ln_w, None, None)
-                main_moved()
-                on_side(lambda ws=fws: ops.layernorm_bwd_params(ws, B * T, h, Go.final_ln_w, Go.final_ln_b), fws)
-            else:
-                dxt, _ = ops.layernorm_bwd(dlnf, None, xt, fmean, frstd, Po.final_ln_w, None, None,
-                                           Go.final_ln_w, Go.final_ln_b)
-            dx, dy0 = ops.pad_text_rows(dxt, B, S, P, cd if cd != torch.float32 else None)
-            main_moved()
-            ready(L)
-        else:
-            dy0 = None
-        dy = dy0  # dx in compute dtype (GEMM operand)
-        dy_bias_done = False  # colsum(dy) already accumulated into this layer's two residual-branch bias gradients
-        for i in range(L - 1, -1, -1):
-            ext = dhidden[i + 1] if (i + 1) < min(len(dhidden), L) else None  # grad of hidden_states[i+1] = output of layer i
-            if ext is not None:
-                ext = ext.reshape(rows, h)
-                if dx is not None and dy_bias_done:
-                    # the LayerNorm backward above already added colsum(dx) to this layer's bias gradients: add the rest
-                    ops.colsum_(ext.to(torch.float32).contiguous(), grads.layers[i].fc2_b)
-                    ops.colsum_(ext.to(torch.float32).contiguous(), grads.layers[i].dense_b)
-                dx = ext.to(torch.float32) if dx is None else dx.add_(ext)
-                dy = None
-                main_moved()
-            inj = inject.get(i) if inject else None
-            if dx is None:
-                # nothing flows into this layer's output (distillation of shallower layers only): its own backward is skipped,
-                # but a distilled hidden_states[i] (this layer's input) still starts the gradient for the layers below
-                if inj is not None:
-                    dx = ops.distill_bwd(sv["layers"][i]["x"].view(B, S, h), inj[0], am, P, inj[1], cosine=inj_cos).view(rows, h)
-                    main_moved()
-                if overwrite:
-                    self._zero_layer_matrices([i])   # (no weight-gradient GEMM will write this layer's matrices in this sweep)
-                    main_moved()
-                continue
-            if dy is None:
-                dy = dx if cd == torch.float32 else ops.cast(dx, cd)
-                main_moved()
-            w, p, g = wts.layers[i], pars.layers[i], grads.layers[i]
-            s = sv["layers"][i]
-            # parameter gradients that only need dy: MLP down-projection and attention output projection
-            wgrad_layer(dy, s["a"], i, 3, with_bias=not dy_bias_done)
-            wgrad_layer(dy, s["ao"], i, 1, with_bias=not dy_bias_done)
-            # MLP branch
-            # (the bias gradients of the two up-projections are column sums of du / dqkv: folded into the producing kernels)
-            du = ops.gemm(dy, w.fc2_w, False, False, epilogue=EPI_GELU_BWD, aux=s["u"], colsum=g.fc1_b)
-            main_moved()
-            wgrad_layer(du, s["ln2"], i, 2)
-            dln2 = ops.gemm(du, w.fc1_w, False, False)
-            # attention branch
-            dao = ops.gemm(dy, w.dense_w, False, False)
-            dqkv = ops.attn_bwd(s["qkv"], s["ao"], dao, s["lse"], B, S, H, D, rot, cos, sin, am, colsum=g.qkv_b)
-            main_moved()
-            wgrad_layer(dqkv, s["ln1"], i, 0)
-            dln1 = ops.gemm(dqkv, w.qkv_w, False, False)
-            # both LayerNorms + the residual path, one pass; also emits the compute-dtype copy the next layer's GEMMs read
-            ln_kw = dict(want_lp=(cd != torch.float32), teacher=(inj[0].view(rows, h) if torch.is_tensor(inj[0]) else inj[0]) if inj is not None else None,
-                         attention_mask=am if inj is not None else None, S=S, P=P, inj_scale=inj[1] if inj is not None else None,
-                         inj_mul=-1.0 if inj_cos else 2.0 / h)   # (a negative factor selects the cosine-distance gradient, mafed_hip.h)
-            dxa = grads.layers[i - 1].fc2_b if i > 0 else None   # colsum(dx) is the layer below's two residual-branch bias gradients
-            dxb = grads.layers[i - 1].dense_b if i > 0 else None
-            if defer_ln:
-                # row kernel on the dX chain; the slab reduction into the LayerNorm / bias gradients goes to a side stream (it feeds
-                # parameter gradients only, and on the main stream the whole chip waited for it once per layer)
-                dx, dy, ln_ws = ops.layernorm_bwd_rows(dln1, dln2, s["x"], s["mean"], s["rstd"], p.ln1_w, p.ln2_w, dx, want_dxsum=i > 0, **ln_kw)
-                main_moved()
-                on_side(lambda ws=ln_ws, g=g, dxa=dxa, dxb=dxb: ops.layernorm_bwd_params(
-                    ws, rows, h, g.ln1_w, g.ln1_b, g.ln2_w, g.ln2_b, dxa, dxb), ln_ws)
-            else:
-                dx, dy = ops.layernorm_bwd(dln1, dln2, s["x"], s["mean"], s["rstd"], p.ln1_w, p.ln2_w, dx, g.ln1_w, g.ln1_b, g.ln2_w, g.ln2_b,
-                                           dxsum_a=dxa, dxsum_b=dxb, **ln_kw)
-                main_moved()
-            dy_bias_done = i > 0
-            if cd == torch.float32:
-                dy = dx
-            if taps is not None and i in taps:
-                taps[i] = dx  # = dL/d hidden_states[i] (fresh buffer, never written again on this path)
-            if group_dw:
-                pending_layers.append(i)
-                if len(pending_layers) >= int(self.dw_group_layers):
-                    flush_dw()
-            else:
-                ready(i)
-        flush_dw()
-        # every layer's LayerNorm / distillation kernel -- the last readers of the teacher's hidden states -- is queued: a consumer
-        # that only has to stay behind THOSE (the next step's teacher forward re-uses that memory) can wait for this event instead of
-        # for the whole backward, whose side streams still carry ~0.3 ms of parameter-gradient tail
-        sweep.dx_chain_event = main.record_event()
-        ext0 = dhidden[0] if len(dhidden) > 0 else None
-        if ext0 is not None:
-            ext0 = ext0.reshape(rows, h)
-            dx = ext0.to(torch.float32).contiguous() if dx is None else dx.add_(ext0)
-            main_moved()
-        if dx is not None:
-            fc, u0, a0 = sv["proj"]
-            dimg = ops.embed_concat_bwd(dx, sv["input_ids"], B, P, T, h, cfg.vocab_size, Go.embed_in, cd)
-            main_moved()
-            wgrad(dimg, a0, Go.proj2_w, Go.proj2_b)
-            du0 = ops.gemm(dimg, Wo.proj2_w, False, False, epilogue=EPI_GELU_BWD, aux=u0, colsum=Go.proj0_b)
-            main_moved()
-            wgrad(du0, fc, Go.proj0_w)
-        ready(-1)
-        if sides is not None:
-            for st in sides:
-                main.wait_stream(st)  # gradients complete (and `keep` safe to release) from the main stream's point of view
-        keep.clear()
-
-
-class _ModelFn(torch.autograd.Function):
-    """The whole model as one autograd node: outputs (loss, logits, *hidden_states)."""
-
-    @staticmethod
-    def forward(ctx, anchor, model: VLPythiaForCausalLM, feats, input_ids, attention_mask, labels, want_hidden, ctx_box, label_rows_hint=None):
-        sv = model._engine_forward(feats, input_ids, attention_mask, labels, want_hidden, train=True, label_rows_hint=label_rows_hint, pad_text=True)
-        ctx.model, ctx.sv = model, sv
-        ctx_box.append(sv)
-        ctx.set_materialize_grads(False)  # outputs nobody differentiated arrive as None, not as zero tensors
-        # (a 0-dim view of the CE kernel's own output: a clone here was a device copy on the chain between forward and backward)
-        loss = sv["loss"].reshape(()) if sv["loss"] is not None else torch.zeros((), device=anchor.device)
-        # outs[2] is a 0-dim "hook": the fused distillation node takes it as an input so that this node's backward runs
-        # (after the distillation node has left its per-layer coefficients in sv["inject"]) even without a CE gradient; nobody reads
-        # its value, so it is not filled
-        pub = _trim(sv["logits"], sv["T_in"]) if sv.get("sparse_head") is None else torch.empty(0, device=anchor.device)   # compact logits are internal
-        # (one cached zero per device: an uninitialised scalar may hold NaN / Inf, which trips anomaly detection and would propagate if
-        #  autograd ever accumulated the hook's gradient with another path; re-using the tensor costs no fill kernel per step)
-        outs = [loss, pub.detach(), model._hook_zero().view(())]
-        ctx.mark_non_differentiable(outs[1])
-        if want_hidden:
-            outs += [x.detach() for x in sv["hidden"]]  # aliases: no reference cycle through ctx
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, dloss, dlogits, dhook, *dhidden):
-        sv = ctx.sv
-        ctx.sv = None
-        if sv is None:
-            raise RuntimeError("mafed_amd: backward through the model twice (activations already released)")
-        if sv["loss"] is None:
-            dloss = None
-        ctx.model._engine_backward(sv, dloss, list(dhidden))
-        sv.pop("inject", None)
-        return (None,) * 9
 
 
 model_architecture = {"vlpythia": VLPythiaForCausalLM}
