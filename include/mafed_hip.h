@@ -343,6 +343,21 @@ int mafed_ewc_penalty_fwd(const float* p, const float* p_old, const float* fishe
 int mafed_ewc_penalty_bwd(const float* p, const float* p_old, const float* fisher, int64_t n, float lambda,
                           const float* coef_dev, float* grad, void* stream);
 
+/* ---- A-GEM gradient projection (Chaudhry et al., 2019) ---------------------------------------
+ * On flat fp32 buffers, g = the step's gradient, r = the gradient of one replay-memory batch at the same parameters:
+ *   dots:    stats4 = {dot = sum g r, rsq = sum r r, alpha, violated} with alpha = dot / rsq and violated = 1 if dot < 0 and rsq > 0,
+ *            else alpha = 0 and violated = 0.  A non-finite dot or rsq gives alpha = NaN, violated = 1 (nothing is hidden: g' and its
+ *            norm are then non-finite and the optimiser's guard skips the step).  Per-block partials in the workspace
+ *            (mafed_agem_workspace_bytes), folded in double by one block: no atomics, the same bits on every run.
+ *   project: out[i] = g[i] - alpha * r[i] with alpha read from stats4[2] on the device; alpha == 0 copies g bit for bit (r is not read).  out may
+ *            alias r (or g).  sumsq_partials (or NULL) receives mafed_agem_blocks(n) sum-of-squares partials of out, which
+ *            mafed_gradnorm_finish folds into the clip norm.
+ * n == 0: dots writes stats4 = {0, 0, 0, 0}, project writes one zero partial. */
+size_t mafed_agem_workspace_bytes(int64_t n);
+int mafed_agem_blocks(int64_t n);
+int mafed_agem_dots(const float* g, const float* r, int64_t n, float* stats4, void* workspace, size_t workspace_bytes, void* stream);
+int mafed_agem_project(const float* g, const float* r, float* out, int64_t n, const float* stats4, float* sumsq_partials, void* stream);
+
 /* ---- representation-drift analysis: per-layer, per-modality linear CKA (mafed/analysis/) --------------------------
  * Modality pooling of one forward's hidden states (mafed/analysis/get_average_CKA_per_layer.py:107-118): for sample b and
  * layer l (hidden_host[l] = hidden_states[l + 1], fp32 [B, S, h], S = P + T)

@@ -53,6 +53,10 @@ SIGNATURES = {
     "mafed_ewc_workspace_bytes": (_z, [_l]),
     "mafed_ewc_penalty_fwd": (_i, [_p, _p, _p, _l, _f, _f, _p, _p, _z, _p]),
     "mafed_ewc_penalty_bwd": (_i, [_p, _p, _p, _l, _f, _p, _p, _p]),
+    "mafed_agem_workspace_bytes": (_z, [_l]),
+    "mafed_agem_blocks": (_i, [_l]),
+    "mafed_agem_dots": (_i, [_p, _p, _l, _p, _p, _z, _p]),
+    "mafed_agem_project": (_i, [_p, _p, _p, _l, _p, _p, _p]),
     "mafed_cka_pool": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _l, _p, _p]),
     "mafed_cka_stats_workspace_bytes": (_z, [_l, _l, _l]),
     "mafed_cka_stats": (_i, [_p, _l, _l, _l, _l, _l, _p, _p, _p, _z, _p]),

@@ -93,6 +93,7 @@ class BackwardSweep:
     def __init__(self, model, sv, dhidden: Sequence[Optional[torch.Tensor]], taps=None):
         self.model, self.sv, self.dhidden, self.taps = model, sv, dhidden, taps
         self.record = model.last_sweep = SweepRecord(model.last_sweep.serial + 1)
+        model.final_grad_sumsq = None   # a norm handed over for the buffer as it was (optim.FlatAdamW.clip_grad_norm_) is stale from here on
         cfg = self.cfg = model.config
         self.cd = model.compute_dtype
         self.B, self.T, self.P, self.S = sv["B"], sv["T"], sv["P"], sv["S"]

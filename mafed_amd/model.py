@@ -293,6 +293,9 @@ class VLPythiaForCausalLM(EngineMixin, GenerationMixin, nn.Module):
         self.grad_overwrite = False   # Trainer writes around a window's first backward: the sweep's grouped dW GEMMs write (beta = 0) the matrix gradients
         self._dw_stale = False        # an optimiser pass with skip_matrix_zero sets, the sweep and zero_grad clear: the matrix gradients hold the last window's values
         self.dw_sumsq: Optional[torch.Tensor] = None   # IncrementalNorm.arm / disarm write, the sweep and the norm hook read: fp32 [L, 4, 16] slots of the norm partials
+        # sum-of-squares partials of the WHOLE gradient buffer as it now is, left by a pass that wrote it behind the backward (A-GEM's projection):
+        # FlatAdamW.clip_grad_norm_ folds them instead of reading the buffer and clears them; every sweep and zero_grad drop them first
+        self.final_grad_sumsq: Optional[torch.Tensor] = None
         self.last_sweep = SweepRecord()
         self.reset_parameters(seed)
         self.register_load_state_dict_post_hook(lambda m, ik: setattr(m, "_shadow_dirty", True))
@@ -457,6 +460,7 @@ class VLPythiaForCausalLM(EngineMixin, GenerationMixin, nn.Module):
     def zero_grad(self, set_to_none: bool = False):  # gradients are views of the flat buffer: always zero in place
         self.flat_grads.zero_()
         self._dw_stale = False
+        self.final_grad_sumsq = None
 
     def layer_matrix_range(self, i: int) -> Tuple[int, int]:
         """Flat range of layer i's four weight matrices (query_key_value, dense, dense_h_to_4h, dense_4h_to_h: contiguous, behind the layer's

@@ -761,6 +761,43 @@ def ewc_penalty_bwd_(p: torch.Tensor, p_old: torch.Tensor, fisher: torch.Tensor,
           "mafed_ewc_penalty_bwd")
 
 
+def agem_blocks(n: int) -> int:
+    """Number of sum-of-squares partials ``agem_project`` writes for n elements."""
+    return int(_lib.load().mafed_agem_blocks(int(n)))
+
+
+def _agem_flat(*ts: torch.Tensor) -> None:
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 1 and t.numel() == ts[0].numel() for t in ts)
+
+
+def agem_dots(g: torch.Tensor, r: torch.Tensor, stats4: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> stats4 = {sum g r, sum r r, alpha, violated} over flat fp32 buffers (A-GEM: alpha = dot / rsq if dot < 0 and rsq > 0, else 0)."""
+    _agem_flat(g, r)
+    lib = _lib.load()
+    if stats4 is None:
+        stats4 = torch.empty(4, dtype=torch.float32, device=g.device)
+    assert stats4.dtype == torch.float32 and stats4.numel() == 4 and stats4.is_contiguous()
+    ws = workspace(g.device).get(lib.mafed_agem_workspace_bytes(g.numel()))
+    check(lib.mafed_agem_dots(_ptr(g), _ptr(r), g.numel(), _ptr(stats4), _ptr(ws), ws.numel(), _stream()), "mafed_agem_dots")
+    return stats4
+
+
+def agem_project(g: torch.Tensor, r: torch.Tensor, stats4: torch.Tensor, out: Optional[torch.Tensor] = None,
+                 sumsq_partials: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = g - stats4[2] * r (alpha is read on the device; 0 copies g bit for bit); ``out`` may be ``r``.  ``sumsq_partials``
+    [>= agem_blocks(n)] receives the sum-of-squares partials of ``out`` for ``gradnorm_finish``."""
+    _agem_flat(g, r)
+    if out is None:
+        out = torch.empty_like(g)
+    _agem_flat(g, out)
+    assert stats4.dtype == torch.float32 and stats4.numel() == 4 and stats4.is_contiguous()
+    if sumsq_partials is not None:
+        assert sumsq_partials.dtype == torch.float32 and sumsq_partials.is_contiguous() and sumsq_partials.numel() >= agem_blocks(g.numel())
+    check(_lib.load().mafed_agem_project(_ptr(g), _ptr(r), _ptr(out), g.numel(), _ptr(stats4), _ptr(sumsq_partials), _stream()),
+          "mafed_agem_project")
+    return out
+
+
 def cka_pool(hidden: Sequence[torch.Tensor], attention_mask: torch.Tensor, P: int, out: torch.Tensor, rows: Optional[torch.Tensor] = None) -> None:
     """out[0, l, rows[b]] = mean of hidden[l][b, :P]; out[1, l, rows[b]] = mean of the last sum(attention_mask[b]) rows of hidden[l][b]
     (fp32 hidden states [B, S, h], text mask [B, T], out fp32 [2, L, n, h])."""

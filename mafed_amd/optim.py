@@ -100,15 +100,17 @@ class IncrementalNorm:
         older partials behind: then the buffer is read in one pass)."""
         return self.seen is not None and len(self.seen) == len(self.plan) and all(v == serial for v in self.seen.values())
 
-    def finish(self, max_norm: float, clip_out: torch.Tensor, advance=None) -> torch.Tensor:
+    def finish(self, max_norm: float, clip_out: torch.Tensor, advance=None, partials: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Fold the partials into ``clip_out`` = {norm, clip scale} -> the norm.  ``advance`` (ops.gradnorm_finish): the schedule advance
-        rides in the same launch, and the norm also goes to a log slot of its own, which is what is returned."""
+        rides in the same launch, and the norm also goes to a log slot of its own, which is what is returned.  ``partials``: somebody
+        else's sum-of-squares partials of the whole buffer (``model.final_grad_sumsq``) instead of the hook's."""
+        partials = self.partials if partials is None else partials
         if advance is None:
-            ops.gradnorm_finish(self.partials, max_norm, clip_out)
+            ops.gradnorm_finish(partials, max_norm, clip_out)
             return clip_out[0]
         i = self.log_i % self.LOG_SLOTS
         self.log_i += 1
-        ops.gradnorm_finish(self.partials, max_norm, clip_out, norm_log=self.log[i:i + 1], advance=advance)
+        ops.gradnorm_finish(partials, max_norm, clip_out, norm_log=self.log[i:i + 1], advance=advance)
         return self.log[i]
 
 
@@ -205,16 +207,24 @@ class FlatAdamW:
         return self._advanced
 
     def clip_grad_norm_(self, max_norm: float, fuse_advance: bool = False) -> torch.Tensor:
-        """Global L2 norm + clip scale on the device; the scale is applied inside the AdamW kernel.  Uses the partials left by the
-        backward's hooks when every range reported in this backward, the single pass otherwise.
+        """Global L2 norm + clip scale on the device; the scale is applied inside the AdamW kernel.  Uses the partials handed over in
+        ``model.final_grad_sumsq`` if there are any, else those left by the backward's hooks when every range reported in this backward,
+        the single pass otherwise.
         ``fuse_advance`` (Trainer): with the partials present, the schedule advance of this optimiser step runs in the finish launch
         (advance() then does nothing) and the returned norm is a view of a log slot of its own -- valid until IncrementalNorm.LOG_SLOTS further
         optimiser steps have run -- instead of ``clip_out[0]``, which the next step overwrites (callers clone that one)."""
         out = self.clip_out[0]
-        if self.norm is not None and self.norm.complete(self.model.last_sweep.serial):
+        # sum-of-squares partials of the final gradient, left by whoever wrote it last (A-GEM's projection pass has every element in
+        # registers): folded instead of reading the buffer again, and used up.  Every backward sweep drops them at its start.
+        handed = getattr(self.model, "final_grad_sumsq", None)
+        if handed is not None:
+            self.model.final_grad_sumsq = None
+        advance = (self.state_dev, self.base_lr, self._sched[0], self._sched[1], self.betas[0], self.betas[1], self.lr_dev) if fuse_advance else None
+        if self.norm is not None and (handed is not None or self.norm.complete(self.model.last_sweep.serial)):
             self._advanced = self._advanced or fuse_advance
-            out = self.norm.finish(max_norm, self.clip_out, advance=(self.state_dev, self.base_lr, self._sched[0], self._sched[1], self.betas[0],
-                                                                     self.betas[1], self.lr_dev) if fuse_advance else None)
+            out = self.norm.finish(max_norm, self.clip_out, advance=advance, partials=handed)
+        elif handed is not None:   # (a model without the flat layer layout: no log slots, no fused advance)
+            ops.gradnorm_finish(handed, max_norm, self.clip_out)
         else:
             ops.gradnorm_clip(self.model.flat_grads, max_norm, self.clip_out)
         if self.norm is not None:

@@ -31,6 +31,9 @@ class Trainer:
                  process_group=None, ddp: bool = False, bucket_mb: float = 64.0, pipeline_optimizer: bool = False,
                  grad_dtype: Optional[torch.dtype] = None, reduce_mode: str = "all_reduce", incremental_norm: bool = True,
                  overwrite_weight_grads: bool = True, reducer=None):
+        if getattr(cl_method, "single_process_only", False) and (ddp or reducer is not None):
+            raise ValueError(f"{type(cl_method).__name__} is single-process only: it rewrites the gradients behind the backward, where a "
+                             "reducer's buckets have already left (ddp=True / reducer= are refused)")
         cfg = config if config is not None else SimpleNamespace()
         self.config = cfg
         self.model = model
