@@ -358,6 +358,26 @@ int mafed_agem_blocks(int64_t n);
 int mafed_agem_dots(const float* g, const float* r, int64_t n, float* stats4, void* workspace, size_t workspace_bytes, void* stream);
 int mafed_agem_project(const float* g, const float* r, float* out, int64_t n, const float* stats4, float* sumsq_partials, void* stream);
 
+/* ---- Synaptic Intelligence (Zenke, Poole, Ganguli 2017) ------------------------------------------
+ * On flat fp32 buffers laid out like the parameters p: the step gradient g, the path integral w, the importance omega, the anchor
+ * and the stash pair (stash_g, stash_p).
+ *   stash:       stash_g = g and stash_p = p, bit copies.  With omega and anchor (both or neither): g[i] += two_c * omega[i] * (p[i] -
+ *                anchor[i]) in place; without them g is only read.  sumsq_partials receives mafed_si_blocks(n) sum-of-squares
+ *                partials of the g it leaves (for mafed_gradnorm_finish), pen_partials as many partials of sum omega (p - anchor)^2
+ *                (zeros without omega).  No atomics: the same bits on every run.
+ *   penalty_finish: out[0] = c * sum of n_partials penalty partials, folded in double in a fixed order by one block.
+ *   accumulate:  w[i] -= stash_g[i] * (p[i] - stash_p[i]) where p[i] != stash_p[i]; an element that did not move keeps w[i] bit for
+ *                bit, whatever stash_g[i] holds (a select: a skipped step's non-finite gradient leaves no trace).
+ *   consolidate: omega[i] = max(omega[i] + w[i] / ((p[i] - anchor[i])^2 + xi), 0) by true division (a negative sum gives +0, a NaN
+ *                stays), then anchor[i] = p[i] and w[i] = 0.  xi > 0.
+ * n == 0: stash writes one zero partial of each kind, accumulate and consolidate do nothing. */
+int mafed_si_blocks(int64_t n);
+int mafed_si_stash(float* g, const float* p, const float* omega, const float* anchor, int64_t n, float two_c, float* stash_g,
+                   float* stash_p, float* sumsq_partials, float* pen_partials, void* stream);
+int mafed_si_penalty_finish(const float* pen_partials, int n_partials, float c, float* out, void* stream);
+int mafed_si_accumulate(const float* stash_g, const float* stash_p, const float* p, float* w, int64_t n, void* stream);
+int mafed_si_consolidate(const float* p, float* anchor, float* w, float* omega, int64_t n, float xi, void* stream);
+
 /* ---- representation-drift analysis: per-layer, per-modality linear CKA (mafed/analysis/) --------------------------
  * Modality pooling of one forward's hidden states (mafed/analysis/get_average_CKA_per_layer.py:107-118): for sample b and
  * layer l (hidden_host[l] = hidden_states[l + 1], fp32 [B, S, h], S = P + T)

@@ -57,6 +57,11 @@ SIGNATURES = {
     "mafed_agem_blocks": (_i, [_l]),
     "mafed_agem_dots": (_i, [_p, _p, _l, _p, _p, _z, _p]),
     "mafed_agem_project": (_i, [_p, _p, _p, _l, _p, _p, _p]),
+    "mafed_si_blocks": (_i, [_l]),
+    "mafed_si_stash": (_i, [_p, _p, _p, _p, _l, _f, _p, _p, _p, _p, _p]),
+    "mafed_si_penalty_finish": (_i, [_p, _i, _f, _p, _p]),
+    "mafed_si_accumulate": (_i, [_p, _p, _p, _p, _l, _p]),
+    "mafed_si_consolidate": (_i, [_p, _p, _p, _p, _l, _f, _p]),
     "mafed_cka_pool": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _l, _p, _p]),
     "mafed_cka_stats_workspace_bytes": (_z, [_l, _l, _l]),
     "mafed_cka_stats": (_i, [_p, _l, _l, _l, _l, _l, _p, _p, _p, _z, _p]),

@@ -1,0 +1,209 @@
+// Synaptic Intelligence (Zenke, Poole, Ganguli 2017) on the flat fp32 buffers.  State laid out like the
+// parameters: path integral w, importance Omega, anchor p*, and the stash pair (g^, p^) of the window that is being stepped.
+//   stash       (in front of the clip)   g^ = g   p^ = p   from task 1 on  g += 2c Omega (p - p*)  in place; leaves the sum-of-squares
+//                                        partials of the g it leaves (mafed_gradnorm_finish) and the partials of sum Omega (p - p*)^2
+//   accumulate  (behind the optimiser)   w -= g^ (p - p^)  where p != p^; an element that did not move keeps its w bit for bit
+//   consolidate (between tasks)          Omega = max(Omega + w / ((p - p*)^2 + xi), 0)   p* = p   w = 0
+// HBM-bound passes of 16 (task 0), 28, 20 and 28 bytes per parameter; the penalty never enters autograd and every scalar stays on the
+// device.
+#include "common.h"
+
+namespace mafed {
+
+constexpr int SI_BLOCKS = 2048;   // 8 blocks of 256 threads per CU, two 16-byte vectors per stream in flight per thread (the cap of agem.hip)
+
+__device__ __forceinline__ float sq4(const float4& a) { return (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w); }
+
+// One element of the penalty form: d = p - p*, t = Omega d, g' = fma(2c, t, g); pen += t d  (= Omega d^2)
+__device__ __forceinline__ float si_pen1(float g, float p, float om, float an, float two_c, float& pen) {
+  const float d = p - an, t = om * d;
+  pen += t * d;
+  return fmaf(two_c, t, g);
+}
+
+// One vector of the stash pass.  PEN = false: g is only read.  Every element is read and written by the same thread, all reads of a
+// trip in front of its writes -- hence no __restrict__ on g.
+template <bool PEN>
+__device__ __forceinline__ float4 si_stash4(float* g, const float* p, const float* om, const float* an, float* sg, float* sp, int64_t i4,
+                                            float two_c, float& pen) {
+  float4 a = load4(g + i4 * 4);
+  const float4 b = load4(p + i4 * 4);
+  store4(sg + i4 * 4, a);
+  store4(sp + i4 * 4, b);
+  if (PEN) {
+    const float4 o = load4(om + i4 * 4), q = load4(an + i4 * 4);
+    float p0 = 0.f, p1 = 0.f;
+    a.x = si_pen1(a.x, b.x, o.x, q.x, two_c, p0);
+    a.y = si_pen1(a.y, b.y, o.y, q.y, two_c, p1);
+    a.z = si_pen1(a.z, b.z, o.z, q.z, two_c, p0);
+    a.w = si_pen1(a.w, b.w, o.w, q.w, two_c, p1);
+    pen += p0 + p1;
+    store4(g + i4 * 4, a);
+  }
+  return a;
+}
+
+template <bool PEN>
+__global__ __launch_bounds__(256) void si_stash_kernel(float* g, const float* __restrict__ p, const float* __restrict__ om,
+                                                       const float* __restrict__ an, int64_t n, float two_c, float* __restrict__ sg,
+                                                       float* __restrict__ sp, float* __restrict__ sumsq, float* __restrict__ pen_out) {
+  __shared__ float sm[4];
+  const int64_t n4 = n / 4;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  float s0 = 0.f, s1 = 0.f, e0 = 0.f, e1 = 0.f;
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; i + stride < n4; i += 2 * stride) {
+    const float4 a = si_stash4<PEN>(g, p, om, an, sg, sp, i, two_c, e0), b = si_stash4<PEN>(g, p, om, an, sg, sp, i + stride, two_c, e1);
+    s0 += sq4(a);
+    s1 += sq4(b);
+  }
+  for (; i < n4; i += stride) s0 += sq4(si_stash4<PEN>(g, p, om, an, sg, sp, i, two_c, e0));
+  if (blockIdx.x == 0 && threadIdx.x < (n - n4 * 4)) {
+    const int64_t j = n4 * 4 + threadIdx.x;
+    float a = g[j];
+    const float b = p[j];
+    sg[j] = a;
+    sp[j] = b;
+    if (PEN) {
+      a = si_pen1(a, b, om[j], an[j], two_c, e0);
+      g[j] = a;
+    }
+    s0 += a * a;
+  }
+  const float s = block_sum<256>(s0 + s1, sm);
+  const float e = block_sum<256>(e0 + e1, sm);
+  if (threadIdx.x == 0) {
+    sumsq[blockIdx.x] = s;
+    pen_out[blockIdx.x] = e;
+  }
+}
+
+// sum of v over a 256-thread block in double, fixed association; valid in thread 0
+__device__ __forceinline__ double si_block_sum_f64(double v, double* sm) {
+  __syncthreads();
+  sm[threadIdx.x] = v;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) sm[threadIdx.x] += sm[threadIdx.x + w];
+    __syncthreads();
+  }
+  return sm[0];
+}
+
+// One block: the penalty partials folded in double (index order per thread, then a fixed tree) -> out[0] = c * sum
+__global__ __launch_bounds__(256) void si_penalty_finish_kernel(const float* __restrict__ partial, int nblk, float c, float* __restrict__ out) {
+  __shared__ double sm[256];
+  double e = 0.0;
+  for (int b = threadIdx.x; b < nblk; b += 256) e += (double)partial[b];
+  e = si_block_sum_f64(e, sm);
+  if (threadIdx.x == 0) out[0] = (float)((double)c * e);
+}
+
+// w' = w - g^ (p - p^) where the parameter moved; a select, not a multiply by zero: an unmoved element keeps its w whatever g^ holds
+// (the step the non-finite-norm guard skipped moved nothing and has a non-finite g^).
+__device__ __forceinline__ float si_acc1(float w, float sg, float sp, float p) { return p == sp ? w : fmaf(-sg, p - sp, w); }
+
+__device__ __forceinline__ float4 si_acc4(const float* sg, const float* sp, const float* p, const float* w, int64_t i4) {
+  const float4 a = load4(sg + i4 * 4), b = load4(sp + i4 * 4), c = load4(p + i4 * 4), d = load4(w + i4 * 4);
+  return make_float4(si_acc1(d.x, a.x, b.x, c.x), si_acc1(d.y, a.y, b.y, c.y), si_acc1(d.z, a.z, b.z, c.z), si_acc1(d.w, a.w, b.w, c.w));
+}
+
+__global__ __launch_bounds__(256) void si_accumulate_kernel(const float* __restrict__ sg, const float* __restrict__ sp,
+                                                            const float* __restrict__ p, float* w, int64_t n) {
+  const int64_t n4 = n / 4;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; i + stride < n4; i += 2 * stride) {
+    const float4 a = si_acc4(sg, sp, p, w, i), b = si_acc4(sg, sp, p, w, i + stride);
+    store4(w + i * 4, a);
+    store4(w + (i + stride) * 4, b);
+  }
+  for (; i < n4; i += stride) store4(w + i * 4, si_acc4(sg, sp, p, w, i));
+  if (blockIdx.x == 0 && threadIdx.x < (n - n4 * 4)) {
+    const int64_t j = n4 * 4 + threadIdx.x;
+    w[j] = si_acc1(w[j], sg[j], sp[j], p[j]);
+  }
+}
+
+// Omega' = max(Omega + w / ((p - p*)^2 + xi), 0): a true division; a negative sum gives exactly +0, a NaN stays a NaN
+__device__ __forceinline__ float si_cons1(float om, float w, float p, float an, float xi) {
+  const float d = p - an;
+  const float v = om + w / fmaf(d, d, xi);
+  return v < 0.f ? 0.f : v;
+}
+
+__device__ __forceinline__ void si_cons4(const float* p, float* an, float* w, float* om, int64_t i4, float xi) {
+  const float4 a = load4(p + i4 * 4), q = load4(an + i4 * 4), x = load4(w + i4 * 4), o = load4(om + i4 * 4);
+  store4(om + i4 * 4, make_float4(si_cons1(o.x, x.x, a.x, q.x, xi), si_cons1(o.y, x.y, a.y, q.y, xi), si_cons1(o.z, x.z, a.z, q.z, xi),
+                                  si_cons1(o.w, x.w, a.w, q.w, xi)));
+  store4(an + i4 * 4, a);
+  store4(w + i4 * 4, make_float4(0.f, 0.f, 0.f, 0.f));
+}
+
+__global__ __launch_bounds__(256) void si_consolidate_kernel(const float* __restrict__ p, float* __restrict__ an, float* __restrict__ w,
+                                                             float* __restrict__ om, int64_t n, float xi) {
+  const int64_t n4 = n / 4;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) si_cons4(p, an, w, om, i, xi);
+  if (blockIdx.x == 0 && threadIdx.x < (n - n4 * 4)) {
+    const int64_t j = n4 * 4 + threadIdx.x;
+    om[j] = si_cons1(om[j], w[j], p[j], an[j], xi);
+    an[j] = p[j];
+    w[j] = 0.f;
+  }
+}
+
+}  // namespace mafed
+
+using namespace mafed;
+
+extern "C" int mafed_si_blocks(int64_t n) {
+  int64_t nb = cdiv(n / 4 + 1, 256 * 4);
+  if (nb > SI_BLOCKS) nb = SI_BLOCKS;
+  if (nb < 1) nb = 1;
+  return (int)nb;
+}
+
+extern "C" int mafed_si_stash(float* g, const float* p, const float* omega, const float* anchor, int64_t n, float two_c, float* stash_g,
+                              float* stash_p, float* sumsq_partials, float* pen_partials, void* stream) {
+  MAFED_CHECK_ARG(sumsq_partials && pen_partials && n >= 0 && (n == 0 || (g && p && stash_g && stash_p)), "si_stash: bad arguments");
+  MAFED_CHECK_ARG((omega == nullptr) == (anchor == nullptr), "si_stash: omega and anchor come together");
+  MAFED_CHECK_ARG((((uintptr_t)g | (uintptr_t)p | (uintptr_t)omega | (uintptr_t)anchor | (uintptr_t)stash_g | (uintptr_t)stash_p) & 15) == 0,
+                  "si_stash: buffers must be 16-byte aligned");
+  const dim3 grid((unsigned)mafed_si_blocks(n));   // (n == 0: one block that writes a zero partial of each kind)
+  if (omega)
+    launch(K_SI, (double)n * 28.0, si_stash_kernel<true>, grid, dim3(256), 0, as_stream(stream), g, p, omega, anchor, n, two_c, stash_g, stash_p,
+           sumsq_partials, pen_partials);
+  else
+    launch(K_SI, (double)n * 16.0, si_stash_kernel<false>, grid, dim3(256), 0, as_stream(stream), g, p, omega, anchor, n, two_c, stash_g, stash_p,
+           sumsq_partials, pen_partials);
+  MAFED_CHECK_LAUNCH("si_stash");
+  return MAFED_OK;
+}
+
+extern "C" int mafed_si_penalty_finish(const float* pen_partials, int n_partials, float c, float* out, void* stream) {
+  MAFED_CHECK_ARG(pen_partials && out && n_partials >= 0, "si_penalty_finish: bad arguments");
+  launch(K_SMALL, 0.0, si_penalty_finish_kernel, dim3(1), dim3(256), 0, as_stream(stream), pen_partials, n_partials, c, out);
+  MAFED_CHECK_LAUNCH("si_penalty_finish");
+  return MAFED_OK;
+}
+
+extern "C" int mafed_si_accumulate(const float* stash_g, const float* stash_p, const float* p, float* w, int64_t n, void* stream) {
+  MAFED_CHECK_ARG(n >= 0 && (n == 0 || (stash_g && stash_p && p && w)), "si_accumulate: bad arguments");
+  MAFED_CHECK_ARG((((uintptr_t)stash_g | (uintptr_t)stash_p | (uintptr_t)p | (uintptr_t)w) & 15) == 0,
+                  "si_accumulate: buffers must be 16-byte aligned");
+  if (n == 0) return MAFED_OK;
+  launch(K_SI, (double)n * 20.0, si_accumulate_kernel, dim3((unsigned)mafed_si_blocks(n)), dim3(256), 0, as_stream(stream), stash_g, stash_p, p, w, n);
+  MAFED_CHECK_LAUNCH("si_accumulate");
+  return MAFED_OK;
+}
+
+extern "C" int mafed_si_consolidate(const float* p, float* anchor, float* w, float* omega, int64_t n, float xi, void* stream) {
+  MAFED_CHECK_ARG(n >= 0 && xi > 0.f && (n == 0 || (p && anchor && w && omega)), "si_consolidate: bad arguments (xi must be positive)");
+  MAFED_CHECK_ARG((((uintptr_t)p | (uintptr_t)anchor | (uintptr_t)w | (uintptr_t)omega) & 15) == 0,
+                  "si_consolidate: buffers must be 16-byte aligned");
+  if (n == 0) return MAFED_OK;
+  launch(K_SI, (double)n * 28.0, si_consolidate_kernel, dim3((unsigned)mafed_si_blocks(n)), dim3(256), 0, as_stream(stream), p, anchor, w, omega, n, xi);
+  MAFED_CHECK_LAUNCH("si_consolidate");
+  return MAFED_OK;
+}

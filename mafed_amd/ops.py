@@ -798,6 +798,45 @@ def agem_project(g: torch.Tensor, r: torch.Tensor, stats4: torch.Tensor, out: Op
     return out
 
 
+def si_blocks(n: int) -> int:
+    """Number of partials of each kind ``si_stash`` writes for n elements."""
+    return int(_lib.load().mafed_si_blocks(int(n)))
+
+
+def si_stash(g: torch.Tensor, p: torch.Tensor, omega: Optional[torch.Tensor], anchor: Optional[torch.Tensor], two_c: float,
+             stash_g: torch.Tensor, stash_p: torch.Tensor, sumsq_partials: torch.Tensor, pen_partials: torch.Tensor) -> None:
+    """stash_g = g, stash_p = p (bit copies); with ``omega`` / ``anchor``: g += two_c * omega * (p - anchor) in place.  ``sumsq_partials``
+    [>= si_blocks(n)] receives the sum-of-squares partials of the g it leaves (``gradnorm_finish``), ``pen_partials`` those of
+    sum omega (p - anchor)^2 (``si_penalty_finish``)."""
+    _agem_flat(g, p, stash_g, stash_p, *([] if omega is None else [omega, anchor]))
+    assert (omega is None) == (anchor is None)
+    nb = si_blocks(g.numel())
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= nb for t in (sumsq_partials, pen_partials))
+    check(_lib.load().mafed_si_stash(_ptr(g), _ptr(p), _ptr(omega), _ptr(anchor), g.numel(), float(two_c), _ptr(stash_g), _ptr(stash_p),
+                                     _ptr(sumsq_partials), _ptr(pen_partials), _stream()), "mafed_si_stash")
+
+
+def si_penalty_finish(pen_partials: torch.Tensor, c: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[0] = c * sum of the penalty partials (folded in double, fixed order)."""
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=pen_partials.device)
+    assert pen_partials.dtype == torch.float32 and pen_partials.is_contiguous() and out.dtype == torch.float32 and out.numel() == 1
+    check(_lib.load().mafed_si_penalty_finish(_ptr(pen_partials), pen_partials.numel(), float(c), _ptr(out), _stream()), "mafed_si_penalty_finish")
+    return out
+
+
+def si_accumulate_(stash_g: torch.Tensor, stash_p: torch.Tensor, p: torch.Tensor, w: torch.Tensor) -> None:
+    """w -= stash_g * (p - stash_p) where p != stash_p; an unmoved element keeps its w bit for bit."""
+    _agem_flat(stash_g, stash_p, p, w)
+    check(_lib.load().mafed_si_accumulate(_ptr(stash_g), _ptr(stash_p), _ptr(p), _ptr(w), w.numel(), _stream()), "mafed_si_accumulate")
+
+
+def si_consolidate_(p: torch.Tensor, anchor: torch.Tensor, w: torch.Tensor, omega: torch.Tensor, xi: float) -> None:
+    """omega = max(omega + w / ((p - anchor)^2 + xi), 0); anchor = p; w = 0."""
+    _agem_flat(p, anchor, w, omega)
+    check(_lib.load().mafed_si_consolidate(_ptr(p), _ptr(anchor), _ptr(w), _ptr(omega), p.numel(), float(xi), _stream()), "mafed_si_consolidate")
+
+
 def cka_pool(hidden: Sequence[torch.Tensor], attention_mask: torch.Tensor, P: int, out: torch.Tensor, rows: Optional[torch.Tensor] = None) -> None:
     """out[0, l, rows[b]] = mean of hidden[l][b, :P]; out[1, l, rows[b]] = mean of the last sum(attention_mask[b]) rows of hidden[l][b]
     (fp32 hidden states [B, S, h], text mask [B, T], out fp32 [2, L, n, h])."""
