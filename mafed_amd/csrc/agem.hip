@@ -4,15 +4,13 @@
 // Two HBM-bound passes, 8 and 12 bytes per parameter (8 and 8 when nothing is violated); every scalar stays on the device (stats4) and
 // the second pass leaves the sum-of-squares partials of g' for the clip norm (mafed_gradnorm_finish), which then does not read the
 // buffer again.
-#include "common.h"
+#include "flat_pass.h"
 
 namespace mafed {
 
-constexpr int AGEM_BLOCKS = 2048;   // 8 blocks of 256 threads per CU, 4 x 16 bytes in flight per thread (the cap of ewc.hip)
-
-__device__ __forceinline__ float dot4(const float4& a, const float4& b) { return (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w); }
-
-// partial[b] = this block's share of sum g r, partial[gridDim.x + b] = its share of sum r r
+// partial[b] = this block's share of sum g r, partial[gridDim.x + b] = its share of sum r r.  The vectors of a pair go into (d0, q0)
+// and (d1, q1), a single vector and the tail into (d0, q0).  The loop of flat_pass2 written out: through the callables hipcc packs the
+// two sums into other lanes and contracts the other product of each a.x b.x + a.y b.y into the fma -- other bits in both sums.
 __global__ __launch_bounds__(256) void agem_dots_partial_kernel(const float* __restrict__ g, const float* __restrict__ r, int64_t n,
                                                                 float* __restrict__ partial) {
   __shared__ float sm[4];
@@ -22,12 +20,12 @@ __global__ __launch_bounds__(256) void agem_dots_partial_kernel(const float* __r
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   for (; i + stride < n4; i += 2 * stride) {
     const float4 ga = load4(g + i * 4), ra = load4(r + i * 4), gb = load4(g + (i + stride) * 4), rb = load4(r + (i + stride) * 4);
-    d0 += dot4(ga, ra); q0 += dot4(ra, ra);
-    d1 += dot4(gb, rb); q1 += dot4(rb, rb);
+    d0 += dot4(ga, ra); q0 += sq4(ra);
+    d1 += dot4(gb, rb); q1 += sq4(rb);
   }
   for (; i < n4; i += stride) {
     const float4 ga = load4(g + i * 4), ra = load4(r + i * 4);
-    d0 += dot4(ga, ra); q0 += dot4(ra, ra);
+    d0 += dot4(ga, ra); q0 += sq4(ra);
   }
   if (blockIdx.x == 0 && threadIdx.x < (n - n4 * 4)) {
     const int64_t j = n4 * 4 + threadIdx.x;
@@ -42,30 +40,15 @@ __global__ __launch_bounds__(256) void agem_dots_partial_kernel(const float* __r
   }
 }
 
-// sum of v over a 256-thread block in double, fixed association; valid in thread 0
-__device__ __forceinline__ double block_sum_f64(double v, double* sm) {
-  __syncthreads();
-  sm[threadIdx.x] = v;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) sm[threadIdx.x] += sm[threadIdx.x + w];
-    __syncthreads();
-  }
-  return sm[0];
-}
-
 // One block: the partials folded in double (index order per thread, then a fixed tree) -> stats4 = {dot, rsq, alpha, violated}.
 // A non-finite dot or rsq is not hidden: alpha = NaN (and violated = 1: the projection pass then poisons g', whose norm trips the
 // optimiser's non-finite guard).
 __global__ __launch_bounds__(256) void agem_dots_finish_kernel(const float* __restrict__ partial, int nblk, float* __restrict__ stats4) {
   __shared__ double sm[256];
-  double d = 0.0, q = 0.0;
-  for (int b = threadIdx.x; b < nblk; b += 256) {
-    d += (double)partial[b];
-    q += (double)partial[nblk + b];
-  }
-  d = block_sum_f64(d, sm);
-  q = block_sum_f64(q, sm);
+  double mine[2];
+  fold_partials_f64(partial, nblk, mine);
+  const double d = block_sum_f64(mine[0], sm);
+  const double q = block_sum_f64(mine[1], sm);
   if (threadIdx.x == 0) {
     const float dot = (float)d, rsq = (float)q;
     const bool finite = isfinite(dot) && isfinite(rsq);
@@ -87,32 +70,30 @@ __device__ __forceinline__ float4 project4(const float* g, const float* r, int64
   return make_float4(fmaf(-alpha, b.x, a.x), fmaf(-alpha, b.y, a.y), fmaf(-alpha, b.z, a.z), fmaf(-alpha, b.w, a.w));
 }
 
-// This thread's share of out = g - alpha r -> its share of sum out^2.  out may alias r (or g): every element is read and written by the
-// same thread, all reads of a trip in front of its writes -- hence no __restrict__ on g, r and out.
+// This thread's share of out = g - alpha r -> its share of sum out^2 (the vectors of a pair into s0 and s1, a single vector and the tail
+// into s0).  out may alias r (or g): every element is read and written by the same thread, all reads of a trip in front of its writes --
+// hence no __restrict__ on g, r and out.
 template <bool KEEP>
 __device__ __forceinline__ float project_pass(const float* g, const float* r, float* out, int64_t n, float alpha) {
-  const int64_t n4 = n / 4;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   float s0 = 0.f, s1 = 0.f;
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (; i + stride < n4; i += 2 * stride) {
-    const float4 a = project4<KEEP>(g, r, i, alpha), b = project4<KEEP>(g, r, i + stride, alpha);
-    store4(out + i * 4, a);
-    store4(out + (i + stride) * 4, b);
-    s0 += dot4(a, a);
-    s1 += dot4(b, b);
-  }
-  for (; i < n4; i += stride) {
-    const float4 a = project4<KEEP>(g, r, i, alpha);
-    store4(out + i * 4, a);
-    s0 += dot4(a, a);
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n - n4 * 4)) {
-    const int64_t j = n4 * 4 + threadIdx.x;
-    const float a = KEEP ? g[j] : fmaf(-alpha, r[j], g[j]);
-    out[j] = a;
-    s0 += a * a;
-  }
+  flat_pass2(n,
+             [&](int64_t i, int64_t j) {
+               const float4 a = project4<KEEP>(g, r, i, alpha), b = project4<KEEP>(g, r, j, alpha);
+               store4(out + i * 4, a);
+               store4(out + j * 4, b);
+               s0 += sq4(a);
+               s1 += sq4(b);
+             },
+             [&](int64_t i) {
+               const float4 a = project4<KEEP>(g, r, i, alpha);
+               store4(out + i * 4, a);
+               s0 += sq4(a);
+             },
+             [&](int64_t t) {
+               const float a = KEEP ? g[t] : fmaf(-alpha, r[t], g[t]);
+               out[t] = a;
+               s0 += a * a;
+             });
   return s0 + s1;
 }
 
@@ -133,19 +114,14 @@ __global__ __launch_bounds__(256) void agem_project_kernel(const float* g, const
 
 using namespace mafed;
 
-extern "C" int mafed_agem_blocks(int64_t n) {
-  int64_t nb = cdiv(n / 4 + 1, 256 * 4);
-  if (nb > AGEM_BLOCKS) nb = AGEM_BLOCKS;
-  if (nb < 1) nb = 1;
-  return (int)nb;
-}
+extern "C" int mafed_agem_blocks(int64_t n) { return flat_blocks(n, FLAT_BLOCKS_CAP); }
 
-extern "C" size_t mafed_agem_workspace_bytes(int64_t n) { (void)n; return (size_t)2 * AGEM_BLOCKS * sizeof(float); }
+extern "C" size_t mafed_agem_workspace_bytes(int64_t n) { (void)n; return (size_t)2 * FLAT_BLOCKS_CAP * sizeof(float); }
 
 extern "C" int mafed_agem_dots(const float* g, const float* r, int64_t n, float* stats4, void* workspace, size_t workspace_bytes,
                                void* stream) {
   MAFED_CHECK_ARG(stats4 && n >= 0 && (n == 0 || (g && r)), "agem_dots: bad arguments");
-  MAFED_CHECK_ARG((((uintptr_t)g | (uintptr_t)r) & 15) == 0, "agem_dots: buffers must be 16-byte aligned");
+  MAFED_CHECK_ARG(aligned16({g, r}), "agem_dots: buffers must be 16-byte aligned");
   if (!workspace || workspace_bytes < mafed_agem_workspace_bytes(n)) {
     set_error("agem_dots: workspace %zu < %zu", workspace_bytes, mafed_agem_workspace_bytes(n));
     return MAFED_EWORKSPACE;
@@ -162,7 +138,7 @@ extern "C" int mafed_agem_dots(const float* g, const float* r, int64_t n, float*
 extern "C" int mafed_agem_project(const float* g, const float* r, float* out, int64_t n, const float* stats4, float* sumsq_partials,
                                   void* stream) {
   MAFED_CHECK_ARG(stats4 && n >= 0 && (n == 0 || (g && r && out)), "agem_project: bad arguments");
-  MAFED_CHECK_ARG((((uintptr_t)g | (uintptr_t)r | (uintptr_t)out) & 15) == 0, "agem_project: buffers must be 16-byte aligned");
+  MAFED_CHECK_ARG(aligned16({g, r, out}), "agem_project: buffers must be 16-byte aligned");
   if (n == 0 && !sumsq_partials) return MAFED_OK;
   launch(K_GRADNORM, (double)n * 12.0, agem_project_kernel, dim3((unsigned)mafed_agem_blocks(n)), dim3(256), 0, as_stream(stream), g, r, out, n,
          stats4, sumsq_partials);

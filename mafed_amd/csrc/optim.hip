@@ -1,31 +1,21 @@
 // Flat-buffer optimiser kernels: global gradient L2 norm + clip scale (Lightning gradient_clip_val,
 // mafed/train.py:288), HF-style AdamW (mafed/optim/adamw.py:86-111) and torch.optim.Adam / Adamax (the other two choices of
 // configure_optimizers, vqa_cont_learner.py:71-128).  HBM-bound streaming, 16-byte accesses.
-#include "common.h"
+#include "flat_pass.h"
 
 namespace mafed {
 
-constexpr int GN_BLOCKS = 1024;
-
+// partial[b] = this block's share of sum g^2: the vectors of a pair into s0 and s1, a single vector and the tail into s0
 __global__ __launch_bounds__(256) void gradnorm_partial_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ partial) {
   __shared__ float sm[4];
-  const int64_t n4 = n / 4;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   float s0 = 0.f, s1 = 0.f;
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (; i + stride < n4; i += 2 * stride) {
-    const float4 a = load4(g + i * 4), b = load4(g + (i + stride) * 4);
-    s0 += (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w);
-    s1 += (b.x * b.x + b.y * b.y) + (b.z * b.z + b.w * b.w);
-  }
-  for (; i < n4; i += stride) {
-    const float4 a = load4(g + i * 4);
-    s0 += (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w);
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n - n4 * 4)) {
-    const float a = g[n4 * 4 + threadIdx.x];
-    s0 += a * a;
-  }
+  flat_pass2(n,
+             [&](int64_t i, int64_t j) {
+               const float4 a = load4(g + i * 4), b = load4(g + j * 4);
+               s0 += sq4(a);
+               s1 += sq4(b);
+             },
+             [&](int64_t i) { s0 += sq4(load4(g + i * 4)); }, [&](int64_t t) { s0 += g[t] * g[t]; });
   const float s = block_sum<256>(s0 + s1, sm);
   if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
@@ -33,16 +23,8 @@ __global__ __launch_bounds__(256) void gradnorm_partial_kernel(const float* __re
 // sumsq16[blockIdx & 15] += sum of squares of this block's share of x (the unfused form of the weight-gradient epilogue's squares)
 __global__ __launch_bounds__(256) void sumsq_accumulate_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ sumsq16) {
   __shared__ float sm[4];
-  const int64_t n4 = n / 4, stride = (int64_t)gridDim.x * blockDim.x;
   float s0 = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
-    const float4 a = load4(x + i * 4);
-    s0 += (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w);
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n - n4 * 4)) {
-    const float a = x[n4 * 4 + threadIdx.x];
-    s0 += a * a;
-  }
+  flat_pass1(n, [&](int64_t i) { s0 += sq4(load4(x + i * 4)); }, [&](int64_t t) { s0 += x[t] * x[t]; });
   const float s = block_sum<256>(s0, sm);
   if (threadIdx.x == 0) atomicAdd(sumsq16 + (blockIdx.x & 15), s);
 }
@@ -292,21 +274,21 @@ extern "C" int mafed_optim_advance_guarded(int64_t* state_dev, double base_lr, i
 }
 
 extern "C" int mafed_sumsq_accumulate(const float* x, int64_t n, float* sumsq16, void* stream) {
-  MAFED_CHECK_ARG(x && sumsq16 && n >= 0 && ((uintptr_t)x & 15) == 0, "sumsq_accumulate: bad arguments");
+  MAFED_CHECK_ARG(x && sumsq16 && n >= 0 && aligned16({x}), "sumsq_accumulate: bad arguments");
   if (n == 0) return MAFED_OK;
   launch(K_GRADNORM, (double)n * 4.0, sumsq_accumulate_kernel, dim3((unsigned)mafed_gradnorm_blocks(n)), dim3(256), 0, as_stream(stream), x, n, sumsq16);
   MAFED_CHECK_LAUNCH("sumsq_accumulate");
   return MAFED_OK;
 }
 
-extern "C" size_t mafed_gradnorm_workspace_bytes(int64_t n) { (void)n; return (size_t)GN_BLOCKS * sizeof(float); }
+extern "C" size_t mafed_gradnorm_workspace_bytes(int64_t n) { (void)n; return (size_t)NORM_BLOCKS_CAP * sizeof(float); }
 
 extern "C" int mafed_gradnorm_clip(const float* g, int64_t n, float max_norm, float* out2, void* workspace, size_t workspace_bytes,
                                    void* stream) {
   MAFED_CHECK_ARG(g && out2 && n >= 0, "gradnorm_clip: bad arguments");
-  MAFED_CHECK_ARG(((uintptr_t)g & 15) == 0, "gradnorm_clip: g must be 16-byte aligned");
-  if (!workspace || workspace_bytes < GN_BLOCKS * sizeof(float)) {
-    set_error("gradnorm_clip: workspace %zu < %zu", workspace_bytes, (size_t)GN_BLOCKS * sizeof(float));
+  MAFED_CHECK_ARG(aligned16({g}), "gradnorm_clip: g must be 16-byte aligned");
+  if (!workspace || workspace_bytes < NORM_BLOCKS_CAP * sizeof(float)) {
+    set_error("gradnorm_clip: workspace %zu < %zu", workspace_bytes, (size_t)NORM_BLOCKS_CAP * sizeof(float));
     return MAFED_EWORKSPACE;
   }
   hipStream_t st = as_stream(stream);
@@ -322,16 +304,11 @@ extern "C" int mafed_gradnorm_clip(const float* g, int64_t n, float max_norm, fl
 // on whatever stream finished it), then one finish over all partials.  With these the optimiser step keeps only the last range and
 // the finish on its critical path instead of a 1.6 GB pass (0.28 ms at 410M).  Deterministic: every range has a fixed block count
 // and the finish adds the partials in index order.
-extern "C" int mafed_gradnorm_blocks(int64_t n) {
-  int64_t nb = cdiv(n / 4 + 1, 256 * 4);
-  if (nb > GN_BLOCKS) nb = GN_BLOCKS;
-  if (nb < 1) nb = 1;
-  return (int)nb;
-}
+extern "C" int mafed_gradnorm_blocks(int64_t n) { return flat_blocks(n, NORM_BLOCKS_CAP); }
 
 extern "C" int mafed_gradnorm_partial(const float* g, int64_t n, float* partial_out, void* stream) {
   MAFED_CHECK_ARG(g && partial_out && n >= 0, "gradnorm_partial: bad arguments");
-  MAFED_CHECK_ARG(((uintptr_t)g & 15) == 0, "gradnorm_partial: g must be 16-byte aligned");
+  MAFED_CHECK_ARG(aligned16({g}), "gradnorm_partial: g must be 16-byte aligned");
   launch(K_GRADNORM, (double)n * 4.0, gradnorm_partial_kernel, dim3((unsigned)mafed_gradnorm_blocks(n)), dim3(256), 0, as_stream(stream), g, n, partial_out);
   MAFED_CHECK_LAUNCH("gradnorm_partial");
   return MAFED_OK;
@@ -365,7 +342,7 @@ static int adam_family_impl(AdamRule rule, const char* name, float* p, float* g,
                             void* p_bf16, int64_t zero_n, void* stream) {
   MAFED_CHECK_ARG(p && g && m && s && lr_dev && n >= 0 && step >= 0, "%s: bad arguments", name);
   MAFED_CHECK_ARG(zero_n >= 0 && zero_n <= n && (zero_n == n || zero_n % 4 == 0), "%s: zero_n must be 0 .. n and a multiple of 4 (or n)", name);
-  MAFED_CHECK_ARG((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)s) & 15) == 0, "%s: buffers must be 16-byte aligned", name);
+  MAFED_CHECK_ARG(aligned16({p, g, m, s}), "%s: buffers must be 16-byte aligned", name);
   MAFED_CHECK_ARG(!p_bf16 || ((uintptr_t)p_bf16 & 7) == 0, "%s: p_bf16 must be 8-byte aligned", name);
   MAFED_CHECK_ARG(rule == RULE_ADAMW || (beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0 && eps >= 0.f && weight_decay >= 0.f),
                   "%s: betas must be in [0, 1), eps and weight_decay >= 0", name);

@@ -6,13 +6,9 @@
 //   consolidate (between tasks)          Omega = max(Omega + w / ((p - p*)^2 + xi), 0)   p* = p   w = 0
 // HBM-bound passes of 16 (task 0), 28, 20 and 28 bytes per parameter; the penalty never enters autograd and every scalar stays on the
 // device.
-#include "common.h"
+#include "flat_pass.h"
 
 namespace mafed {
-
-constexpr int SI_BLOCKS = 2048;   // 8 blocks of 256 threads per CU, two 16-byte vectors per stream in flight per thread (the cap of agem.hip)
-
-__device__ __forceinline__ float sq4(const float4& a) { return (a.x * a.x + a.y * a.y) + (a.z * a.z + a.w * a.w); }
 
 // One element of the penalty form: d = p - p*, t = Omega d, g' = fma(2c, t, g); pen += t d  (= Omega d^2)
 __device__ __forceinline__ float si_pen1(float g, float p, float om, float an, float two_c, float& pen) {
@@ -43,33 +39,32 @@ __device__ __forceinline__ float4 si_stash4(float* g, const float* p, const floa
   return a;
 }
 
+// sumsq[b], pen_out[b] = this block's shares of sum g'^2 and sum Omega (p - p*)^2: the vectors of a pair into (s0, e0) and (s1, e1),
+// a single vector and the tail into (s0, e0)
 template <bool PEN>
 __global__ __launch_bounds__(256) void si_stash_kernel(float* g, const float* __restrict__ p, const float* __restrict__ om,
                                                        const float* __restrict__ an, int64_t n, float two_c, float* __restrict__ sg,
                                                        float* __restrict__ sp, float* __restrict__ sumsq, float* __restrict__ pen_out) {
   __shared__ float sm[4];
-  const int64_t n4 = n / 4;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   float s0 = 0.f, s1 = 0.f, e0 = 0.f, e1 = 0.f;
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (; i + stride < n4; i += 2 * stride) {
-    const float4 a = si_stash4<PEN>(g, p, om, an, sg, sp, i, two_c, e0), b = si_stash4<PEN>(g, p, om, an, sg, sp, i + stride, two_c, e1);
-    s0 += sq4(a);
-    s1 += sq4(b);
-  }
-  for (; i < n4; i += stride) s0 += sq4(si_stash4<PEN>(g, p, om, an, sg, sp, i, two_c, e0));
-  if (blockIdx.x == 0 && threadIdx.x < (n - n4 * 4)) {
-    const int64_t j = n4 * 4 + threadIdx.x;
-    float a = g[j];
-    const float b = p[j];
-    sg[j] = a;
-    sp[j] = b;
-    if (PEN) {
-      a = si_pen1(a, b, om[j], an[j], two_c, e0);
-      g[j] = a;
-    }
-    s0 += a * a;
-  }
+  flat_pass2(n,
+             [&](int64_t i, int64_t j) {
+               const float4 a = si_stash4<PEN>(g, p, om, an, sg, sp, i, two_c, e0), b = si_stash4<PEN>(g, p, om, an, sg, sp, j, two_c, e1);
+               s0 += sq4(a);
+               s1 += sq4(b);
+             },
+             [&](int64_t i) { s0 += sq4(si_stash4<PEN>(g, p, om, an, sg, sp, i, two_c, e0)); },
+             [&](int64_t t) {
+               float a = g[t];
+               const float b = p[t];
+               sg[t] = a;
+               sp[t] = b;
+               if (PEN) {
+                 a = si_pen1(a, b, om[t], an[t], two_c, e0);
+                 g[t] = a;
+               }
+               s0 += a * a;
+             });
   const float s = block_sum<256>(s0 + s1, sm);
   const float e = block_sum<256>(e0 + e1, sm);
   if (threadIdx.x == 0) {
@@ -78,24 +73,12 @@ __global__ __launch_bounds__(256) void si_stash_kernel(float* g, const float* __
   }
 }
 
-// sum of v over a 256-thread block in double, fixed association; valid in thread 0
-__device__ __forceinline__ double si_block_sum_f64(double v, double* sm) {
-  __syncthreads();
-  sm[threadIdx.x] = v;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) sm[threadIdx.x] += sm[threadIdx.x + w];
-    __syncthreads();
-  }
-  return sm[0];
-}
-
 // One block: the penalty partials folded in double (index order per thread, then a fixed tree) -> out[0] = c * sum
 __global__ __launch_bounds__(256) void si_penalty_finish_kernel(const float* __restrict__ partial, int nblk, float c, float* __restrict__ out) {
   __shared__ double sm[256];
-  double e = 0.0;
-  for (int b = threadIdx.x; b < nblk; b += 256) e += (double)partial[b];
-  e = si_block_sum_f64(e, sm);
+  double mine[1];
+  fold_partials_f64(partial, nblk, mine);
+  const double e = block_sum_f64(mine[0], sm);
   if (threadIdx.x == 0) out[0] = (float)((double)c * e);
 }
 
@@ -110,19 +93,14 @@ __device__ __forceinline__ float4 si_acc4(const float* sg, const float* sp, cons
 
 __global__ __launch_bounds__(256) void si_accumulate_kernel(const float* __restrict__ sg, const float* __restrict__ sp,
                                                             const float* __restrict__ p, float* w, int64_t n) {
-  const int64_t n4 = n / 4;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (; i + stride < n4; i += 2 * stride) {
-    const float4 a = si_acc4(sg, sp, p, w, i), b = si_acc4(sg, sp, p, w, i + stride);
-    store4(w + i * 4, a);
-    store4(w + (i + stride) * 4, b);
-  }
-  for (; i < n4; i += stride) store4(w + i * 4, si_acc4(sg, sp, p, w, i));
-  if (blockIdx.x == 0 && threadIdx.x < (n - n4 * 4)) {
-    const int64_t j = n4 * 4 + threadIdx.x;
-    w[j] = si_acc1(w[j], sg[j], sp[j], p[j]);
-  }
+  flat_pass2(n,
+             [&](int64_t i, int64_t j) {
+               const float4 a = si_acc4(sg, sp, p, w, i), b = si_acc4(sg, sp, p, w, j);
+               store4(w + i * 4, a);
+               store4(w + j * 4, b);
+             },
+             [&](int64_t i) { store4(w + i * 4, si_acc4(sg, sp, p, w, i)); },
+             [&](int64_t t) { w[t] = si_acc1(w[t], sg[t], sp[t], p[t]); });
 }
 
 // Omega' = max(Omega + w / ((p - p*)^2 + xi), 0): a true division; a negative sum gives exactly +0, a NaN stays a NaN
@@ -142,34 +120,25 @@ __device__ __forceinline__ void si_cons4(const float* p, float* an, float* w, fl
 
 __global__ __launch_bounds__(256) void si_consolidate_kernel(const float* __restrict__ p, float* __restrict__ an, float* __restrict__ w,
                                                              float* __restrict__ om, int64_t n, float xi) {
-  const int64_t n4 = n / 4;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) si_cons4(p, an, w, om, i, xi);
-  if (blockIdx.x == 0 && threadIdx.x < (n - n4 * 4)) {
-    const int64_t j = n4 * 4 + threadIdx.x;
-    om[j] = si_cons1(om[j], w[j], p[j], an[j], xi);
-    an[j] = p[j];
-    w[j] = 0.f;
-  }
+  flat_pass1(n, [&](int64_t i) { si_cons4(p, an, w, om, i, xi); },
+             [&](int64_t t) {
+               om[t] = si_cons1(om[t], w[t], p[t], an[t], xi);
+               an[t] = p[t];
+               w[t] = 0.f;
+             });
 }
 
 }  // namespace mafed
 
 using namespace mafed;
 
-extern "C" int mafed_si_blocks(int64_t n) {
-  int64_t nb = cdiv(n / 4 + 1, 256 * 4);
-  if (nb > SI_BLOCKS) nb = SI_BLOCKS;
-  if (nb < 1) nb = 1;
-  return (int)nb;
-}
+extern "C" int mafed_si_blocks(int64_t n) { return flat_blocks(n, FLAT_BLOCKS_CAP); }
 
 extern "C" int mafed_si_stash(float* g, const float* p, const float* omega, const float* anchor, int64_t n, float two_c, float* stash_g,
                               float* stash_p, float* sumsq_partials, float* pen_partials, void* stream) {
   MAFED_CHECK_ARG(sumsq_partials && pen_partials && n >= 0 && (n == 0 || (g && p && stash_g && stash_p)), "si_stash: bad arguments");
   MAFED_CHECK_ARG((omega == nullptr) == (anchor == nullptr), "si_stash: omega and anchor come together");
-  MAFED_CHECK_ARG((((uintptr_t)g | (uintptr_t)p | (uintptr_t)omega | (uintptr_t)anchor | (uintptr_t)stash_g | (uintptr_t)stash_p) & 15) == 0,
-                  "si_stash: buffers must be 16-byte aligned");
+  MAFED_CHECK_ARG(aligned16({g, p, omega, anchor, stash_g, stash_p}), "si_stash: buffers must be 16-byte aligned");
   const dim3 grid((unsigned)mafed_si_blocks(n));   // (n == 0: one block that writes a zero partial of each kind)
   if (omega)
     launch(K_SI, (double)n * 28.0, si_stash_kernel<true>, grid, dim3(256), 0, as_stream(stream), g, p, omega, anchor, n, two_c, stash_g, stash_p,
@@ -190,8 +159,7 @@ extern "C" int mafed_si_penalty_finish(const float* pen_partials, int n_partials
 
 extern "C" int mafed_si_accumulate(const float* stash_g, const float* stash_p, const float* p, float* w, int64_t n, void* stream) {
   MAFED_CHECK_ARG(n >= 0 && (n == 0 || (stash_g && stash_p && p && w)), "si_accumulate: bad arguments");
-  MAFED_CHECK_ARG((((uintptr_t)stash_g | (uintptr_t)stash_p | (uintptr_t)p | (uintptr_t)w) & 15) == 0,
-                  "si_accumulate: buffers must be 16-byte aligned");
+  MAFED_CHECK_ARG(aligned16({stash_g, stash_p, p, w}), "si_accumulate: buffers must be 16-byte aligned");
   if (n == 0) return MAFED_OK;
   launch(K_SI, (double)n * 20.0, si_accumulate_kernel, dim3((unsigned)mafed_si_blocks(n)), dim3(256), 0, as_stream(stream), stash_g, stash_p, p, w, n);
   MAFED_CHECK_LAUNCH("si_accumulate");
@@ -200,8 +168,7 @@ extern "C" int mafed_si_accumulate(const float* stash_g, const float* stash_p, c
 
 extern "C" int mafed_si_consolidate(const float* p, float* anchor, float* w, float* omega, int64_t n, float xi, void* stream) {
   MAFED_CHECK_ARG(n >= 0 && xi > 0.f && (n == 0 || (p && anchor && w && omega)), "si_consolidate: bad arguments (xi must be positive)");
-  MAFED_CHECK_ARG((((uintptr_t)p | (uintptr_t)anchor | (uintptr_t)w | (uintptr_t)omega) & 15) == 0,
-                  "si_consolidate: buffers must be 16-byte aligned");
+  MAFED_CHECK_ARG(aligned16({p, anchor, w, omega}), "si_consolidate: buffers must be 16-byte aligned");
   if (n == 0) return MAFED_OK;
   launch(K_SI, (double)n * 28.0, si_consolidate_kernel, dim3((unsigned)mafed_si_blocks(n)), dim3(256), 0, as_stream(stream), p, anchor, w, omega, n, xi);
   MAFED_CHECK_LAUNCH("si_consolidate");

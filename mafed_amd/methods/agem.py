@@ -17,13 +17,14 @@ from typing import Optional
 import torch
 
 from mafed_amd import ops
+from mafed_amd.methods.flat import require_native
 from mafed_amd.methods.replay import ER
 
 
 class AGEM(ER):
     """A-GEM.  The memory, the constructor arguments and ``update(dataset, model=...)`` are ER's; the work is in
     ``update_after_backward`` (Lightning's on_before_optimizer_step)."""
-    grads_only_through_model = False   # the projection rewrites the gradient buffer behind the model's backward: one-pass / handed-over clip norm
+    grads_only_through_model = False   # (ER's is True) the projection rewrites the gradient buffer behind the model's backward: one-pass / handed-over clip norm
     single_process_only = True         # under DDP the projection would have to act on the reduced gradients (Trainer refuses a reducer)
 
     def __init__(self, opts, memory_size, model_type, **kwargs):
@@ -34,11 +35,11 @@ class AGEM(ER):
         # views of ``_stats`` (no host synchronisation); None until the first projection
         self.last_dot = self.last_ref_sq = self.last_alpha = self.last_projected = None
 
-    _FOREIGN = "AGEM needs the native model: the projection runs on its flat gradient buffer (model.flat_grads)"
+    _WHY_NATIVE = "the projection runs on its flat gradient buffer (model.flat_grads)"
 
     def update(self, dataset, model=None, **kwargs):
-        if model is not None and not hasattr(model, "flat_params"):
-            raise TypeError(self._FOREIGN)
+        if model is not None:
+            require_native(model, "AGEM", self._WHY_NATIVE)
         super().update(dataset, model=model, **kwargs)
 
     def replay(self, model, **kwargs):
@@ -51,8 +52,7 @@ class AGEM(ER):
     def update_after_backward(self, model=None, **kwargs) -> None:
         if self.task_id == 0 or self.mem_dataloader is None or len(self.mem_dataloader) == 0:
             return
-        if not hasattr(model, "flat_params"):
-            raise TypeError(self._FOREIGN)
+        require_native(model, "AGEM", self._WHY_NATIVE)
         g = model.flat_grads
         if self._stash is None or self._stash.shape != g.shape or self._stash.device != g.device:
             self._stash = torch.empty_like(g)

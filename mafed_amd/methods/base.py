@@ -13,6 +13,16 @@ Call order seen by a plugin:
                     update_after_backward(model=)                           Lightning's on_before_optimizer_step
                     [clip, optimiser step, scheduler step]
                     update_after_step(model=, batch_idx=)                   Lightning's on_train_batch_end
+
+Two class attributes are promises that Trainer reads off the plugin when it is built (with ``getattr(..., False)``, since it also
+takes plugin objects that do not derive from ``CLStrategy``).  ``CLStrategy`` declares both False; a subclass overrides one only
+where it differs.
+
+    grads_only_through_model   every parameter gradient of a step comes out of the model's own backward: nothing else writes to
+                               ``flat_grads`` between the backward and the clip.  Trainer then lets the backward sweep collect the
+                               clip norm incrementally; without the promise the norm is taken in one pass, or handed over by the plugin.
+    single_process_only        the plugin's hooks act on this process's gradients alone and would be wrong on reduced ones: Trainer
+                               refuses ``ddp=True`` / ``reducer=`` for such a plugin.
 """
 from __future__ import annotations
 
@@ -21,6 +31,8 @@ from typing import Any, Optional, Tuple
 
 class CLStrategy:
     """Base plugin.  Every hook is a no-op, ``compute_loss`` is abstract and ``replay`` reports "nothing replayed"."""
+    grads_only_through_model = False   # the two promises to Trainer (module docstring): neither is made by default
+    single_process_only = False
 
     def __init__(self, reg_lambda: float = 1.0, mask: Any = None, scaler: Any = None, **kwargs):
         self.reg_lambda = reg_lambda      # weight of a regularisation term (EWC); unused by MAFED

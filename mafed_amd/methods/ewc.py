@@ -14,14 +14,7 @@ import torch
 
 from mafed_amd import ops
 from mafed_amd.methods.base import CLStrategy
-
-
-class _FlatDict(dict):
-    """name -> view into one flat tensor (``.flat``)."""
-
-    def __init__(self, model, flat: torch.Tensor):
-        super().__init__({name: flat[o:o + n].view(shape) for name, (o, n, shape) in model._offsets.items()})
-        self.flat = flat
+from mafed_amd.methods.flat import FlatDict
 
 
 class _EwcPenaltyFn(torch.autograd.Function):
@@ -56,7 +49,7 @@ class EWC(CLStrategy):
     def update(self, model, dataloader, **kwargs):
         wimportances = self.compute_importances(model, dataloader)
         native = hasattr(model, "flat_params")
-        prev_w = _FlatDict(model, model.flat_params.detach().clone()) if native else {k: p.data.clone() for k, p in model.named_parameters()}
+        prev_w = FlatDict(model, model.flat_params.detach().clone()) if native else {k: p.data.clone() for k, p in model.named_parameters()}
         if self.online:
             if self.task_id <= 1:
                 self.fisher[0] = wimportances
@@ -94,14 +87,14 @@ class EWC(CLStrategy):
             seen += n
         model.zero_grad()
         if native:
-            return _FlatDict(model, acc.div_(seen))
+            return FlatDict(model, acc.div_(seen))
         torch._foreach_div_(acc, seen)
         return dict(zip(names, acc))
 
     # inside a step ---------------------------------------------------------------------------------------------------
     def compute_regularization(self, model, loss, task_id):
         fisher, old = self.fisher[task_id], self.old_params[task_id]
-        if hasattr(model, "flat_params") and isinstance(fisher, _FlatDict) and model.flat_params.is_cuda:
+        if hasattr(model, "flat_params") and isinstance(fisher, FlatDict) and model.flat_params.is_cuda:
             return loss + _EwcPenaltyFn.apply(model._anchor, model, old.flat, fisher.flat, float(self.reg_lambda))
         # foreign nn.Module: 0.5 * lambda * sum_k <F_k, (p_k - p*_k)^2> with multi-tensor ops (ewc.py:105-115)
         keys = [k for k, p in model.named_parameters() if p.requires_grad]

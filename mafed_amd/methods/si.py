@@ -24,16 +24,14 @@ import torch
 
 from mafed_amd import ops
 from mafed_amd.methods.base import CLStrategy
-from mafed_amd.methods.ewc import _FlatDict
+from mafed_amd.methods.flat import FlatDict, require_native
 
 
 class SI(CLStrategy):
     """``SI(reg_lambda=1.0, xi=1e-3)``.  ``xi`` damps the division where a parameter barely moved; 1e-3 is the paper's CIFAR value and has
     not been tuned for this model."""
-    grads_only_through_model = False   # pass A rewrites the gradient buffer behind the model's backward: handed-over clip norm
+    # grads_only_through_model stays False: pass A rewrites the gradient buffer behind the model's backward (handed-over clip norm)
     single_process_only = True         # under a reducer the hook runs before the reduced gradients exist (Trainer refuses one)
-
-    _FOREIGN = "SI needs the native model: its passes run on the flat buffers (model.flat_params / model.flat_grads)"
 
     def __init__(self, reg_lambda=1.0, xi=1e-3, **kwargs):
         super().__init__(reg_lambda, **{k: v for k, v in kwargs.items() if k in ("mask", "scaler", "opts")})
@@ -49,8 +47,7 @@ class SI(CLStrategy):
 
     # ---- buffers -----------------------------------------------------------------------------------------------------------
     def _native(self, model):
-        if not hasattr(model, "flat_params"):
-            raise TypeError(self._FOREIGN)
+        require_native(model, "SI", "its passes run on the flat buffers (model.flat_params / model.flat_grads)")
         return model.flat_params
 
     def _ensure(self, model) -> None:
@@ -68,12 +65,12 @@ class SI(CLStrategy):
             self._sumsq, self._pen = torch.zeros(nb, dtype=torch.float32, device=p.device), torch.zeros(nb, dtype=torch.float32, device=p.device)
             self.last_penalty = torch.zeros(1, dtype=torch.float32, device=p.device)[0]
 
-    def named(self, model, which: str = "omega") -> _FlatDict:
+    def named(self, model, which: str = "omega") -> FlatDict:
         """name -> view of ``omega`` / ``small_omega`` / ``anchor``, like EWC's ``fisher[0]``."""
         if which not in ("omega", "small_omega", "anchor"):
             raise KeyError(which)
         self._ensure(model)
-        return _FlatDict(model, getattr(self, which))
+        return FlatDict(model, getattr(self, which))
 
     @staticmethod
     def _behind_optimizer(model) -> None:

@@ -536,12 +536,11 @@ def sample_token(logits: torch.Tensor, temperature: float = 1.0, top_k: int = 0,
 def gemm_grouped_fuses_sumsq(shapes: Sequence[Tuple[int, int, int]], transA: bool, transB: bool) -> bool:
     """Would ``gemm_grouped`` run these (M, N, K) bf16 -> fp32 products as one persistent launch with the squares of C fused into its
     epilogue?  (host-side query, no launch)"""
-    import ctypes
     n = len(shapes)
-    arr = lambda k: (ctypes.c_int64 * n)(*[int(s[k]) for s in shapes])
+    arr = lambda k: (C.c_int64 * n)(*[int(s[k]) for s in shapes])
     Ms, Ns, Ks = arr(0), arr(1), arr(2)
-    return bool(_lib.load().mafed_gemm_grouped_fuses_sumsq(_lib.BF16, int(transA), int(transB), _lib.F32, ctypes.cast(Ms, ctypes.c_void_p),
-                                                           ctypes.cast(Ns, ctypes.c_void_p), ctypes.cast(Ks, ctypes.c_void_p), n))
+    return bool(_lib.load().mafed_gemm_grouped_fuses_sumsq(_lib.BF16, int(transA), int(transB), _lib.F32, C.cast(Ms, C.c_void_p),
+                                                           C.cast(Ns, C.c_void_p), C.cast(Ks, C.c_void_p), n))
 
 
 def decode_supported(M: int, h: int, n1: int) -> bool:
@@ -741,10 +740,15 @@ def distill_cls_bwd(s, t, coef) -> torch.Tensor:
     return out
 
 
+def _flat_f32(*ts: torch.Tensor) -> None:
+    """The flat-buffer passes take contiguous one-dimensional fp32 tensors of one length."""
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 1 and t.numel() == ts[0].numel() for t in ts)
+
+
 def ewc_penalty_fwd(p: torch.Tensor, p_old: torch.Tensor, fisher: torch.Tensor, half_lambda: float,
                     out: Optional[torch.Tensor] = None, beta: float = 0.0) -> torch.Tensor:
     """out[0] = beta * out[0] + half_lambda * sum fisher * (p - p_old)^2 over flat fp32 buffers."""
-    assert p.dtype == torch.float32 and p.is_contiguous() and p_old.shape == p.shape and fisher.shape == p.shape
+    _flat_f32(p, p_old, fisher)
     lib = _lib.load()
     if out is None:
         out = torch.zeros(1, dtype=torch.float32, device=p.device)
@@ -756,7 +760,8 @@ def ewc_penalty_fwd(p: torch.Tensor, p_old: torch.Tensor, fisher: torch.Tensor, 
 
 def ewc_penalty_bwd_(p: torch.Tensor, p_old: torch.Tensor, fisher: torch.Tensor, lam: float, coef: torch.Tensor, grad: torch.Tensor) -> None:
     """grad += coef[0] * lam * fisher * (p - p_old)"""
-    assert grad.dtype == torch.float32 and grad.shape == p.shape and coef.dtype == torch.float32
+    _flat_f32(p, p_old, fisher, grad)
+    assert coef.dtype == torch.float32
     check(_lib.load().mafed_ewc_penalty_bwd(_ptr(p), _ptr(p_old), _ptr(fisher), p.numel(), float(lam), _ptr(coef), _ptr(grad), _stream()),
           "mafed_ewc_penalty_bwd")
 
@@ -766,13 +771,9 @@ def agem_blocks(n: int) -> int:
     return int(_lib.load().mafed_agem_blocks(int(n)))
 
 
-def _agem_flat(*ts: torch.Tensor) -> None:
-    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 1 and t.numel() == ts[0].numel() for t in ts)
-
-
 def agem_dots(g: torch.Tensor, r: torch.Tensor, stats4: Optional[torch.Tensor] = None) -> torch.Tensor:
     """-> stats4 = {sum g r, sum r r, alpha, violated} over flat fp32 buffers (A-GEM: alpha = dot / rsq if dot < 0 and rsq > 0, else 0)."""
-    _agem_flat(g, r)
+    _flat_f32(g, r)
     lib = _lib.load()
     if stats4 is None:
         stats4 = torch.empty(4, dtype=torch.float32, device=g.device)
@@ -786,10 +787,10 @@ def agem_project(g: torch.Tensor, r: torch.Tensor, stats4: torch.Tensor, out: Op
                  sumsq_partials: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = g - stats4[2] * r (alpha is read on the device; 0 copies g bit for bit); ``out`` may be ``r``.  ``sumsq_partials``
     [>= agem_blocks(n)] receives the sum-of-squares partials of ``out`` for ``gradnorm_finish``."""
-    _agem_flat(g, r)
+    _flat_f32(g, r)
     if out is None:
         out = torch.empty_like(g)
-    _agem_flat(g, out)
+    _flat_f32(g, out)
     assert stats4.dtype == torch.float32 and stats4.numel() == 4 and stats4.is_contiguous()
     if sumsq_partials is not None:
         assert sumsq_partials.dtype == torch.float32 and sumsq_partials.is_contiguous() and sumsq_partials.numel() >= agem_blocks(g.numel())
@@ -808,7 +809,7 @@ def si_stash(g: torch.Tensor, p: torch.Tensor, omega: Optional[torch.Tensor], an
     """stash_g = g, stash_p = p (bit copies); with ``omega`` / ``anchor``: g += two_c * omega * (p - anchor) in place.  ``sumsq_partials``
     [>= si_blocks(n)] receives the sum-of-squares partials of the g it leaves (``gradnorm_finish``), ``pen_partials`` those of
     sum omega (p - anchor)^2 (``si_penalty_finish``)."""
-    _agem_flat(g, p, stash_g, stash_p, *([] if omega is None else [omega, anchor]))
+    _flat_f32(g, p, stash_g, stash_p, *([] if omega is None else [omega, anchor]))
     assert (omega is None) == (anchor is None)
     nb = si_blocks(g.numel())
     assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= nb for t in (sumsq_partials, pen_partials))
@@ -827,13 +828,13 @@ def si_penalty_finish(pen_partials: torch.Tensor, c: float, out: Optional[torch.
 
 def si_accumulate_(stash_g: torch.Tensor, stash_p: torch.Tensor, p: torch.Tensor, w: torch.Tensor) -> None:
     """w -= stash_g * (p - stash_p) where p != stash_p; an unmoved element keeps its w bit for bit."""
-    _agem_flat(stash_g, stash_p, p, w)
+    _flat_f32(stash_g, stash_p, p, w)
     check(_lib.load().mafed_si_accumulate(_ptr(stash_g), _ptr(stash_p), _ptr(p), _ptr(w), w.numel(), _stream()), "mafed_si_accumulate")
 
 
 def si_consolidate_(p: torch.Tensor, anchor: torch.Tensor, w: torch.Tensor, omega: torch.Tensor, xi: float) -> None:
     """omega = max(omega + w / ((p - anchor)^2 + xi), 0); anchor = p; w = 0."""
-    _agem_flat(p, anchor, w, omega)
+    _flat_f32(p, anchor, w, omega)
     check(_lib.load().mafed_si_consolidate(_ptr(p), _ptr(anchor), _ptr(w), _ptr(omega), p.numel(), float(xi), _stream()), "mafed_si_consolidate")
 
 
@@ -892,6 +893,7 @@ def cka_hsic(products: Sequence[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, 
 
 def gradnorm_clip(g: torch.Tensor, max_norm: float, out2: Optional[torch.Tensor] = None) -> torch.Tensor:
     """-> out[2] = {||g||, clip scale}"""
+    _flat_f32(g)
     lib = _lib.load()
     if out2 is None:
         out2 = torch.empty(2, dtype=torch.float32, device=g.device)
@@ -951,6 +953,7 @@ def gradnorm_blocks(n: int) -> int:
 
 def gradnorm_partial(g: torch.Tensor, partial_out: torch.Tensor) -> None:
     """sum-of-squares partials of the (contiguous, 16-byte aligned) range ``g`` -> partial_out[:gradnorm_blocks(g.numel())]"""
+    _flat_f32(g)
     check(_lib.load().mafed_gradnorm_partial(_ptr(g), g.numel(), _ptr(partial_out), _stream()), "mafed_gradnorm_partial")
 
 

@@ -11,7 +11,10 @@ from tests.test_gpu_model import DEV, build_model, check_named_grads, close, gra
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("n", [1, 7, 4096, 1000003])
+# The sizes of the other flat-buffer passes (tests/test_gpu_si.py): tail only, one vector, less than one block, several blocks and a
+# tail, and above 2 * 2048 * 256 * 4, where the grid at its cap takes more than one two-vector trip.  Without 0: both entry points
+# refuse an empty tensor's null pointer.
+@pytest.mark.parametrize("n", [1, 7, 4096, 1000003, 3, 4, 1023, 4 * 1024 + 1, 3 * 2 ** 21 + 5])
 def test_ewc_penalty_kernels(n):
     from mafed_amd import ops
     g = torch.Generator().manual_seed(n)
@@ -40,12 +43,12 @@ def test_ewc_step_with_synthetic_fisher_matches_reference_golden():
     """compute_regularization + its gradient, exact: the Fisher diagonal is the synthetic one the reference object was
     given when the fixture was made (no bf16 importance pass involved)."""
     from mafed_amd import CLMethod
-    from mafed_amd.methods.ewc import _FlatDict
+    from mafed_amd.methods.flat import FlatDict
     cfg, g, sd0, sd1, loaders, batch, syn = ewc_setup()
     model = build_model(cfg, sd1)
     ewc = CLMethod["ewc"](reg_lambda=float(g["reg_lambda"]))
-    ewc.fisher[0] = _FlatDict(model, _flat_of(cfg, syn))
-    ewc.old_params[0] = _FlatDict(model, _flat_of(cfg, sd0))
+    ewc.fisher[0] = FlatDict(model, _flat_of(cfg, syn))
+    ewc.old_params[0] = FlatDict(model, _flat_of(cfg, sd0))
     ewc.task_id = 1
     model.zero_grad()
     ce = model(**to_dev(batch), compute_loss=True, return_dict=True).loss

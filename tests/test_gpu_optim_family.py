@@ -40,6 +40,30 @@ def to_dev(batch):
     return {k: v.to(DEV) for k, v in batch.items()}
 
 
+# ---- 0. the piecewise clip norm at the sizes of the flat-buffer passes ----------------------------------------------------------
+@pytest.mark.parametrize("n", [1, 3, 4, 1023, 4 * 1024 + 1, 3 * 2 ** 21 + 5])
+def test_gradnorm_partial_and_finish_vs_one_pass_and_fp64(n):
+    """The sizes of tests/test_gpu_si.py: tail only (twice), one vector, less than one block, several blocks and a tail, and a grid at
+    its cap (1024 blocks here) that takes more than one two-vector trip; without 0, since gradnorm_partial refuses an empty tensor's
+    null pointer.  Exactly gradnorm_blocks(n) partials are written, run to run the same bits, and their fold equals the one-pass norm
+    and float64 to 1e-6."""
+    from mafed_amd import ops
+    g = torch.randn(n, generator=torch.Generator().manual_seed(3000 + n % 997)).to(DEV)
+    nb = ops.gradnorm_blocks(n)
+    partials, again = torch.full((nb + 3,), -7.0, device=DEV), torch.full((nb + 3,), -7.0, device=DEV)
+    ops.gradnorm_partial(g, partials)
+    ops.gradnorm_partial(g, again)
+    assert 1 <= nb <= 1024 and bool((partials[nb:] == -7.0).all()) and torch.equal(partials.view(torch.int32), again.view(torch.int32))
+    folded = ops.gradnorm_finish(partials[:nb], 2.0, torch.empty(2, device=DEV))
+    ref64 = float(g.double().square().sum().sqrt())
+    print(f"[gradnorm] n {n}: {nb} partials, norm {float(folded[0]):.8g} (fp64 {ref64:.8g})")
+    one_pass = ops.gradnorm_clip(g, 2.0)
+    for i, what in enumerate(("norm", "clip scale")):
+        a, b = float(folded[i]), float(one_pass[i])
+        assert abs(a - b) <= 1e-6 * abs(b), f"{what}: folded {a} vs one pass {b}"
+    assert abs(float(folded[0]) - ref64) <= 1e-6 * ref64
+
+
 # ---- 1. the kernels against torch in fp64 --------------------------------------------------------------------------------------
 @pytest.mark.parametrize("rule", list(RULES))
 def test_kernel_vs_torch_fp64(rule):

@@ -292,8 +292,8 @@ def _si_run(cls, c, dtype=torch.float32, overwrite=True, pipeline=False, checks=
 
 
 def _views(model, flat):
-    from mafed_amd.methods.ewc import _FlatDict
-    return _FlatDict(model, flat)
+    from mafed_amd.methods.flat import FlatDict
+    return FlatDict(model, flat)
 
 
 def test_si_trainer_matches_torch_double():

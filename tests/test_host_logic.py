@@ -36,6 +36,29 @@ def test_registry_and_protocol():
     assert n.task_id == 1
 
 
+def test_plugin_promises_to_the_trainer_are_declared():
+    """grads_only_through_model / single_process_only (methods/base.py): declared False on the base, overridden only where they differ."""
+    from mafed_amd import AGEM, CLStrategy, ER, EWC, FeatureDistillation, LwF, Naive, SI
+    promises = lambda cls: (cls.grads_only_through_model, cls.single_process_only)
+    assert promises(CLStrategy) == (False, False) and {"grads_only_through_model", "single_process_only"} <= set(vars(CLStrategy))
+    for cls in (Naive, ER, LwF, FeatureDistillation):
+        assert promises(cls) == (True, False), cls.__name__
+    for cls in (AGEM, SI):
+        assert promises(cls) == (False, True), cls.__name__
+    assert promises(EWC) == (False, False)
+    assert not {"grads_only_through_model", "single_process_only"} & set(vars(EWC))   # nothing restated where nothing differs
+
+
+def test_flat_pass_block_counts_follow_the_closed_formula():
+    """The three grid-size queries (host-side, no launch): clamp(ceil((n // 4 + 1) / 1024), 1, cap) with cap 1024 for the clip norm and
+    2048 for A-GEM and SI.  The sizes sit on both sides of one block, of either cap, and at 2^31."""
+    from mafed_amd import ops
+    want = lambda n, cap: min(max(-(-(n // 4 + 1) // 1024), 1), cap)
+    for n in (0, 1, 3, 4, 4091, 4092, 4096, 4 * 1024 * 1024 - 4, 4 * 1024 * 1024, 4 * 1024 * 2048, 2 ** 31):
+        assert ops.gradnorm_blocks(n) == want(n, 1024), n
+        assert ops.agem_blocks(n) == ops.si_blocks(n) == want(n, 2048), n
+
+
 def test_distillation_weights_match_reference_vectors():
     from mafed_amd.methods import DistillationWeights
     g = load_golden("optim.npz")
