@@ -378,6 +378,23 @@ int mafed_si_penalty_finish(const float* pen_partials, int n_partials, float c, 
 int mafed_si_accumulate(const float* stash_g, const float* stash_p, const float* p, float* w, int64_t n, void* stream);
 int mafed_si_consolidate(const float* p, float* anchor, float* w, float* omega, int64_t n, float xi, void* stream);
 
+/* ---- Memory Aware Synapses (Aljundi et al. 2018) --------------------------------------------------
+ * On flat fp32 buffers laid out like the parameters p: the gradient g, the importance accumulator acc, the importance omega, the anchor.
+ *   accumulate:  acc[i] = fma(weight, |g[i]|, acc[i])  (one batch of the importance pass; the sign of g, a -0.0 included, is dropped).
+ *   consolidate: first != 0: omega[i] = inv_seen * acc[i] (omega is not read);  else omega[i] = alpha * omega[i] + (1 - alpha) * inv_seen *
+ *                acc[i] as fma(alpha, omega, k acc) with k = (1 - alpha) * inv_seen folded in double.  Then anchor[i] = p[i], acc[i] = 0.
+ *                inv_seen > 0, 0 <= alpha <= 1.
+ *   penalty:     g[i] += two_c * omega[i] * (p[i] - anchor[i]) in place: the arithmetic, the partials (mafed_mas_blocks(n) of each kind,
+ *                == mafed_si_blocks(n)) and the bits of mafed_si_stash with omega and anchor, without the stash.  sumsq_partials goes to
+ *                mafed_gradnorm_finish, pen_partials to mafed_si_penalty_finish.  No atomics: the same bits on every run.
+ * n == 0: penalty writes one zero partial of each kind, accumulate and consolidate do nothing. */
+int mafed_mas_blocks(int64_t n);
+int mafed_mas_accumulate(const float* g, float* acc, int64_t n, float weight, void* stream);
+int mafed_mas_consolidate(float* acc, float* omega, const float* p, float* anchor, int64_t n, float inv_seen, float alpha, int first,
+                          void* stream);
+int mafed_mas_penalty(float* g, const float* p, const float* omega, const float* anchor, int64_t n, float two_c, float* sumsq_partials,
+                      float* pen_partials, void* stream);
+
 /* ---- representation-drift analysis: per-layer, per-modality linear CKA (mafed/analysis/) --------------------------
  * Modality pooling of one forward's hidden states (mafed/analysis/get_average_CKA_per_layer.py:107-118): for sample b and
  * layer l (hidden_host[l] = hidden_states[l + 1], fp32 [B, S, h], S = P + T)
@@ -435,6 +452,19 @@ int mafed_ce_fwd_guarded(const void* logits, mafed_dtype dtype, const int64_t* l
  * gloss_dev: device scalar (upstream dL/dloss).  dlogits may alias logits. */
 int mafed_ce_bwd(const void* logits, mafed_dtype dtype, const int64_t* labels, const float* lse, int B, int T, int64_t V,
                  const float* gloss_dev, void* dlogits, void* stream);
+
+/* ---- squared-norm head objective (the MAS importance pass) ----------------------------------
+ * logits, labels, the shift, V % 4 == 0 and the alignment as for mafed_ce_fwd; a row (b,t) is labelled when t < T-1 and labels[b,t+1] != -100.
+ * The label values are not used otherwise.
+ *   fwd: rowsq fp32 [B,T] = sum_c logits[b,t,c]^2 on labelled rows, 0 elsewhere; out fp32 [1] = J = mean_b( sum_t rowsq[b,t] /
+ *        max(count_b, 1e-13) ).  poison_flag (may be NULL): a non-zero device flag turns J into NaN (mafed_ce_fwd_guarded).
+ *   bwd: dlogits[b,t,:] = dloss * 2 logits[b,t,:] / (B * max(count_b, 1e-13)) on labelled rows, exact zeros elsewhere, in `dtype`; no
+ *        forward output is needed.  dloss_dev: device scalar (upstream dL/dJ).  dlogits: a buffer of its own.
+ * No atomics, no workspace: the same bits on every call. */
+int mafed_sqnorm_fwd(const void* logits, mafed_dtype dtype, const int64_t* labels, int B, int T, int64_t V, float* rowsq, float* out,
+                     const int* poison_flag, void* stream);
+int mafed_sqnorm_bwd(const void* logits, mafed_dtype dtype, const int64_t* labels, int B, int T, int64_t V, const float* dloss_dev,
+                     void* dlogits, void* stream);
 
 /* ---- LwF head loss: the cross-entropy above + temperature-softened logit distillation, one pass per direction ----
  * student, teacher: logits [B,T,V] of the same head rows in `dtype` (F32 or BF16; the teacher's are a frozen model's); labels as above.

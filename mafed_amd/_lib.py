@@ -62,6 +62,10 @@ SIGNATURES = {
     "mafed_si_penalty_finish": (_i, [_p, _i, _f, _p, _p]),
     "mafed_si_accumulate": (_i, [_p, _p, _p, _p, _l, _p]),
     "mafed_si_consolidate": (_i, [_p, _p, _p, _p, _l, _f, _p]),
+    "mafed_mas_blocks": (_i, [_l]),
+    "mafed_mas_accumulate": (_i, [_p, _p, _l, _f, _p]),
+    "mafed_mas_consolidate": (_i, [_p, _p, _p, _p, _l, _f, _f, _i, _p]),
+    "mafed_mas_penalty": (_i, [_p, _p, _p, _p, _l, _f, _p, _p, _p]),
     "mafed_cka_pool": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _l, _p, _p]),
     "mafed_cka_stats_workspace_bytes": (_z, [_l, _l, _l]),
     "mafed_cka_stats": (_i, [_p, _l, _l, _l, _l, _l, _p, _p, _p, _z, _p]),
@@ -87,6 +91,8 @@ SIGNATURES = {
     "mafed_ce_fwd": (_i, [_p, _i, _p, _i, _i, _l, _p, _p, _p, _p]),
     "mafed_ce_fwd_guarded": (_i, [_p, _i, _p, _i, _i, _l, _p, _p, _p, _p, _p]),
     "mafed_ce_bwd": (_i, [_p, _i, _p, _p, _i, _i, _l, _p, _p, _p]),
+    "mafed_sqnorm_fwd": (_i, [_p, _i, _p, _i, _i, _l, _p, _p, _p, _p]),
+    "mafed_sqnorm_bwd": (_i, [_p, _i, _p, _i, _i, _l, _p, _p, _p]),
     "mafed_ce_kd_fwd": (_i, [_p, _p, _i, _p, _i, _i, _l, _f, _f, _p, _p, _p, _p, _p, _p]),
     "mafed_ce_kd_bwd": (_i, [_p, _p, _i, _p, _p, _i, _i, _l, _f, _f, _p, _p, _p]),
     "mafed_distill_workspace_bytes": (_z, [_l]),

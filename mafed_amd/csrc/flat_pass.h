@@ -1,4 +1,4 @@
-// The one copy of what the HBM-bound passes over the flat fp32 buffers share (clip norm: optim.hip; EWC: ewc.hip; A-GEM: agem.hip;
+// The one copy of what the HBM-bound passes over the flat fp32 buffers share (clip norm: optim.hip; EWC: ewc.hip; A-GEM: agem.hip; MAS: mas.hip;
 // SI: si.hip): the grid-stride loops with their n % 4 tail, the grid size, the float4 dot, the double fold of a finish kernel and the
 // entry points' alignment check.  A kernel's body shows its arithmetic and nothing else.
 #pragma once

@@ -6,72 +6,9 @@
 //   consolidate (between tasks)          Omega = max(Omega + w / ((p - p*)^2 + xi), 0)   p* = p   w = 0
 // HBM-bound passes of 16 (task 0), 28, 20 and 28 bytes per parameter; the penalty never enters autograd and every scalar stays on the
 // device.
-#include "flat_pass.h"
+#include "penalty_pass.h"   // the stash pass is penalty_pass_kernel<PEN, STASH = true>, shared with mas.hip
 
 namespace mafed {
-
-// One element of the penalty form: d = p - p*, t = Omega d, g' = fma(2c, t, g); pen += t d  (= Omega d^2)
-__device__ __forceinline__ float si_pen1(float g, float p, float om, float an, float two_c, float& pen) {
-  const float d = p - an, t = om * d;
-  pen += t * d;
-  return fmaf(two_c, t, g);
-}
-
-// One vector of the stash pass.  PEN = false: g is only read.  Every element is read and written by the same thread, all reads of a
-// trip in front of its writes -- hence no __restrict__ on g.
-template <bool PEN>
-__device__ __forceinline__ float4 si_stash4(float* g, const float* p, const float* om, const float* an, float* sg, float* sp, int64_t i4,
-                                            float two_c, float& pen) {
-  float4 a = load4(g + i4 * 4);
-  const float4 b = load4(p + i4 * 4);
-  store4(sg + i4 * 4, a);
-  store4(sp + i4 * 4, b);
-  if (PEN) {
-    const float4 o = load4(om + i4 * 4), q = load4(an + i4 * 4);
-    float p0 = 0.f, p1 = 0.f;
-    a.x = si_pen1(a.x, b.x, o.x, q.x, two_c, p0);
-    a.y = si_pen1(a.y, b.y, o.y, q.y, two_c, p1);
-    a.z = si_pen1(a.z, b.z, o.z, q.z, two_c, p0);
-    a.w = si_pen1(a.w, b.w, o.w, q.w, two_c, p1);
-    pen += p0 + p1;
-    store4(g + i4 * 4, a);
-  }
-  return a;
-}
-
-// sumsq[b], pen_out[b] = this block's shares of sum g'^2 and sum Omega (p - p*)^2: the vectors of a pair into (s0, e0) and (s1, e1),
-// a single vector and the tail into (s0, e0)
-template <bool PEN>
-__global__ __launch_bounds__(256) void si_stash_kernel(float* g, const float* __restrict__ p, const float* __restrict__ om,
-                                                       const float* __restrict__ an, int64_t n, float two_c, float* __restrict__ sg,
-                                                       float* __restrict__ sp, float* __restrict__ sumsq, float* __restrict__ pen_out) {
-  __shared__ float sm[4];
-  float s0 = 0.f, s1 = 0.f, e0 = 0.f, e1 = 0.f;
-  flat_pass2(n,
-             [&](int64_t i, int64_t j) {
-               const float4 a = si_stash4<PEN>(g, p, om, an, sg, sp, i, two_c, e0), b = si_stash4<PEN>(g, p, om, an, sg, sp, j, two_c, e1);
-               s0 += sq4(a);
-               s1 += sq4(b);
-             },
-             [&](int64_t i) { s0 += sq4(si_stash4<PEN>(g, p, om, an, sg, sp, i, two_c, e0)); },
-             [&](int64_t t) {
-               float a = g[t];
-               const float b = p[t];
-               sg[t] = a;
-               sp[t] = b;
-               if (PEN) {
-                 a = si_pen1(a, b, om[t], an[t], two_c, e0);
-                 g[t] = a;
-               }
-               s0 += a * a;
-             });
-  const float s = block_sum<256>(s0 + s1, sm);
-  const float e = block_sum<256>(e0 + e1, sm);
-  if (threadIdx.x == 0) {
-    sumsq[blockIdx.x] = s;
-    pen_out[blockIdx.x] = e;
-  }
-}
 
 // One block: the penalty partials folded in double (index order per thread, then a fixed tree) -> out[0] = c * sum
 __global__ __launch_bounds__(256) void si_penalty_finish_kernel(const float* __restrict__ partial, int nblk, float c, float* __restrict__ out) {
@@ -141,10 +78,10 @@ extern "C" int mafed_si_stash(float* g, const float* p, const float* omega, cons
   MAFED_CHECK_ARG(aligned16({g, p, omega, anchor, stash_g, stash_p}), "si_stash: buffers must be 16-byte aligned");
   const dim3 grid((unsigned)mafed_si_blocks(n));   // (n == 0: one block that writes a zero partial of each kind)
   if (omega)
-    launch(K_SI, (double)n * 28.0, si_stash_kernel<true>, grid, dim3(256), 0, as_stream(stream), g, p, omega, anchor, n, two_c, stash_g, stash_p,
+    launch(K_SI, (double)n * 28.0, penalty_pass_kernel<true, true>, grid, dim3(256), 0, as_stream(stream), g, p, omega, anchor, n, two_c, stash_g, stash_p,
            sumsq_partials, pen_partials);
   else
-    launch(K_SI, (double)n * 16.0, si_stash_kernel<false>, grid, dim3(256), 0, as_stream(stream), g, p, omega, anchor, n, two_c, stash_g, stash_p,
+    launch(K_SI, (double)n * 16.0, penalty_pass_kernel<false, true>, grid, dim3(256), 0, as_stream(stream), g, p, omega, anchor, n, two_c, stash_g, stash_p,
            sumsq_partials, pen_partials);
   MAFED_CHECK_LAUNCH("si_stash");
   return MAFED_OK;

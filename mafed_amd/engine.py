@@ -207,7 +207,9 @@ class BackwardSweep:
         n_head = logits.shape[0] * logits.shape[1]
         head_labels = sp[1] if sp is not None else sv["labels"]
         kd = sv.pop("kd", None)   # (teacher logits, lse3, tau, lambda): the head loss was CE + lambda tau^2 KL (_head_kd_loss)
-        if kd is not None:
+        if sv.get("sqnorm"):   # the head loss was the squared norm of the labelled rows (_head_text)
+            dlog = ops.sqnorm_bwd(logits, head_labels, gl).view(n_head, V)
+        elif kd is not None:
             dlog = ops.ce_kd_bwd(logits, kd[0], head_labels, kd[1], kd[2], kd[3], gl).view(n_head, V)
         else:
             dlog = ops.ce_bwd(logits, head_labels, sv["ce_lse"], gl).view(n_head, V)
@@ -484,8 +486,11 @@ class EngineMixin:
             # returns NaN (no host synchronisation: the step fails loudly instead of training on a wrong loss)
             self.last_label_overflow = ov
             sv["sparse_head"] = (sor, labels)
+        if self.head_objective not in ("ce", "sqnorm"):
+            raise ValueError(f"head_objective must be 'ce' or 'sqnorm', got {self.head_objective!r}")
+        sqnorm = self.head_objective == "sqnorm" and train and sv["labels"] is not None   # the MAS importance pass
         teacher = None
-        if train and sv["labels"] is not None and self.logit_teacher is not None:
+        if train and sv["labels"] is not None and self.logit_teacher is not None and not sqnorm:
             # the teacher's logits on the padded batch of this forward and the head's row selection (the row-sparse head's ``row_of_slot``,
             # None = all text rows): on the caller's stream, in front of the student's head
             t_logits, tau, lam = self.logit_teacher(feats, sv["input_ids"], sv["attention_mask"], ros)
@@ -493,8 +498,12 @@ class EngineMixin:
         if ros is not None:
             lnf = ops.gather_rows(lnf, ros)
         logits = sv["logits"] = ops.gemm(lnf, self._tensors(0).outer.embed_out, False, True).view(B, Rc or T, self.config.vocab_size)
-        # the loss, chosen here and nowhere else: CE + lambda tau^2 KL under a logit teacher, else CE
-        if teacher is not None:
+        # the loss, chosen here and nowhere else: the squared norm of the labelled rows' logits under ``head_objective = "sqnorm"``,
+        # CE + lambda tau^2 KL under a logit teacher, else CE
+        if sqnorm:
+            sv["loss"], _ = ops.sqnorm_fwd(logits, labels, poison=ov)
+            sv["sqnorm"] = True
+        elif teacher is not None:
             self._head_kd_loss(sv, logits, labels, teacher, ov)
         elif labels is not None:
             sv["loss"], lse_ce = ops.ce_fwd(logits, labels, poison=ov)

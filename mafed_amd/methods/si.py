@@ -24,7 +24,7 @@ import torch
 
 from mafed_amd import ops
 from mafed_amd.methods.base import CLStrategy
-from mafed_amd.methods.flat import FlatDict, require_native
+from mafed_amd.methods.flat import FlatDict, behind_optimizer, require_native
 
 
 class SI(CLStrategy):
@@ -72,13 +72,7 @@ class SI(CLStrategy):
         self._ensure(model)
         return FlatDict(model, getattr(self, which))
 
-    @staticmethod
-    def _behind_optimizer(model) -> None:
-        """Order the caller's stream behind a pipelined optimiser update still in flight: its last chunk's event suffices, all chunks
-        share one stream.  The events stay where they are -- the next forward still waits on them layer by layer."""
-        pe = getattr(model, "_param_events", None)
-        if pe:
-            torch.cuda.current_stream().wait_event(list(pe.values())[-1])
+    _behind_optimizer = staticmethod(behind_optimizer)
 
     # ---- between tasks -----------------------------------------------------------------------------------------------------
     def update(self, model, **kwargs) -> None:

@@ -280,6 +280,10 @@ class VLPythiaForCausalLM(EngineMixin, GenerationMixin, nn.Module):
         self.logit_teacher = None
         # device [3] = (loss, CE, KD) of the last training forward that had a logit teacher (written there; read by callers, no sync)
         self.last_head_losses: Optional[torch.Tensor] = None
+        # The head loss of a training forward with labels: "ce" (with a logit teacher: CE + KL), or "sqnorm" = the squared norm of the logits
+        # on the labelled rows, the objective of the MAS importance pass (methods/mas.py sets and restores it).  Anything else
+        # raises in the forward.
+        self.head_objective = "ce"
         self.defer_ln_param_reduce = True   # LayerNorm parameter-gradient reduction on a side stream (needs overlap_param_grads)
         # generation (mafed_amd/generation.py)
         self.beam_trace: Optional[List[Any]] = None   # a list: generate(num_beams > 1) appends every step's candidate lists to it

@@ -643,6 +643,31 @@ def ce_bwd(logits: torch.Tensor, labels: torch.Tensor, lse: torch.Tensor, gloss:
     return out
 
 
+def sqnorm_fwd(logits: torch.Tensor, labels: torch.Tensor, poison: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Squared-norm head objective (mafed_sqnorm_fwd): logits [B,T,V], labels [B,T] -> (J[1], rowsq[B,T]); the rows and the normaliser
+    of :func:`ce_fwd`, the label values unused.  ``poison`` as in :func:`ce_fwd`."""
+    B, T, V = logits.shape
+    assert logits.is_contiguous() and labels.is_contiguous() and labels.dtype == torch.int64 and labels.shape == (B, T)
+    assert poison is None or (poison.dtype == torch.int32 and poison.numel() == 1)
+    rowsq = torch.empty((B, T), dtype=torch.float32, device=logits.device)
+    out = torch.empty(1, dtype=torch.float32, device=logits.device)
+    check(_lib.load().mafed_sqnorm_fwd(_ptr(logits), _dt(logits), _ptr(labels), B, T, V, _ptr(rowsq), _ptr(out), _ptr(poison), _stream()),
+          "mafed_sqnorm_fwd")
+    return out, rowsq
+
+
+def sqnorm_bwd(logits: torch.Tensor, labels: torch.Tensor, dloss: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dJ/dlogits in the logits' dtype, exact zeros on unlabelled rows (``out``: a buffer of its own)."""
+    B, T, V = logits.shape
+    assert logits.is_contiguous() and labels.is_contiguous() and labels.dtype == torch.int64 and labels.shape == (B, T)
+    assert dloss.dtype == torch.float32 and dloss.numel() == 1
+    if out is None:
+        out = torch.empty_like(logits)
+    assert out.dtype == logits.dtype and out.shape == logits.shape and out.is_contiguous()
+    check(_lib.load().mafed_sqnorm_bwd(_ptr(logits), _dt(logits), _ptr(labels), B, T, V, _ptr(dloss), _ptr(out), _stream()), "mafed_sqnorm_bwd")
+    return out
+
+
 def _kd_check(student: torch.Tensor, teacher: torch.Tensor, labels: torch.Tensor) -> Tuple[int, int, int]:
     B, T, V = student.shape
     if teacher.shape != student.shape or teacher.dtype != student.dtype:
@@ -836,6 +861,36 @@ def si_consolidate_(p: torch.Tensor, anchor: torch.Tensor, w: torch.Tensor, omeg
     """omega = max(omega + w / ((p - anchor)^2 + xi), 0); anchor = p; w = 0."""
     _flat_f32(p, anchor, w, omega)
     check(_lib.load().mafed_si_consolidate(_ptr(p), _ptr(anchor), _ptr(w), _ptr(omega), p.numel(), float(xi), _stream()), "mafed_si_consolidate")
+
+
+def mas_blocks(n: int) -> int:
+    """Number of partials of each kind ``mas_penalty_`` writes for n elements (== ``si_blocks(n)``)."""
+    return int(_lib.load().mafed_mas_blocks(int(n)))
+
+
+def mas_accumulate_(g: torch.Tensor, acc: torch.Tensor, weight: float) -> None:
+    """acc = fma(weight, |g|, acc)."""
+    _flat_f32(g, acc)
+    check(_lib.load().mafed_mas_accumulate(_ptr(g), _ptr(acc), g.numel(), float(weight), _stream()), "mafed_mas_accumulate")
+
+
+def mas_consolidate_(acc: torch.Tensor, omega: torch.Tensor, p: torch.Tensor, anchor: torch.Tensor, inv_seen: float, alpha: float,
+                     first: bool) -> None:
+    """omega = inv_seen * acc (``first``; omega is not read) or alpha * omega + (1 - alpha) * inv_seen * acc; anchor = p; acc = 0."""
+    _flat_f32(acc, omega, p, anchor)
+    check(_lib.load().mafed_mas_consolidate(_ptr(acc), _ptr(omega), _ptr(p), _ptr(anchor), p.numel(), float(inv_seen), float(alpha),
+                                            int(bool(first)), _stream()), "mafed_mas_consolidate")
+
+
+def mas_penalty_(g: torch.Tensor, p: torch.Tensor, omega: torch.Tensor, anchor: torch.Tensor, two_c: float, sumsq_partials: torch.Tensor,
+                 pen_partials: torch.Tensor) -> None:
+    """g += two_c * omega * (p - anchor) in place.  ``sumsq_partials`` [>= mas_blocks(n)] receives the sum-of-squares partials of the g it
+    leaves (``gradnorm_finish``), ``pen_partials`` those of sum omega (p - anchor)^2 (``si_penalty_finish``)."""
+    _flat_f32(g, p, omega, anchor)
+    nb = mas_blocks(g.numel())
+    assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() >= nb for t in (sumsq_partials, pen_partials))
+    check(_lib.load().mafed_mas_penalty(_ptr(g), _ptr(p), _ptr(omega), _ptr(anchor), g.numel(), float(two_c), _ptr(sumsq_partials),
+                                        _ptr(pen_partials), _stream()), "mafed_mas_penalty")
 
 
 def cka_pool(hidden: Sequence[torch.Tensor], attention_mask: torch.Tensor, P: int, out: torch.Tensor, rows: Optional[torch.Tensor] = None) -> None:
