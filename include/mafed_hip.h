@@ -395,6 +395,35 @@ int mafed_mas_consolidate(float* acc, float* omega, const float* p, float* ancho
 int mafed_mas_penalty(float* g, const float* p, const float* omega, const float* anchor, int64_t n, float two_c, float* sumsq_partials,
                       float* pen_partials, void* stream);
 
+/* ---- PackNet (Mallya & Lazebnik 2018) ---------------------------------------------------------------
+ * On flat buffers laid out like the fp32 parameters p: the gradient g, the anchor, the bf16 shadow of p (raw bits; NULL = none) and the
+ * byte-wide owner map (owner[i] = the task that trained element i).  Base pointers must be 16-byte aligned.
+ *   mask_grad:  g[i] = owner[i] == task ? g[i] : +0.0 in place; sumsq_partials receives mafed_packnet_blocks(n) sum-of-squares partials
+ *               of the g it leaves, for mafed_gradnorm_finish.  No atomics: the same bits on every run.  n == 0: one zero partial.
+ *   hold:       where owner[i] != task: p[i] = anchor[i], shadow[i] = bf16(anchor[i]) (round to nearest even).  Nothing else is written.
+ *   view:       where owner[i] > k: p[i] = +0.0, shadow[i] = 0.  Nothing else is written.
+ * The prune is an exact k-th-smallest selection per segment, a three-pass radix select (11 + 10 + 10 bits) on the 31-bit pattern of |p|
+ * (-0 equals +0, a NaN sorts above +inf).  segments = device int64 [n_segments][2] = {offset, length} into the flat buffers, any alignment,
+ * length < 2^32; an element outside [0, n) is ignored.  One launch covers all segments, grid (blocks_per_segment, n_segments).
+ *   hist:   pass 0, 1, 2: hist[s][bin] (uint32 [n_segments][2048], cleared by the call) = number of elements of segment s with
+ *           owner == task whose bits above the pass's digit equal the prefix in state; integer atomics only.
+ *   scan:   one block per segment.  Pass 0 also derives m = number of elements with owner == task and k = floor(fraction * m) in IEEE
+ *           double.  Walks the bins to the one that holds rank k and writes the extended prefix and the remaining rank.
+ *           state = int64 [n_segments][4] = {prefix, rank, active (k > 0), unused}; stats = int64 [n_segments][4] = {m, k, pruned, tau},
+ *           tau = the pattern of the k-th smallest |p| (0 while k == 0), written by pass 2.
+ *   apply:  every element with owner == task and |p| <= tau (as patterns): p = +0.0, anchor = +0.0, owner = task + 1, shadow = 0;
+ *           stats[s][2] = their number (ties at tau are all pruned, so it may exceed k).
+ * 0 <= task <= 254, 0 <= fraction <= 1.  The host reads nothing back. */
+int mafed_packnet_blocks(int64_t n);
+int mafed_packnet_mask_grad(float* g, const uint8_t* owner, int64_t n, int task, float* sumsq_partials, void* stream);
+int mafed_packnet_hold(float* p, void* shadow, const uint8_t* owner, const float* anchor, int64_t n, int task, void* stream);
+int mafed_packnet_view(float* p, void* shadow, const uint8_t* owner, int64_t n, int k, void* stream);
+int mafed_packnet_hist(const float* p, const uint8_t* owner, int64_t n, const int64_t* segments, int n_segments, int blocks_per_segment,
+                       int task, int pass, const int64_t* state, uint32_t* hist, void* stream);
+int mafed_packnet_scan(const uint32_t* hist, int n_segments, int pass, double fraction, int64_t* state, int64_t* stats, void* stream);
+int mafed_packnet_apply(float* p, void* shadow, uint8_t* owner, float* anchor, int64_t n, const int64_t* segments, int n_segments,
+                        int blocks_per_segment, int task, const int64_t* state, int64_t* stats, void* stream);
+
 /* ---- representation-drift analysis: per-layer, per-modality linear CKA (mafed/analysis/) --------------------------
  * Modality pooling of one forward's hidden states (mafed/analysis/get_average_CKA_per_layer.py:107-118): for sample b and
  * layer l (hidden_host[l] = hidden_states[l + 1], fp32 [B, S, h], S = P + T)

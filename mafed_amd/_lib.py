@@ -66,6 +66,13 @@ SIGNATURES = {
     "mafed_mas_accumulate": (_i, [_p, _p, _l, _f, _p]),
     "mafed_mas_consolidate": (_i, [_p, _p, _p, _p, _l, _f, _f, _i, _p]),
     "mafed_mas_penalty": (_i, [_p, _p, _p, _p, _l, _f, _p, _p, _p]),
+    "mafed_packnet_blocks": (_i, [_l]),
+    "mafed_packnet_mask_grad": (_i, [_p, _p, _l, _i, _p, _p]),
+    "mafed_packnet_hold": (_i, [_p, _p, _p, _p, _l, _i, _p]),
+    "mafed_packnet_view": (_i, [_p, _p, _p, _l, _i, _p]),
+    "mafed_packnet_hist": (_i, [_p, _p, _l, _p, _i, _i, _i, _i, _p, _p, _p]),
+    "mafed_packnet_scan": (_i, [_p, _i, _i, _d, _p, _p, _p]),
+    "mafed_packnet_apply": (_i, [_p, _p, _p, _p, _l, _p, _i, _i, _i, _p, _p, _p]),
     "mafed_cka_pool": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _l, _p, _p]),
     "mafed_cka_stats_workspace_bytes": (_z, [_l, _l, _l]),
     "mafed_cka_stats": (_i, [_p, _l, _l, _l, _l, _l, _p, _p, _p, _z, _p]),

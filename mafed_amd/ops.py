@@ -893,6 +893,99 @@ def mas_penalty_(g: torch.Tensor, p: torch.Tensor, omega: torch.Tensor, anchor: 
                                         _ptr(pen_partials), _stream()), "mafed_mas_penalty")
 
 
+PACKNET_BINS = 2048   # uint32 bins per segment of the prune's histogram workspace
+
+
+def packnet_blocks(n: int) -> int:
+    """Number of sum-of-squares partials ``packnet_mask_grad_`` writes for n elements."""
+    return int(_lib.load().mafed_packnet_blocks(int(n)))
+
+
+def _packnet_flat(x: torch.Tensor, owner: torch.Tensor, shadow: Optional[torch.Tensor] = None, anchor: Optional[torch.Tensor] = None) -> None:
+    """fp32 buffers, the uint8 owner map and the bf16 shadow: contiguous, one-dimensional, of one length."""
+    _flat_f32(x, *([] if anchor is None else [anchor]))
+    assert owner.dtype == torch.uint8 and owner.is_contiguous() and owner.dim() == 1 and owner.numel() == x.numel()
+    assert shadow is None or (shadow.dtype == torch.bfloat16 and shadow.is_contiguous() and shadow.dim() == 1 and shadow.numel() == x.numel())
+
+
+def packnet_mask_grad_(g: torch.Tensor, owner: torch.Tensor, task: int, sumsq_partials: torch.Tensor) -> None:
+    """g = owner == task ? g : +0.0 in place.  ``sumsq_partials`` [>= packnet_blocks(n)] receives the sum-of-squares partials of the g it
+    leaves (``gradnorm_finish``)."""
+    _packnet_flat(g, owner)
+    assert sumsq_partials.dtype == torch.float32 and sumsq_partials.is_contiguous() and sumsq_partials.numel() >= packnet_blocks(g.numel())
+    check(_lib.load().mafed_packnet_mask_grad(_ptr(g), _ptr(owner), g.numel(), int(task), _ptr(sumsq_partials), _stream()), "mafed_packnet_mask_grad")
+
+
+def packnet_hold_(p: torch.Tensor, shadow: Optional[torch.Tensor], owner: torch.Tensor, anchor: torch.Tensor, task: int) -> None:
+    """Where owner != task: p = anchor, shadow = bf16(anchor).  Nothing else is written."""
+    _packnet_flat(p, owner, shadow, anchor)
+    check(_lib.load().mafed_packnet_hold(_ptr(p), _ptr(shadow), _ptr(owner), _ptr(anchor), p.numel(), int(task), _stream()), "mafed_packnet_hold")
+
+
+def packnet_view_(p: torch.Tensor, shadow: Optional[torch.Tensor], owner: torch.Tensor, k: int) -> None:
+    """Where owner > k: p = +0.0, shadow = 0.  Nothing else is written."""
+    _packnet_flat(p, owner, shadow)
+    check(_lib.load().mafed_packnet_view(_ptr(p), _ptr(shadow), _ptr(owner), p.numel(), int(k), _stream()), "mafed_packnet_view")
+
+
+def packnet_select_blocks(max_length: int, n_segments: int) -> int:
+    """Blocks per segment of the prune's launches: one per 1024 fp32 vectors of the longest segment, and about 4096 blocks in all at most
+    (every block adds its non-empty bins to the segment's histogram)."""
+    want = (int(max_length) // 4 + 1 + 1023) // 1024
+    return max(1, min(want, 4096 // max(1, int(n_segments))))
+
+
+def _packnet_tables(segments: torch.Tensor, state: torch.Tensor, stats: Optional[torch.Tensor] = None, hist: Optional[torch.Tensor] = None) -> int:
+    assert segments.dtype == torch.int64 and segments.is_contiguous() and segments.dim() == 2 and segments.size(1) == 2
+    n_seg = segments.size(0)
+    for t in (state, stats):
+        assert t is None or (t.dtype == torch.int64 and t.is_contiguous() and t.numel() >= 4 * n_seg)
+    assert hist is None or (hist.dtype == torch.int32 and hist.is_contiguous() and hist.numel() >= PACKNET_BINS * n_seg)
+    return n_seg
+
+
+def packnet_hist(p: torch.Tensor, owner: torch.Tensor, segments: torch.Tensor, blocks_per_segment: int, task: int, radix_pass: int,
+                 state: torch.Tensor, hist: torch.Tensor) -> None:
+    """hist[s][bin] = number of elements of segment s with owner == task whose bits above digit ``radix_pass`` equal the prefix in state."""
+    _packnet_flat(p, owner)
+    n_seg = _packnet_tables(segments, state, hist=hist)
+    check(_lib.load().mafed_packnet_hist(_ptr(p), _ptr(owner), p.numel(), _ptr(segments), n_seg, int(blocks_per_segment), int(task), int(radix_pass),
+                                         _ptr(state), _ptr(hist), _stream()), "mafed_packnet_hist")
+
+
+def packnet_scan(hist: torch.Tensor, n_segments: int, radix_pass: int, fraction: float, state: torch.Tensor, stats: torch.Tensor) -> None:
+    """Per segment: the bin that holds the wanted rank -> the extended prefix and the remaining rank in state; pass 0 derives m and k."""
+    assert hist.dtype == torch.int32 and hist.numel() >= PACKNET_BINS * n_segments and state.numel() >= 4 * n_segments and stats.numel() >= 4 * n_segments
+    assert state.dtype == torch.int64 and stats.dtype == torch.int64
+    check(_lib.load().mafed_packnet_scan(_ptr(hist), int(n_segments), int(radix_pass), float(fraction), _ptr(state), _ptr(stats), _stream()),
+          "mafed_packnet_scan")
+
+
+def packnet_apply_(p: torch.Tensor, shadow: Optional[torch.Tensor], owner: torch.Tensor, anchor: torch.Tensor, segments: torch.Tensor,
+                   blocks_per_segment: int, task: int, state: torch.Tensor, stats: torch.Tensor) -> None:
+    """Where owner == task and |p| <= tau of the segment: p = anchor = +0.0, shadow = 0, owner = task + 1; stats[s][2] = their number."""
+    _packnet_flat(p, owner, shadow, anchor)
+    n_seg = _packnet_tables(segments, state, stats)
+    check(_lib.load().mafed_packnet_apply(_ptr(p), _ptr(shadow), _ptr(owner), _ptr(anchor), p.numel(), _ptr(segments), n_seg, int(blocks_per_segment),
+                                          int(task), _ptr(state), _ptr(stats), _stream()), "mafed_packnet_apply")
+
+
+def packnet_prune_(p: torch.Tensor, shadow: Optional[torch.Tensor], owner: torch.Tensor, anchor: torch.Tensor, segments: torch.Tensor,
+                   blocks_per_segment: int, task: int, fraction: float, state: Optional[torch.Tensor] = None, hist: Optional[torch.Tensor] = None,
+                   stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The whole prune of every segment (int64 [S, 2] = {offset, length} on the device): three histogram + scan passes, then the apply pass;
+    seven launches, nothing read back.  -> stats, int64 [S, 4] = {m, k, pruned, pattern of tau} on the device."""
+    n_seg, dev = segments.size(0), p.device
+    state = torch.zeros(n_seg, 4, dtype=torch.int64, device=dev) if state is None else state
+    stats = torch.zeros(n_seg, 4, dtype=torch.int64, device=dev) if stats is None else stats
+    hist = torch.zeros(n_seg, PACKNET_BINS, dtype=torch.int32, device=dev) if hist is None else hist
+    for radix_pass in range(3):
+        packnet_hist(p, owner, segments, blocks_per_segment, task, radix_pass, state, hist)
+        packnet_scan(hist, n_seg, radix_pass, fraction, state, stats)
+    packnet_apply_(p, shadow, owner, anchor, segments, blocks_per_segment, task, state, stats)
+    return stats
+
+
 def cka_pool(hidden: Sequence[torch.Tensor], attention_mask: torch.Tensor, P: int, out: torch.Tensor, rows: Optional[torch.Tensor] = None) -> None:
     """out[0, l, rows[b]] = mean of hidden[l][b, :P]; out[1, l, rows[b]] = mean of the last sum(attention_mask[b]) rows of hidden[l][b]
     (fp32 hidden states [B, S, h], text mask [B, T], out fp32 [2, L, n, h])."""

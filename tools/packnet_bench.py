@@ -1,0 +1,234 @@
+"""The PackNet passes, prune and step (run on the GPU box, one process on an otherwise idle GPU):
+
+  * the 410M bf16 step at B = 32, 256 + 32 tokens with the pipelined optimiser, for ``naive``, ``packnet task 0`` (nothing launched),
+    ``packnet task>=1`` (after one prune at 0.5 and update(): half of every layer matrix is trainable, everything else held) and
+    ``mas task>=1``.  Wall ms around Trainer.step ending in a device synchronise, and beside it the free-running figure -- blocks of
+    steps with one synchronise behind each.  Method names as arguments run only those step rows.
+  * a whole ``prune`` over the 410M layout's 96 layer matrices (seven launches, nothing read back), beside the same prune with torch:
+    ``kthvalue`` of |p| per tensor on the GPU and masked fills (no float64, no host read either).  Device-event time around the whole call.
+  * ``packnet_mask_grad``, ``packnet_hold`` with 0 %, 50 % (independently per element, what a prune leaves) and 100 % held and
+    ``packnet_view`` (50 %) on flat buffers of the VLPythia-410M parameter count, beside ``gradnorm_clip``, ``mas_penalty`` and
+    ``si_stash (penalty)`` in the same run: device-event time around each call, median and min .. max of REPS calls after a warm-up, and
+    the achieved TB/s against the bytes the call moves (a held element: 4 B anchor read, 4 + 2 B written; every element: 1 B owner read).
+
+There is no speed gate: the table is reported as measured.  A per-step pass (mask_grad, hold at 50 % and 100 %) below 0.8 of
+``mas_penalty``'s TB/s in the same run is marked.
+
+    python tools/packnet_bench.py > profiles/packnet_step.txt
+    python tools/packnet_bench.py --resources        # no GPU: registers and scratch of the kernels, from the hipcc gfx950 build
+"""
+import os
+import re
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+import types
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+REPS = 15
+FREE_RUNS, FREE_STEPS = 5, 8
+dev = "cuda"
+
+
+def resources():
+    """VGPRs, SGPRs, scratch, LDS and occupancy of every kernel in packnet.hip as hipcc reports them for gfx950."""
+    from mafed_amd import build
+    print("# hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage")
+    print(f"{'kernel':>44s} {'VGPRs':>6s} {'SGPRs':>6s} {'scratch B/lane':>15s} {'LDS B/block':>12s} {'waves/SIMD':>11s}")
+    with tempfile.TemporaryDirectory() as tmp:
+        r = subprocess.run([build._hipcc()] + build.FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(build.CSRC, "packnet.hip"), "-o",
+                            os.path.join(tmp, "o.o")], capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(r.stderr[-2000:])
+    field = lambda block, key: re.search(key + r": (\d+)", block).group(1)
+    for block in r.stderr.split("Function Name: ")[1:]:
+        name = subprocess.run(["c++filt", block.split()[0]], capture_output=True, text=True).stdout.strip() or block.split()[0]
+        name = re.sub(r"\(.*", "", name).replace("void ", "").replace("mafed::", "")
+        cols = [field(block, key) for key in (" VGPRs", "TotalSGPRs", r"ScratchSize \[bytes/lane\]", r"LDS Size \[bytes/block\]", r"Occupancy \[waves/SIMD\]")]
+        print(f"{name:>44s} {cols[0]:>6s} {cols[1]:>6s} {cols[2]:>15s} {cols[3]:>12s} {cols[4]:>11s}")
+
+
+if "--resources" in sys.argv[1:]:
+    resources()
+    sys.exit(0)
+
+import torch  # noqa: E402
+
+from mafed_amd import MAS, Naive, PackNet, Trainer, VLPythiaConfig, VLPythiaForCausalLM, ops  # noqa: E402
+
+
+def timed(fn, reps=REPS, warmup=3, before=None):
+    """[us per call] from device events around each call; ``before`` runs outside the events."""
+    out = []
+    for k in range(warmup + reps):
+        if before is not None:
+            before()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        if k >= warmup:
+            out.append(e0.elapsed_time(e1) * 1e3)
+    return out
+
+
+def _row(name, nbytes, us, mark=""):
+    med = statistics.median(us)
+    print(f"{name:>36s} {med:10.1f} {min(us):8.1f} {max(us):8.1f} {nbytes / 1e6:8.1f} {nbytes / med / 1e6:6.2f}{mark}", flush=True)
+    return nbytes / med / 1e6
+
+
+def kernel_table(n):
+    gen = torch.Generator(device=dev).manual_seed(n % 1000003)
+    g = torch.randn(n, generator=gen, device=dev) * 1e-3
+    p = torch.randn(n, generator=gen, device=dev) * 2e-2
+    anchor = p + 1e-3 * torch.randn(n, generator=gen, device=dev)
+    omega = torch.rand(n, generator=gen, device=dev)
+    shadow = p.to(torch.bfloat16)
+    sg, sp = torch.empty_like(g), torch.empty_like(g)
+    half = (torch.rand(n, generator=gen, device=dev) < 0.5).to(torch.uint8)    # owner 1 = trainable in task 1, 0 = held
+    ones, zeros = torch.ones(n, dtype=torch.uint8, device=dev), torch.zeros(n, dtype=torch.uint8, device=dev)
+    held = 1.0 - float(half.float().mean())
+    nb = ops.mas_blocks(n)
+    sumsq, pen = torch.empty(nb, device=dev), torch.empty(nb, device=dev)
+    clip2 = torch.empty(2, device=dev)
+    rows = [
+        ("gradnorm_clip", 4, lambda: ops.gradnorm_clip(g, 2.0, clip2)),
+        ("si_stash (penalty)", 28, lambda: ops.si_stash(g, p, omega, anchor, 1e-6, sg, sp, sumsq, pen)),
+        ("mas_penalty", 20, lambda: ops.mas_penalty_(g, p, omega, anchor, 1e-6, sumsq, pen)),
+        ("packnet_mask_grad (50 % held)", 9, lambda: ops.packnet_mask_grad_(g, half, 1, sumsq)),
+        ("packnet_hold (0 % held)", 1, lambda: ops.packnet_hold_(p, shadow, ones, anchor, 1)),
+        ("packnet_hold (50 % held)", 1 + 4 + 6 * held, lambda: ops.packnet_hold_(p, shadow, half, anchor, 1)),
+        ("packnet_hold (100 % held)", 11, lambda: ops.packnet_hold_(p, shadow, zeros, anchor, 1)),
+        ("packnet_view (50 % zeroed)", 1 + 6 * (1.0 - held), lambda: ops.packnet_view_(p, shadow, half, 0)),
+    ]
+    print(f"{'pass [bytes per parameter]':>36s} {'median us':>10s} {'min':>8s} {'max':>8s} {'MB':>8s} {'TB/s':>6s}")
+    rate = {}
+    for name, bpp, fn in rows:
+        us = timed(fn)
+        per_step = name.startswith(("packnet_mask_grad", "packnet_hold (50", "packnet_hold (100"))
+        below = per_step and n * bpp / statistics.median(us) / 1e6 < 0.8 * rate["mas_penalty"]
+        rate[name] = _row(f"{name} [{bpp:.3g}]", n * bpp, us, "   <-- below 0.8 of mas_penalty" if below else "")
+
+
+def _batch(cfg, B, P, T):
+    gcpu = torch.Generator().manual_seed(1235)
+    ids = torch.randint(1, cfg.vocab_size, (B, T), generator=gcpu)
+    labels = torch.full((B, T), -100, dtype=torch.int64)
+    labels[:, -4:] = ids[:, -4:]
+    feats = torch.randn(B, P, cfg.vision_hidden_size, generator=gcpu).to(torch.bfloat16)
+    batch = {"input_ids": ids, "attention_mask": torch.ones(B, T, dtype=torch.int64), "labels": labels, "patch_embeddings": feats}
+    return {k: v.to(dev) for k, v in batch.items()}
+
+
+def prune_times(cfg, reps=7):
+    """A whole prune of the 410M model's 96 layer matrices at 0.5, and the same with torch.kthvalue per tensor."""
+    model = VLPythiaForCausalLM(cfg, compute_dtype=torch.bfloat16, device=dev, seed=1234)
+    model.sync_shadow()
+    pk = PackNet(prune_fraction=0.5)
+    pk._ensure(model)
+    p0 = model.flat_params.clone()
+    names = pk.prunable_names(model)
+    elements = sum(model._offsets[name][1] for name in names)
+
+    def reset():
+        model.flat_params.copy_(p0)
+        pk.owner.zero_()
+        pk.pruned = False
+
+    us = timed(lambda: pk.prune(model), reps=reps, warmup=2, before=reset)
+    report = pk.prune_report(model)
+    exact = all(r["pruned"] >= r["k"] == r["m"] // 2 for r in report.values())
+    print(f"{'packnet prune':>36s}: {statistics.median(us) / 1e3:8.2f} ({min(us) / 1e3:.2f} .. {max(us) / 1e3:.2f}) ms   {len(names)} tensors, {elements} elements, "
+          f"{sum(r['pruned'] for r in report.values())} pruned, k = m // 2 in every tensor: {exact}", flush=True)
+    owner, anchor, shadow = pk.owner, pk.anchor, model.flat_shadow
+    views = [(model._offsets[name][0], model._offsets[name][1]) for name in names]
+
+    def torch_prune():
+        for o, n in views:
+            w = model.flat_params[o:o + n]
+            a = w.abs()
+            hit = a <= a.kthvalue(n // 2).values
+            w.masked_fill_(hit, 0.0)
+            anchor[o:o + n].masked_fill_(hit, 0.0)
+            shadow[o:o + n].masked_fill_(hit, 0.0)
+            owner[o:o + n].masked_fill_(hit, 1)
+    try:
+        us = timed(torch_prune, reps=reps, warmup=2, before=reset)
+        print(f"{'torch kthvalue per tensor':>36s}: {statistics.median(us) / 1e3:8.2f} ({min(us) / 1e3:.2f} .. {max(us) / 1e3:.2f}) ms   "
+              f"{int((owner == 1).sum())} pruned", flush=True)
+    except Exception as e:   # reported, not hidden: the baseline is torch's, not this project's
+        print(f"{'torch kthvalue per tensor':>36s}: failed ({type(e).__name__}: {str(e)[:120]})", flush=True)
+
+
+def step_times(method_name, cfg, B, P, T, steps=12, warmup=4):
+    student = VLPythiaForCausalLM(cfg, compute_dtype=torch.bfloat16, device=dev, seed=1234)
+    batch = _batch(cfg, B, P, T)
+    dense = dict(batch)
+    batch["max_label_rows"] = 4   # the loader's hint: the row-sparse head (256 of 1024 rows)
+    conf = types.SimpleNamespace(accumulate_grad_batches=1, replay_interval=1, grad_norm=2.0, learning_rate=5e-5, betas=(0.9, 0.98),
+                                 weight_decay=0.01, optim="adamw", warmup_steps=0, total_steps=100000)   # no warm-up: the parameters move from step 1
+    method = {"naive": lambda: Naive(), "packnet task 0": lambda: PackNet(), "packnet task>=1": lambda: PackNet(prune_fraction=0.5),
+              "mas task>=1": lambda: MAS(reg_lambda=1.0)}[method_name]()
+    later = method_name.endswith("task>=1")
+    tr = Trainer(student, method, conf, task_id=1 if later else 0, n_batches_per_epoch=1000, pipeline_optimizer=True)
+    if later:
+        # one step so that the parameters have left their start, then the task boundary (PackNet: prune at 0.5 and consolidate)
+        tr.step(dict(batch), 0)
+        tr.join()
+        method.update(student, dataloader=[dense])
+        student.zero_grad()
+    ts, rec, i = [], None, 0
+    for _ in range(warmup + steps):
+        t0 = time.perf_counter()
+        rec = tr.step(dict(batch), i)
+        torch.cuda.synchronize()
+        if i >= warmup:
+            ts.append((time.perf_counter() - t0) * 1e3)
+        i += 1
+    free = []
+    for _ in range(FREE_RUNS):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(FREE_STEPS):
+            rec = tr.step(dict(batch), i)
+            i += 1
+        torch.cuda.synchronize()
+        free.append((time.perf_counter() - t0) * 1e3 / FREE_STEPS)
+    tr.join()
+    torch.cuda.synchronize()
+    parts = ""
+    if isinstance(method, PackNet) and method.owner is not None:
+        parts = f"  trainable {float((method.owner == method.task_id).float().mean()):.3f} of the buffer"
+    return ts, free, float(rec["loss"]), float(rec["grad_norm"]), parts, student.flat_grads.numel()
+
+
+def main():
+    assert torch.cuda.is_available(), "packnet_bench needs a GPU"
+    B, P, T = 32, 256, 32
+    cfg = VLPythiaConfig.preset("410m", num_vision_tokens=P)
+    print(f"# {torch.cuda.get_device_name(0)}; VLPythia-410M bf16 step, B = {B}, {P} + {T} tokens, row-sparse head, pipelined optimiser; wall ms per Trainer.step, "
+          f"median (min .. max): 12 steps after 4, each followed by a synchronise | free-running, {FREE_RUNS} blocks of {FREE_STEPS} steps")
+    n_flat = 0
+    names = sys.argv[1:] or ["naive", "packnet task 0", "packnet task>=1", "mas task>=1", "naive"]
+    for name in names:
+        ts, free, loss, gn, parts, n_flat = step_times(name, cfg, B, P, T)
+        print(f"{name:>24s}: {statistics.median(ts):7.2f} ({min(ts):.2f} .. {max(ts):.2f}) | {statistics.median(free):7.2f} ({min(free):.2f} .. {max(free):.2f}) ms"
+              f"   loss {loss:.4f}  grad norm {gn:.4f}{parts}", flush=True)
+        torch.cuda.empty_cache()
+    if sys.argv[1:]:
+        return
+    print("# a whole prune at 0.5 of the same model's layer matrices; device-event time around the call, ms, median (min .. max) of 7 after 2")
+    prune_times(cfg)
+    torch.cuda.empty_cache()
+    print(f"# flat buffers of {n_flat} elements ({n_flat * 4 / 1e9:.2f} GB per fp32 buffer); device-event time around each call, us, median (min .. max) of {REPS}")
+    kernel_table(n_flat)
+
+
+if __name__ == "__main__":
+    main()
