@@ -580,7 +580,10 @@ def decode_ln_linear(x: torch.Tensor, ln_w, ln_b, eps: float, w: torch.Tensor, b
 
 
 def decode_out_workspace(M: int, h: int, device) -> torch.Tensor:
-    """Zero-filled workspace of ``decode_out`` (partial tiles + arrival counters; one per stream, re-usable across calls)."""
+    """Zero-filled workspace of ``decode_out`` (partial tiles + arrival counters; one per stream).  The counters sit behind the partial
+    tiles at an offset that depends on ``ceil(M / 16)``, so a workspace serves calls with the M it was sized for (any M of the same
+    ``ceil(M / 16)``), again and again, and the chunked M > 64 form, which is sized as 64 rows and shifts the view for a shorter last block
+    itself.  A call with another row-block count would find its counters among the partial tiles: allocate one workspace per M."""
     return torch.zeros(int(_lib.load().mafed_decode_out_workspace_bytes(int(M), int(h))), dtype=torch.uint8, device=device)
 
 
