@@ -20,23 +20,172 @@ class BeamSearchOutput:
     sequences_scores: Optional[torch.Tensor] = None
 
 
-def _greedy_pick(last_logits: torch.Tensor, unfinished: torch.Tensor, eos_token_id, pad_token_id) -> Tuple[torch.Tensor, torch.Tensor]:
-    """HF ``greedy_search`` token rule: argmax of the last position, finished rows emit ``pad_token_id``; -> (tokens [B], the
-    updated ``unfinished`` flags).  Shared by the eager loop and the captured graph's body."""
-    nxt = last_logits.float().argmax(dim=-1)
-    if eos_token_id is not None:
-        nxt = nxt * unfinished + pad_token_id * (1 - unfinished)
-        unfinished = unfinished * (nxt != eos_token_id).to(torch.int64)
-    return nxt, unfinished
+def _eos_cut(gen: torch.Tensor, eos_token_id) -> int:
+    """HF leaves the loop as soon as every row has finished: of the tokens ``gen`` [R, n] -> how many the slowest row needed, up to and
+    including its first eos.  The one host synchronisation of the greedy and the sampled paths."""
+    if eos_token_id is None:
+        return gen.shape[1]
+    done = (gen == eos_token_id).to(torch.int64).cumsum(1).clamp_(max=1)       # 1 from the first eos on
+    first = (done.shape[1] - done.sum(1)) + done[:, -1]                        # tokens up to and including the first eos
+    return int(first.max().clamp_(max=gen.shape[1]))
 
 
-def _sample_pick(last_logits: torch.Tensor, warp, seed: torch.Tensor, step: int, unfinished: Optional[torch.Tensor], eos_token_id, pad_token_id,
-                 logprob: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The sampled counterpart of ``_greedy_pick`` as one launch: ``warp`` = (temperature, top_k, top_p, min_p); ``unfinished`` is
-    updated in place.  Shared by the eager loops and the captured graph's body."""
-    temperature, top_k, top_p, min_p = warp
-    return ops.sample_token(last_logits, temperature, top_k, top_p, min_p, seed=seed, step=step, unfinished=unfinished,
-                            eos_token_id=eos_token_id, pad_token_id=0 if pad_token_id is None else pad_token_id, logprob=logprob)
+def _rows(x: torch.Tensor, n: int) -> torch.Tensor:
+    """Every row of ``x`` n times in a row (HF's ``expand_inputs_for_generation`` order)."""
+    return x.repeat_interleave(n, 0) if n > 1 else x
+
+
+class _GreedyPick:
+    """A pick object is what differs between greedy, sampled and beam decoding; ``GenerationMixin._decode`` is the loop around it.  It says
+    into how many ``rows`` a prompt expands, draws the next tokens [B * rows] from the step's logits when called with (logits, step) --
+    step 0 of the cached loop hands it the prefill's one row per prompt --, sees the cache once after the prefill (``start``) and before
+    every cached step (``before_step``), names the tokens of the steps so far for the recompute loop (``drawn``) and assembles the result
+    (``result``, the one host synchronisation).  For the captured graph: ``key`` tells two captures apart (None: cannot be captured),
+    ``reset`` forgets the draws from inside the captured body, ``inputs`` are the device words a replay reads.
+    This one is HF ``greedy_search``; it owns the ``unfinished`` flags, the drawn tokens and, if wanted, every step's logits."""
+
+    rows, key, inputs = 1, (), ()
+
+    def __init__(self, R: int, dev, eos_token_id, pad_token_id, want_steps: bool = False, flags: bool = True):
+        self.R, self.dev, self.eos, self.pad, self.want_steps = R, dev, eos_token_id, pad_token_id, want_steps
+        self.unfinished = torch.ones(R, dtype=torch.int64, device=dev) if flags else None
+        self.tokens, self.steps, self.logprobs = [], [], []
+
+    def reset(self) -> None:
+        self.unfinished = torch.ones_like(self.unfinished)
+        self.tokens, self.steps, self.logprobs = [], [], []
+
+    def start(self, cache: "_DecodeCache") -> None:
+        pass
+
+    def before_step(self, cache: "_DecodeCache") -> None:
+        pass
+
+    def __call__(self, logits: torch.Tensor, t: int) -> torch.Tensor:
+        nxt = logits.float().argmax(dim=-1)   # the token rule: argmax of the last position, finished rows emit ``pad_token_id``
+        if self.eos is not None:
+            nxt = nxt * self.unfinished + self.pad * (1 - self.unfinished)
+            self.unfinished = self.unfinished * (nxt != self.eos).to(torch.int64)
+        return self._keep(nxt, logits)
+
+    def _keep(self, nxt: torch.Tensor, logits: torch.Tensor) -> torch.Tensor:
+        self.tokens.append(nxt)
+        if self.want_steps:
+            self.steps.append(logits.float())
+        return nxt
+
+    def drawn(self, t: int) -> torch.Tensor:
+        return torch.stack(self.tokens, dim=1)
+
+    def result(self, ids: torch.Tensor) -> Tuple[Optional[torch.Tensor], ...]:
+        """-> (sequences [B * rows, T + n_keep], the kept steps' logits [n_keep, B * rows, V] or None, the kept draws' log-probabilities
+        [B * rows, n_keep] or None): all three cut at ``_eos_cut``."""
+        gen = torch.stack(self.tokens, dim=1)
+        n_keep = _eos_cut(gen, self.eos)
+        return (torch.cat([_rows(ids, self.rows), gen[:, :n_keep]], dim=1), torch.stack(self.steps[:n_keep], dim=0) if self.want_steps else None,
+                torch.stack(self.logprobs, dim=1)[:, :n_keep] if self.logprobs else None)
+
+
+class _SampledPick(_GreedyPick):
+    """HF ``sample`` for n = ``rows`` sequences per prompt, every draw one launch of ``ops.sample_token``: beside the greedy state it owns the
+    seed's device word and, if wanted, the drawn tokens' log-probabilities.  Over the cache the n samples of a prompt share its prefix:
+    each keeps its slot for good (an identity ancestry table), and step 0 draws all n from the prompt's one logits row."""
+
+    def __init__(self, R: int, dev, eos_token_id, pad_token_id, warp, n: int, seed: int, want_steps: bool = False, want_logprobs: bool = False):
+        super().__init__(R, dev, eos_token_id, pad_token_id, want_steps, flags=eos_token_id is not None)
+        self.rows, self.warp, self.key, self.want_logprobs = n, warp, ("sample",) + warp, want_logprobs
+        self.seed = ops.seed_word(seed, dev)
+        self.inputs = (self.seed,)   # a replay of the captured steps reads the seed from this word: a new seed needs no new capture
+
+    def reset(self) -> None:
+        if self.unfinished is not None:
+            self.unfinished.fill_(1)   # the draws update it in place: one buffer, reset at the head of every replay
+        self.tokens, self.steps, self.logprobs = [], [], []
+
+    def start(self, cache: "_DecodeCache") -> None:
+        if self.rows > 1:
+            if not cache.prerot:
+                raise NotImplementedError("sampling n > 1 over the shared prefix needs the pre-rotated cache (rotary dims % 16 == 0, head size 64 / 128 / 256)")
+            # every sample keeps its own slot for good: the ancestry table of the beam attention is the identity
+            cache.anc = torch.arange(self.R, dtype=torch.int32, device=self.dev)[:, None].expand(self.R, cache.cap).contiguous()
+
+    def __call__(self, logits: torch.Tensor, t: int) -> torch.Tensor:
+        if logits.shape[0] != self.R:
+            logits = logits.repeat_interleave(self.rows, 0)   # the prompt's one row, named n times (counters b * n + j)
+        lp = None
+        if self.want_logprobs:
+            lp = torch.empty(self.R, dtype=torch.float32, device=self.dev)
+            self.logprobs.append(lp)
+        temperature, top_k, top_p, min_p = self.warp   # the token rule, one launch; ``unfinished`` is updated in place
+        return self._keep(ops.sample_token(logits, temperature, top_k, top_p, min_p, seed=self.seed, step=t, unfinished=self.unfinished, eos_token_id=self.eos,
+                                           pad_token_id=0 if self.pad is None else self.pad, logprob=lp), logits)
+
+
+class _BeamPick:
+    """Beam search with k = ``rows`` beams per prompt (generate(num_beams=k)); every decision on the device (csrc/beam.hip; the beams'
+    attention is csrc/attn_decode_beam.hip), one host synchronisation in ``result``.
+    Per step: mafed_beam_candidates (top 2k of log_softmax + running score per sample) and mafed_beam_update (finished set,
+    continuing beams, early stopping, ancestry / history rewrite) between two copies of the state, ``cur`` naming the live one.  The loop
+    runs to max_new_tokens like the greedy path: a sample whose result is final stops changing (HF leaves the loop once every sample is
+    such), and the output is cut at the end."""
+
+    key, want_steps = None, False
+
+    def __init__(self, B: int, dev, eos_token_id, pad_token_id, k: int, cap: int, length_penalty: float, early_stopping, nrs: int,
+                 return_dict: bool, trace: Optional[list]):
+        eos, pad = -1 if eos_token_id is None else int(eos_token_id), 0 if pad_token_id is None else int(pad_token_id)
+        self.B, self.rows, self.dev, self.nrs, self.return_dict, self.trace = B, k, dev, nrs, return_dict, trace
+        self.args = (cap, eos, pad, {False: 0, True: 1, "never": 2}[early_stopping], length_penalty)
+        BK = B * k
+        i32, i64, f32 = torch.int32, torch.int64, torch.float32
+        self.cand = (torch.empty((B, 2 * k), dtype=f32, device=dev), torch.empty((B, 2 * k), dtype=i64, device=dev),
+                     torch.empty((B, 2 * k), dtype=i32, device=dev))
+        self.run_score = torch.zeros(BK, dtype=f32, device=dev)
+        self.anc = [torch.zeros((BK, cap), dtype=i32, device=dev) for _ in range(2)]
+        self.hist = [torch.zeros((BK, cap), dtype=i64, device=dev) for _ in range(2)]
+        self.fin_tok = [torch.full((B, k, cap), pad, dtype=i64, device=dev) for _ in range(2)]
+        self.fin_score = [torch.full((B, k), -1e9, dtype=f32, device=dev) for _ in range(2)]
+        self.fin_len = [torch.zeros((B, k), dtype=i32, device=dev) for _ in range(2)]
+        self.done = torch.zeros(B, dtype=i32, device=dev)
+        self.next_tok = torch.zeros(BK, dtype=i64, device=dev)
+        self.cur = 0
+
+    def start(self, cache: "_DecodeCache") -> None:
+        if not cache.prerot:
+            raise NotImplementedError("the cached beam search needs the pre-rotated cache (rotary dims % 16 == 0, head size 64 / 128 / 256)")
+
+    def before_step(self, cache: "_DecodeCache") -> None:
+        cache.anc = self.anc[self.cur]
+
+    def __call__(self, logits: torch.Tensor, t: int) -> torch.Tensor:
+        B, k, cur, o = self.B, self.rows, self.cur, 1 - self.cur
+        score = self.run_score
+        if t == 0 and logits.shape[0] == B:   # the cached loop's prefill, one row per sample: only beam 0 is live there
+            score = torch.zeros(B, dtype=torch.float32, device=self.dev)
+        elif t == 0:   # the recompute loop's B * k rows (HF expands every sample k times): beams 1 .. k-1 start at -1e9, so the first
+            score = torch.full((B, k), -1e9, dtype=torch.float32, device=self.dev)   # step's candidates all come from beam 0
+            score[:, 0] = 0.0
+            score = score.view(B * k)
+        ops.beam_candidates(logits, score, B, k, out=self.cand)
+        if self.trace is not None:   # tests / tools: every step's candidate lists (score, token, parent), copied
+            self.trace.append(tuple(c.clone() for c in self.cand))
+        cap, eos, pad, early, length_penalty = self.args
+        ops.beam_update(self.cand, B, k, t, cap, eos, pad, early, length_penalty, self.run_score, (self.anc[cur], self.anc[o]),
+                        (self.hist[cur], self.hist[o]), (self.fin_tok[cur], self.fin_tok[o]), (self.fin_score[cur], self.fin_score[o]),
+                        (self.fin_len[cur], self.fin_len[o]), self.done, self.next_tok)
+        self.cur = o
+        return self.next_tok
+
+    def drawn(self, t: int) -> torch.Tensor:
+        return self.hist[self.cur][:, :t]   # re-read every step: the beams reorder
+
+    def result(self, ids: torch.Tensor):
+        B, nrs, cur = self.B, self.nrs, self.cur
+        n_keep = int(self.fin_len[cur][:, :nrs].max())   # the one host synchronisation
+        seqs = torch.cat([ids.repeat_interleave(nrs, 0), self.fin_tok[cur][:, :nrs, :n_keep].reshape(B * nrs, n_keep)], dim=1)
+        if self.return_dict:
+            return BeamSearchOutput(sequences=seqs, sequences_scores=self.fin_score[cur][:, :nrs].reshape(B * nrs).clone())
+        return seqs
 
 
 class GenerationMixin:
@@ -67,13 +216,13 @@ class GenerationMixin:
         ``early_stopping`` True / False / "never", ``num_return_sequences`` <= k <= 8) -> [B * num_return_sequences, T + n], rows padded
         with ``pad_token_id`` up to the longest returned hypothesis; ``return_dict_in_generate`` adds the length-normalised
         ``sequences_scores`` (a beam-search option: the greedy path returns its tensor as before).  ``use_cache=False`` recomputes the B * k beams' full sequences every step; ``use_cache=True`` prefills
-        each sample once and decodes its k beams over the shared prefix (``_beam_search``).  Not implemented: sampling (beam-sample
+        each sample once and decodes its k beams over the shared prefix (``_BeamPick``).  Not implemented: sampling (beam-sample
         included), graph capture of the beam loop, diverse / constrained beam search.  Sampled decoding is a method of its own, ``sample``.
 
         ``image_index`` (int64 [B], any device): several prompts about one image.  ``patch_embeddings`` is then [N, P, Dv] (or
         ``pixel_values`` holds N images) and prompt b looks at image ``image_index[b]``; N need not equal B.  ``use_cache=False`` recomputes
         on ``feats.index_select(0, image_index)``; ``use_cache=True`` (greedy and beam) runs the image rows through the stack once per
-        image and the text rows once per prompt (``_prefill_shared``, DESIGN.md section 4c''').  Not with ``use_graph``."""
+        image and the text rows once per prompt (``_prefill_shared_rows``, DESIGN.md section 4c''').  Not with ``use_graph``."""
         if do_sample:
             raise NotImplementedError("sampling (do_sample=True, beam-sample included) is not implemented: greedy or beam search only")
         if kwargs.get("num_beam_groups") not in (None, 1) or kwargs.get("constraints") is not None or kwargs.get("force_words_ids") is not None:
@@ -82,11 +231,9 @@ class GenerationMixin:
             raise ValueError(f"num_beams must be an int in 1 .. 8, got {num_beams!r}")
         if num_return_sequences < 1 or num_return_sequences > num_beams:
             raise ValueError(f"num_return_sequences ({num_return_sequences}) must be in 1 .. num_beams ({num_beams})")
-        if input_ids is None or (pixel_values is None and patch_embeddings is None):
-            raise ValueError("generate needs input_ids and pixel_values / patch_embeddings")
+        feats, ids, am, pad_token_id = self._generate_inputs("generate", input_ids, attention_mask, pixel_values, patch_embeddings, pad_token_id, eos_token_id)
         if use_graph and image_index is not None:
             raise NotImplementedError("use_graph=True (hipGraph capture) is not implemented with image_index")
-        inputs = (input_ids, attention_mask, pixel_values, patch_embeddings, pad_token_id, eos_token_id)
         if num_beams > 1:
             if use_graph:
                 raise NotImplementedError("use_graph=True (hipGraph capture) is not implemented for beam search")
@@ -96,59 +243,52 @@ class GenerationMixin:
                 raise ValueError(f"beam search needs max_new_tokens >= 1, got {max_new_tokens}")
             if early_stopping not in (False, True, "never"):
                 raise ValueError(f"early_stopping must be True, False or 'never', got {early_stopping!r}")
-            feats, ids, am, pad_token_id = self._generate_inputs(*inputs)
-            feats, image_index = self._pair_images(feats, image_index, ids.shape[0], use_cache)
-            return self._beam_search(feats, ids, am, pad_token_id, eos_token_id, num_beams, max_new_tokens, use_cache, float(length_penalty),
-                                     early_stopping, num_return_sequences, return_dict_in_generate, image_index=image_index)
-        feats, ids, am, pad_token_id = self._generate_inputs(*inputs)
         feats, image_index = self._pair_images(feats, image_index, ids.shape[0], use_cache)
+        if num_beams > 1:
+            pick = _BeamPick(ids.shape[0], ids.device, eos_token_id, pad_token_id, num_beams, max_new_tokens, float(length_penalty), early_stopping,
+                             num_return_sequences, return_dict_in_generate, self.beam_trace)
+            return self._decode(pick, feats, ids, am, max_new_tokens, use_cache, image_index=image_index)
+        pick = _GreedyPick(ids.shape[0], ids.device, eos_token_id, pad_token_id, return_step_logits)
+        out, steps, _ = self._decode(pick, feats, ids, am, max_new_tokens, use_cache, use_graph, image_index)
+        return (out, steps) if return_step_logits else out
+
+    def _decode(self, pick, feats, ids, am, max_new: int, use_cache: bool, use_graph: bool = False, image_index: Optional[torch.Tensor] = None):
+        """The decode loop of ``generate`` and ``sample`` around a pick object (``_GreedyPick``) -> ``pick.result``.  It issues launches
+        only: no host synchronisation before the one in ``pick.result``."""
         B, T = ids.shape
-        unfinished = torch.ones(B, dtype=torch.int64, device=ids.device)
-        new_tokens, step_logits = [], []
-
-        def pick(last_logits):
-            nonlocal unfinished
-            nxt, unfinished = _greedy_pick(last_logits, unfinished, eos_token_id, pad_token_id)
-            new_tokens.append(nxt)
-            if return_step_logits:
-                step_logits.append(last_logits.float())
-            return nxt
-
         if not use_cache:
-            cur_ids, cur_am = ids, am
-            for _ in range(max_new_tokens):
-                st = self._engine_forward(feats, cur_ids, cur_am, None, False, train=False)
-                nxt = pick(st["logits"][:, -1, :])
-                cur_ids = torch.cat([cur_ids, nxt[:, None]], dim=1)
-                cur_am = torch.cat([cur_am, torch.ones_like(nxt)[:, None]], dim=1)
-        elif use_graph and not return_step_logits and max_new_tokens > 1:
+            # the reference's literal recompute: the B * rows full sequences through the stack for every token
+            feats_r, ids_r, am_r = _rows(feats, pick.rows), _rows(ids, pick.rows), _rows(am, pick.rows)
+            cur_ids, cur_am = ids_r, am_r
+            for t in range(max_new):
+                st = self._engine_forward(feats_r, cur_ids, cur_am, None, False, train=False)
+                pick(st["logits"][:, -1, :], t)
+                gen = pick.drawn(t + 1)
+                cur_ids, cur_am = torch.cat([ids_r, gen], dim=1), torch.cat([am_r, torch.ones_like(gen)], dim=1)
+        elif use_graph and not pick.want_steps and max_new > 1:
             # opt-in: the nine one-row-per-sample steps (~150 launches of 5-20 us kernels each) captured once per (B, T, max_new)
             # into a hipGraph whose K/V cache lives at fixed addresses (the prefill's QKV GEMMs write straight into it).  It
             # takes the host out of the loop; on an idle host it measures the same as eager launches (24.1 vs 24.2 ms at
             # 410M / B = 32): the steps are bound by the GPU-side cost of that many small kernels.
-            key = (B, T, max_new_tokens, eos_token_id, pad_token_id)
+            key = (B, T, max_new, pick.eos, pick.pad) + pick.key
             gd = self._decode_graphs.get(key)
             if gd is None:
-                gd = self._decode_graphs[key] = _GraphedDecode(self, B, T, max_new_tokens, eos_token_id, pad_token_id)
-            gen_all = gd.run(feats, ids, am)
-            new_tokens = list(gen_all.unbind(1))
+                gd = self._decode_graphs[key] = _GraphedDecode(self, B, T, max_new, pick)
+            return gd.run(feats, ids, am, pick)
         else:
-            cache, first_logits = self._prefill(feats, ids, am, max_new_tokens, image_index=image_index)
-            nxt = pick(first_logits)
-            for t in range(max_new_tokens - 1):
-                nxt = pick(self._engine_decode_step(nxt, t, cache))
-        gen = torch.stack(new_tokens, dim=1)
-        if eos_token_id is not None:
-            # HF leaves the loop as soon as every row has finished: the output is as long as the slowest row needed
-            done = (gen == eos_token_id).to(torch.int64).cumsum(1).clamp_(max=1)       # 1 from the first eos on
-            first = (done.shape[1] - done.sum(1)) + done[:, -1]                        # tokens up to and including the first eos
-            n_keep = int(first.max().clamp_(max=gen.shape[1]))
-            gen = gen[:, :n_keep]
-            step_logits = step_logits[:n_keep]
-        out = torch.cat([ids, gen], dim=1)
-        if return_step_logits:
-            return out, torch.stack(step_logits, dim=0)
-        return out
+            # one prefill per prompt: its last-position logits are the first step's, its K/V the prefix that the prompt's rows share
+            cache, first_logits = self._prefill(feats, ids, am, max_new, beams=pick.rows, image_index=image_index)
+            pick.start(cache)
+            self._decode_steps(pick, cache, first_logits, max_new)
+        return pick.result(ids)
+
+    def _decode_steps(self, pick, cache: "_DecodeCache", first_logits: torch.Tensor, max_new: int) -> None:
+        """The cached loop: a pick from the prompt's logits, then max_new - 1 times one row per sequence through the stack and a pick
+        from its logits.  Run eagerly by ``_decode`` and captured by ``_GraphedDecode``."""
+        nxt = pick(first_logits, 0)
+        for t in range(max_new - 1):
+            pick.before_step(cache)
+            nxt = pick(self._engine_decode_step(nxt, t, cache), t + 1)
 
     # ---- sampled decode (DESIGN.md section 4c'') -----------------------------------------------------------------------
     @torch.no_grad()
@@ -189,71 +329,17 @@ class GenerationMixin:
             raise ValueError(f"seed must be an int that fits a uint64, got {seed!r}")
         if max_new_tokens < 1:
             raise ValueError(f"sample needs max_new_tokens >= 1, got {max_new_tokens}")
-        if input_ids is None or (pixel_values is None and patch_embeddings is None):
-            raise ValueError("sample needs input_ids and pixel_values / patch_embeddings")
+        feats, ids, am, pad_token_id = self._generate_inputs("sample", input_ids, attention_mask, pixel_values, patch_embeddings, pad_token_id, eos_token_id)
         if use_graph and (n > 1 or not use_cache or return_step_logits):
             raise NotImplementedError("use_graph=True serves the cached n = 1 path without return_step_logits")
         if use_graph and image_index is not None:
             raise NotImplementedError("use_graph=True (hipGraph capture) is not implemented with image_index")
-        feats, ids, am, pad_token_id = self._generate_inputs(input_ids, attention_mask, pixel_values, patch_embeddings, pad_token_id, eos_token_id)
         feats, image_index = self._pair_images(feats, image_index, ids.shape[0], use_cache)
-        dev = ids.device
-        B, T = ids.shape
-        R = B * n
-        warp = (float(temperature), int(top_k), float(top_p), float(min_p))
-        if use_graph and max_new_tokens > 1:
-            key = (B, T, max_new_tokens, eos_token_id, pad_token_id, "sample") + warp
-            gd = self._decode_graphs.get(key)
-            if gd is None:
-                gd = self._decode_graphs[key] = _GraphedDecode(self, B, T, max_new_tokens, eos_token_id, pad_token_id, sample=warp)
-            gen, logprobs = gd.run(feats, ids, am, seed=seed)
-            step_logits = []
-        else:
-            seed_dev = ops.seed_word(seed, dev)
-            unfinished = torch.ones(R, dtype=torch.int64, device=dev) if eos_token_id is not None else None
-            new_tokens, new_logprobs, step_logits = [], [], []
-
-            def pick(last_logits, t):
-                lp = torch.empty(R, dtype=torch.float32, device=dev) if return_logprobs else None
-                nxt = _sample_pick(last_logits, warp, seed_dev, t, unfinished, eos_token_id, pad_token_id, lp)
-                new_tokens.append(nxt)
-                new_logprobs.append(lp)
-                if return_step_logits:
-                    step_logits.append(last_logits.float())
-                return nxt
-
-            if not use_cache:
-                feats_n, cur_ids, cur_am = feats.repeat_interleave(n, 0), ids.repeat_interleave(n, 0), am.repeat_interleave(n, 0)
-                for t in range(max_new_tokens):
-                    st = self._engine_forward(feats_n, cur_ids, cur_am, None, False, train=False)
-                    nxt = pick(st["logits"][:, -1, :], t)
-                    cur_ids = torch.cat([cur_ids, nxt[:, None]], dim=1)
-                    cur_am = torch.cat([cur_am, torch.ones_like(nxt)[:, None]], dim=1)
-            else:
-                cache, first_logits = self._prefill(feats, ids, am, max_new_tokens, beams=n, image_index=image_index)
-                if n > 1:
-                    if not cache.prerot:
-                        raise NotImplementedError("sampling n > 1 over the shared prefix needs the pre-rotated cache (rotary dims % 16 == 0, head size 64 / 128 / 256)")
-                    # every sample keeps its own slot for good: the ancestry table of the beam attention is the identity
-                    cache.anc = torch.arange(R, dtype=torch.int32, device=dev)[:, None].expand(R, cache.cap).contiguous()
-                    first_logits = first_logits.repeat_interleave(n, 0)   # the prompt's one row, named n times (counters b * n + j)
-                nxt = pick(first_logits, 0)
-                for t in range(max_new_tokens - 1):
-                    nxt = pick(self._engine_decode_step(nxt, t, cache), t + 1)
-            gen = torch.stack(new_tokens, dim=1)
-            logprobs = torch.stack(new_logprobs, dim=1) if return_logprobs else None
-        if eos_token_id is not None:
-            done = (gen == eos_token_id).to(torch.int64).cumsum(1).clamp_(max=1)       # 1 from the first eos on
-            first = (done.shape[1] - done.sum(1)) + done[:, -1]                        # tokens up to and including the first eos
-            n_keep = int(first.max().clamp_(max=gen.shape[1]))                         # the one host synchronisation
-            gen = gen[:, :n_keep]
-            step_logits = step_logits[:n_keep]
-            logprobs = logprobs[:, :n_keep] if logprobs is not None else None
-        out = (torch.cat([ids.repeat_interleave(n, 0) if n > 1 else ids, gen], dim=1),)
-        if return_step_logits:
-            out += (torch.stack(step_logits, dim=0),)
-        if return_logprobs:
-            out += (logprobs,)
+        # (a captured pick serves later calls with and without log-probabilities: it always takes them)
+        pick = _SampledPick(ids.shape[0] * n, ids.device, eos_token_id, pad_token_id, (float(temperature), int(top_k), float(top_p), float(min_p)),
+                            n, seed, return_step_logits, return_logprobs or use_graph)
+        out = self._decode(pick, feats, ids, am, max_new_tokens, use_cache, use_graph, image_index)
+        out = tuple(o for o, wanted in zip(out, (True, return_step_logits, return_logprobs)) if wanted)
         return out[0] if len(out) == 1 else out
 
     # ---- candidate scoring (DESIGN.md section 4c'''') -------------------------------------------------------------------
@@ -285,9 +371,7 @@ class GenerationMixin:
         ``model.prefill_trace`` (a list) receives {"prefix_rows", "candidate_rows"}: the rows that went through the stack."""
         if normalize not in ("sum", "mean"):
             raise ValueError(f"normalize must be 'sum' or 'mean', got {normalize!r}")
-        if input_ids is None or (pixel_values is None and patch_embeddings is None):
-            raise ValueError("score needs input_ids and pixel_values / patch_embeddings")
-        feats, ids, am, _ = self._generate_inputs(input_ids, attention_mask, pixel_values, patch_embeddings, None, None)
+        feats, ids, am, _ = self._generate_inputs("score", input_ids, attention_mask, pixel_values, patch_embeddings, None, None)
         cfg, dev = self.config, ids.device
         B, T = ids.shape
         cand = candidate_ids
@@ -337,13 +421,8 @@ class GenerationMixin:
         P, h, H, D, L = cfg.num_vision_tokens, cfg.hidden_size, cfg.num_attention_heads, cfg.head_dim, cfg.num_hidden_layers
         (B, T), (_, C, A), dev = ids.shape, tok.shape, ids.device
         S0, BC, rot = P + T, B * C, cfg.rotary_ndims
-        if image_index is None:
-            store = self._prefix_store(B, T)
-            first = self._engine_forward(feats, ids, am, None, False, train=False, qkv_out=list(store.unbind(0)), last_only=True)["logits"][:, -1, :]
-            prefix_rows = B * S0
-        else:
-            store, first, _ = self._prefill_shared_rows(feats, image_index, ids, am)
-            prefix_rows = feats.shape[0] * P + B * T
+        store, first, _ = self._prefix_rows(feats, ids, am, image_index)
+        prefix_rows = feats.shape[0] * P + B * T   # every image once (without an index: one per prompt), every prompt's text once
         # token 0 of all C candidates of a prompt reads the prompt's one logits row
         row0 = torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(C)
         lp0 = ops.token_logprob(first, tgt[:, :, 0].contiguous(), row0)
@@ -361,8 +440,11 @@ class GenerationMixin:
         lp1 = ops.token_logprob(self._lm_head(x.view(BC, A_run, h)[:, :A - 1, :].reshape(BC * (A - 1), h)), tgt[:, :, 1:].contiguous())
         return torch.cat([lp0.view(B, C, 1), lp1], dim=2), {"prefix_rows": prefix_rows, "candidate_rows": BC * A_run}
 
-    def _generate_inputs(self, input_ids, attention_mask, pixel_values, patch_embeddings, pad_token_id, eos_token_id):
-        """-> (vision features, token ids, attention mask) on the model's device and the effective ``pad_token_id``."""
+    def _generate_inputs(self, what: str, input_ids, attention_mask, pixel_values, patch_embeddings, pad_token_id, eos_token_id):
+        """The inputs of entry point ``what`` -> (vision features, token ids, attention mask) on the model's device and the effective
+        ``pad_token_id``."""
+        if input_ids is None or (pixel_values is None and patch_embeddings is None):
+            raise ValueError(f"{what} needs input_ids and pixel_values / patch_embeddings")
         dev = self.flat_params.device
         feats = (patch_embeddings if patch_embeddings is not None else self.get_patch_embeddings(pixel_values)).to(dev).contiguous()
         ids = input_ids.to(dev, torch.int64).contiguous()
@@ -400,25 +482,24 @@ class GenerationMixin:
 
     def _prefill(self, feats, ids, am, cap: int, beams: int = 1, image_index: Optional[torch.Tensor] = None) -> Tuple["_DecodeCache", torch.Tensor]:
         """Run the prompt once, its QKV GEMMs writing straight into a fresh prefix store -> (the decode cache over it, the last
-        position's logits [B, V]).  With ``image_index``: the shared-image form, ``_prefill_shared``."""
-        if image_index is not None:
-            return self._prefill_shared(feats, image_index, ids, am, cap, beams)
-        B, T = ids.shape
-        store = self._prefix_store(B, T)
-        st = self._engine_forward(feats, ids, am, None, False, train=False, qkv_out=list(store.unbind(0)), last_only=True)
-        cache = _DecodeCache(self, list(store.unbind(0)), B, st["S"], cap, am, fused=self.fused_decode, prefix_storage=store, beams=beams)
-        return cache, st["logits"][:, -1, :]
-
-    def _prefill_shared(self, feats, image_index, ids, am, cap: int, beams: int = 1) -> Tuple["_DecodeCache", torch.Tensor]:
-        """``_prefill`` for B prompts over the N images of ``feats`` (DESIGN.md section 4c'''): ``_prefill_shared_rows``, then the decode cache over
-        the assembled prefix (which rotates the prefix keys as ever)."""
-        store, logits, record = self._prefill_shared_rows(feats, image_index, ids, am)
-        if self.prefill_trace is not None:   # tests / tools: the row counts that went through the stack
+        position's logits [B, V]).  With ``image_index``: over the shared-image prefix of ``_prefix_rows`` (DESIGN.md section 4c''')."""
+        store, logits, record = self._prefix_rows(feats, ids, am, image_index)
+        if record is not None and self.prefill_trace is not None:   # tests / tools: the row counts that went through the stack
             self.prefill_trace.append(record)
         B, T = ids.shape
         cache = _DecodeCache(self, list(store.unbind(0)), B, self.config.num_vision_tokens + T, cap, am, fused=self.fused_decode,
-                             prefix_storage=store, beams=beams)
+                             prefix_storage=store, beams=beams)   # (rotates the prefix keys)
         return cache, logits
+
+    def _prefix_rows(self, feats, ids, am, image_index: Optional[torch.Tensor] = None, store: Optional[torch.Tensor] = None):
+        """The prefix rows of a prompt -> (prefix store [L, B*S0, 3h] with un-rotated keys, the last position's logits [B, V], the trace
+        record or None).  Without ``image_index`` the engine forward's QKV GEMMs write straight into a fresh store (or the given ``store``,
+        the captured graph's) and there is no record; with it the image rows run once per image: ``_prefill_shared_rows``."""
+        if image_index is not None:
+            return self._prefill_shared_rows(feats, image_index, ids, am)
+        store = self._prefix_store(*ids.shape) if store is None else store
+        st = self._engine_forward(feats, ids, am, None, False, train=False, qkv_out=list(store.unbind(0)), last_only=True)
+        return store, st["logits"][:, -1, :], None
 
     def _prefill_shared_rows(self, feats, image_index, ids, am) -> Tuple[torch.Tensor, torch.Tensor, dict]:
         """The prompt rows of B prompts over the N images of ``feats`` -> (prefix store [L, B*S0, 3h] with un-rotated keys, the last position's
@@ -461,71 +542,6 @@ class GenerationMixin:
         # prefix assembly: [image of the prompt | its text] per layer, one launch for all of them
         store = ops.prefix_gather(img_store, txt_store, image_index, B, P, T, out=self._prefix_store(B, T))
         return store, logits, {"image_store": tuple(img_store.shape), "text_store": tuple(txt_store.shape), "prefix": tuple(store.shape)}
-
-    def _beam_search(self, feats, ids, am, pad_token_id, eos_token_id, k: int, max_new: int, use_cache: bool, length_penalty: float,
-                     early_stopping, nrs: int, return_dict: bool, image_index: Optional[torch.Tensor] = None):
-        """Beam search (generate(num_beams=k)); every decision on the device (csrc/beam.hip; the beams' attention is
-        csrc/attn_decode_beam.hip), one host synchronisation at the end.
-        Per step: mafed_beam_candidates (top 2k of log_softmax + running score per sample) and mafed_beam_update (finished set,
-        continuing beams, early stopping, ancestry / history rewrite).  The loop runs to max_new_tokens like the greedy path: a sample
-        whose result is final stops changing (HF leaves the loop once every sample is such), and the output is cut at the end."""
-        dev = ids.device
-        eos = -1 if eos_token_id is None else int(eos_token_id)
-        pad = 0 if pad_token_id is None else int(pad_token_id)
-        early = {False: 0, True: 1, "never": 2}[early_stopping]
-        B, T = ids.shape
-        BK, cap = B * k, max_new
-        i32, i64, f32 = torch.int32, torch.int64, torch.float32
-        cand = (torch.empty((B, 2 * k), dtype=f32, device=dev), torch.empty((B, 2 * k), dtype=i64, device=dev),
-                torch.empty((B, 2 * k), dtype=i32, device=dev))
-        run_score = torch.zeros(BK, dtype=f32, device=dev)
-        anc = [torch.zeros((BK, cap), dtype=i32, device=dev) for _ in range(2)]
-        hist = [torch.zeros((BK, cap), dtype=i64, device=dev) for _ in range(2)]
-        fin_tok = [torch.full((B, k, cap), pad, dtype=i64, device=dev) for _ in range(2)]
-        fin_score = [torch.full((B, k), -1e9, dtype=f32, device=dev) for _ in range(2)]
-        fin_len = [torch.zeros((B, k), dtype=i32, device=dev) for _ in range(2)]
-        done = torch.zeros(B, dtype=i32, device=dev)
-        next_tok = torch.zeros(BK, dtype=i64, device=dev)
-        cur = 0
-
-        def beam_step(logits, score, n):
-            nonlocal cur
-            ops.beam_candidates(logits, score, B, k, out=cand)
-            if self.beam_trace is not None:   # tests / tools: every step's candidate lists (score, token, parent), copied
-                self.beam_trace.append(tuple(c.clone() for c in cand))
-            o = 1 - cur
-            ops.beam_update(cand, B, k, n, cap, eos, pad, early, length_penalty, run_score, (anc[cur], anc[o]), (hist[cur], hist[o]),
-                            (fin_tok[cur], fin_tok[o]), (fin_score[cur], fin_score[o]), (fin_len[cur], fin_len[o]), done, next_tok)
-            cur = o
-
-        if not use_cache:
-            # the reference's literal recompute: the B * k beams' full sequences through the stack every step (HF expands every
-            # sample k times; beams 1 .. k-1 start at -1e9, so the first step's candidates all come from beam 0)
-            feats_k, ids_k, am_k = feats.repeat_interleave(k, 0), ids.repeat_interleave(k, 0), am.repeat_interleave(k, 0)
-            score0 = torch.full((B, k), -1e9, dtype=f32, device=dev)
-            score0[:, 0] = 0.0
-            score0 = score0.view(BK)
-            for n in range(max_new):
-                cur_ids = torch.cat([ids_k, hist[cur][:, :n]], dim=1)
-                cur_am = torch.cat([am_k, torch.ones((BK, n), dtype=i64, device=dev)], dim=1)
-                st = self._engine_forward(feats_k, cur_ids, cur_am, None, False, train=False)
-                beam_step(st["logits"][:, -1, :], score0 if n == 0 else run_score, n)
-        else:
-            # one prefill per sample: its last-position logits are the first step's (only beam 0 is live there), its K/V the prefix
-            # that the sample's k beams share
-            cache, first_logits = self._prefill(feats, ids, am, max_new, beams=k, image_index=image_index)
-            if not cache.prerot:
-                raise NotImplementedError("the cached beam search needs the pre-rotated cache (rotary dims % 16 == 0, head size 64 / 128 / 256)")
-            beam_step(first_logits, torch.zeros(B, dtype=f32, device=dev), 0)
-            for t in range(max_new - 1):
-                cache.anc = anc[cur]
-                beam_step(self._engine_decode_step(next_tok, t, cache), run_score, t + 1)
-        lens = fin_len[cur][:, :nrs]
-        n_keep = int(lens.max())   # the one host synchronisation
-        seqs = torch.cat([ids.repeat_interleave(nrs, 0), fin_tok[cur][:, :nrs, :n_keep].reshape(B * nrs, n_keep)], dim=1)
-        if return_dict:
-            return BeamSearchOutput(sequences=seqs, sequences_scores=fin_score[cur][:, :nrs].reshape(B * nrs).clone())
-        return seqs
 
     def _engine_decode_step(self, tokens: torch.Tensor, t: int, cache: "_DecodeCache") -> torch.Tensor:
         """One token per sample through the stack: ``tokens`` [B] sit at position S0 + t; returns the logits [B, V]."""
@@ -603,45 +619,26 @@ class _DecodeCache:
 
 
 class _GraphedDecode:
-    """Greedy decode steps 1 .. max_new-1 for one (B, T, max_new) shape as a single hipGraph.  Static buffers: the per-layer
-    K/V cache (prefix written by the prefill's QKV GEMMs through ``qkv_out``, plus the per-token rows), the prompt mask, the
-    prefill's last-position logits, the ``unfinished`` flags and the generated tokens.
-    ``sample`` = (temperature, top_k, top_p, min_p): the captured pick is ``_sample_pick`` instead; it reads the seed from the static
-    device word ``self.seed``, which ``run`` rewrites before the replay, and fills ``self.logprobs`` beside the tokens."""
+    """The decode steps of ``_decode_steps`` for one (B, T, max_new) shape and one pick object as a single hipGraph.  Static buffers: the
+    per-layer K/V cache (prefix written by the prefill's QKV GEMMs through ``qkv_out``, plus the per-token rows), the prompt mask, the
+    prefill's last-position logits and what the pick owns: the capture leaves its tokens (and log-probabilities) at fixed addresses, which
+    every replay fills again; ``pick.inputs`` (the sampled pick's seed word) are rewritten by ``run`` before the replay."""
 
-    def __init__(self, model, B: int, T: int, max_new: int, eos_token_id, pad_token_id, sample=None):
+    def __init__(self, model, B: int, T: int, max_new: int, pick):
         cfg = model.config
         dev, cd = model.flat_params.device, model.compute_dtype
         S0 = cfg.num_vision_tokens + T
-        self.model, self.B, self.T, self.S0, self.max_new = model, B, T, S0, max_new
+        self.model, self.pick = model, pick
         store = model._prefix_store(B, T)
         self.am = torch.ones((B, T), dtype=torch.int64, device=dev)
-        self.first_logits = torch.zeros((B, cfg.vocab_size), dtype=cd if cd != torch.float32 else torch.float32, device=dev)
-        self.tokens = torch.zeros((B, max_new), dtype=torch.int64, device=dev)
-        self.sample = sample
-        if sample is not None:
-            self.seed = ops.seed_word(0, dev)
-            self.logprobs = torch.zeros((B, max_new), dtype=torch.float32, device=dev)
-            self.unfinished = torch.ones(B, dtype=torch.int64, device=dev) if eos_token_id is not None else None
+        self.first_logits = torch.zeros((B, cfg.vocab_size), dtype=cd, device=dev)
         model.rotary_tables(S0 + max(1, max_new))  # built (host -> device copy) before the capture, not inside it
         self.cache = _DecodeCache(model, list(store.unbind(0)), B, S0, max_new, self.am, fused=model.fused_decode,
                                   prefix_storage=store)   # (rotates the still-empty prefix once: harmless)
 
         def body():
-            if sample is not None and self.unfinished is not None:
-                self.unfinished.fill_(1)
-            unfinished = torch.ones(B, dtype=torch.int64, device=dev) if sample is None else self.unfinished
-            logits = self.first_logits
-            for t in range(max_new):
-                if sample is None:
-                    nxt, unfinished = _greedy_pick(logits, unfinished, eos_token_id, pad_token_id)
-                else:
-                    lp = torch.empty(B, dtype=torch.float32, device=dev)
-                    nxt = _sample_pick(logits, sample, self.seed, t, unfinished, eos_token_id, pad_token_id, lp)
-                    self.logprobs[:, t] = lp
-                self.tokens[:, t] = nxt
-                if t + 1 < max_new:
-                    logits = model._engine_decode_step(nxt, t, self.cache)
+            pick.reset()   # inside the capture: every replay starts from fresh ``unfinished`` flags
+            model._decode_steps(pick, self.cache, self.first_logits, max_new)
 
         # one eager pass on a side stream (lazy initialisations must not happen inside the capture), then the capture
         side = torch.cuda.Stream(device=dev)
@@ -653,17 +650,14 @@ class _GraphedDecode:
         with torch.cuda.graph(self.graph):
             body()
 
-    def run(self, feats, ids, am, seed: Optional[int] = None):
-        """-> the generated tokens [B, max_new]; with a sampling pick (``seed`` given) -> (tokens, log-probabilities)."""
-        m = self.model
-        if self.sample is not None:
-            self.seed.copy_(ops.seed_word(seed, self.seed.device))
-        st = m._engine_forward(feats, ids, am, None, False, train=False, qkv_out=self.cache.prefix, last_only=True)
+    def run(self, feats, ids, am, pick):
+        """Prefill into the static cache, replay -> the captured pick's result; ``pick``: this call's, of the captured one's key."""
+        for mine, given in zip(self.pick.inputs, pick.inputs):
+            mine.copy_(given)
+        _, first_logits, _ = self.model._prefix_rows(feats, ids, am, store=self.cache.prefix_storage)
         if self.cache.prerot:
             self.cache.rotate_prefix()   # this prefill's keys, rotated in place for the captured steps
         self.am.copy_(am)
-        self.first_logits.copy_(st["logits"][:, -1, :])
+        self.first_logits.copy_(first_logits)
         self.graph.replay()
-        if self.sample is not None:
-            return self.tokens.clone(), self.logprobs.clone()
-        return self.tokens.clone()
+        return self.pick.result(ids)

@@ -289,7 +289,7 @@ class VLPythiaForCausalLM(EngineMixin, GenerationMixin, nn.Module):
         self.beam_trace: Optional[List[Any]] = None   # a list: generate(num_beams > 1) appends every step's candidate lists to it
         self.prefill_trace: Optional[List[Any]] = None   # a list: a shared-image prefill (image_index) appends the shapes of its three stores to it
         self.fused_decode = True    # written by callers (tests, tools/decode_bench.py): False = the six-launch decode layer; read when a decode cache is built
-        self._decode_graphs: Dict[Tuple, Any] = {}   # written and read by generate(use_graph=True): (B, T, max_new, eos, pad) -> _GraphedDecode
+        self._decode_graphs: Dict[Tuple, Any] = {}   # written and read by generation._decode (generate / sample with use_graph=True): (B, T, max_new, eos, pad) + the pick object's key -> _GraphedDecode
         # The hand-over of a backward sweep (engine.BackwardSweep).  Its inputs are the attributes below, written by Trainer._device_step and
         # the optimiser before it; what it reports -- its serial, whether its weight-gradient GEMMs fill `dw_sumsq`, the end of its dX chain --
         # is the SweepRecord it leaves in `last_sweep`, which the clip norm (optim.IncrementalNorm) and Trainer read.

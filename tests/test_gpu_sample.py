@@ -212,6 +212,27 @@ def test_sample_fp32_matches_the_oracle_loop(case, use_cache):
     close(lp, logprobs, 1e-4, "log-probabilities of the drawn tokens")
 
 
+@pytest.mark.parametrize("use_cache", [True, False])
+@pytest.mark.parametrize("case", ["t64_n1_eos", "t128_n3_eos"])
+def test_sample_step_logits_and_logprobs_share_the_eos_cut(case, use_cache):
+    """7b: with an eos, step logits and log-probabilities asked for together: both are cut where the sequences are, and stay in step with them."""
+    cfg, sd, batch, n, warp, eos, seed, tokens, logprobs, edge = _e2e(case)
+    assert eos is not None
+    model = build_model(cfg, sd)
+    b = to_dev(batch)
+    out, steps, lp = _sample(model, b, n, warp, eos, seed, use_cache=use_cache, return_step_logits=True, return_logprobs=True)
+    T = b["input_ids"].shape[1]
+    kept = out.shape[1] - T
+    assert steps.shape == (kept, tokens.shape[0], cfg.vocab_size) and lp.shape == (tokens.shape[0], kept), (steps.shape, lp.shape, out.shape)
+    assert torch.equal(out[:, T:].cpu(), tokens), (out[:, T:].cpu(), tokens)
+    close(lp, logprobs, 1e-4, "log-probabilities of the drawn tokens")
+    gen = out[:, T:]
+    before = torch.cat([torch.zeros_like(gen[:, :1]), (gen == eos).to(torch.int64).cumsum(1)[:, :-1]], dim=1)   # eos tokens before step t
+    drawn = steps.permute(1, 0, 2).gather(2, gen[:, :, None])[:, :, 0]   # [R, kept]: the logit of the token drawn at (row, step)
+    unfinished = before == 0
+    assert bool(unfinished[:, 0].all()) and bool(torch.isfinite(drawn[unfinished]).all()), drawn
+
+
 @pytest.mark.parametrize("case", ["t64_n1", "t64_n1_eos", "t128_n1"])
 def test_sample_graph_replay_equals_eager(case):
     """8: the decode steps replayed from one hipGraph; a new seed and new prompts need no new capture."""
