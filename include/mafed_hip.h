@@ -459,6 +459,24 @@ typedef struct mafed_cka_product {
 size_t mafed_cka_hsic_workspace_bytes(const mafed_cka_product* products, int count);
 int mafed_cka_hsic(const mafed_cka_product* products, int count, double* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- replay-memory selection in a feature space ---------------------------------------------------------------
+ * Replaces: the memory sub-sampling of mafed/methods/replay.py and distillation.py:182-209 (rng.choice) by the two standard
+ * selections, herding (iCaRL) and k-center greedy, over X fp32 [n, d] (row stride ldx >= d) with its fp64 column mean
+ * (mafed_cka_stats).  k greedy picks from one call, two launches per pick, nothing read back in between.
+ *   dist(i, v) = sum_j (X[i, j] - v[j])^2, fp32, direct differences; its bits depend on row i's contents and on v only.
+ *   A row is eligible while it is not picked and its score is not NaN; ties go to the lowest row; when no row is left the
+ *   remaining picks are -1 and their values NaN.
+ *   herding:  r_0 = mean; pick t minimises dist(i, fp32(r_t)); values[t] = that minimum; r_{t+1} = (r_t + mean) - X[p_t] in fp64.
+ *   k-center: pick 0 is herding's pick 0 (values[0] = its distance to the mean); m_i = +inf; for t >= 1
+ *             m_i = min(m_i, dist(i, X[p_{t-1}])), pick t maximises m_i, values[t] = that maximum.
+ *   last_scores[i] (may be NULL): the score row i had in the last pick, picked rows included.
+ * picks int64 [k], values fp32 [k], 1 <= k <= n < 2^31 - 1.  16-byte loads when d % 4 == 0, ldx % 4 == 0 and X is 16-byte
+ * aligned; any d >= 1 otherwise.  Deterministic.  workspace: mafed_select_workspace_bytes(n, d) bytes, 16-byte aligned. */
+enum { MAFED_SELECT_HERDING = 0, MAFED_SELECT_KCENTER = 1 };
+size_t mafed_select_workspace_bytes(int64_t n, int64_t d);
+int mafed_select_greedy(const float* X, int64_t n, int64_t d, int64_t ldx, const double* mean, int mode, int64_t k, int64_t* picks,
+                        float* values, float* last_scores, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- embedding + concat (mafed/model/vl_pythia.py:282-283) ---------------------------------------------------
  * h0[b, :P] = image[b] ; h0[b, P:] = embed_in[input_ids[b]]  -> fp32 [B,P+T,h].  image in img_dtype [B,P,h]. */
 int mafed_embed_concat_fwd(const void* image, mafed_dtype img_dtype, const float* embed_in, const int64_t* input_ids,

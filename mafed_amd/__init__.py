@@ -11,4 +11,5 @@ from mafed_amd.runtime_env import apply_recommended_runtime_env, runtime_env  # 
 from mafed_amd.methods import AGEM, CLMethod, CLStrategy, ER, EWC, FeatureDistillation, LwF, MAS, Naive, PackNet, SI  # noqa: F401
 from mafed_amd.model import VLPythiaConfig, VLPythiaForCausalLM, model_architecture  # noqa: F401
 from mafed_amd.optim import FlatAdam, FlatAdamax, FlatAdamW, get_linear_schedule_with_warmup  # noqa: F401
+from mafed_amd.selection import MemorySelection, select_rows  # noqa: F401
 from mafed_amd.trainer import Trainer  # noqa: F401

@@ -78,6 +78,8 @@ SIGNATURES = {
     "mafed_cka_stats": (_i, [_p, _l, _l, _l, _l, _l, _p, _p, _p, _z, _p]),
     "mafed_cka_hsic_workspace_bytes": (_z, [_p, _i]),
     "mafed_cka_hsic": (_i, [_p, _i, _p, _p, _z, _p]),
+    "mafed_select_workspace_bytes": (_z, [_l, _l]),
+    "mafed_select_greedy": (_i, [_p, _l, _l, _l, _p, _i, _l, _p, _p, _p, _p, _z, _p]),
     "mafed_colsum_workspace_bytes": (_z, [_l, _l]),
     "mafed_colsum": (_i, [_p, _i, _l, _l, _l, _p, _p, _z, _p]),
     "mafed_layernorm_fwd": (_i, [_p, _l, _i, _f, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),

@@ -17,7 +17,9 @@ import torch
 from mafed_amd import ops
 from mafed_amd.methods.base import CLStrategy
 from mafed_amd.methods.distillation_loss_weights import DistillationWeights
-from mafed_amd.methods.memory import HBMReplayBuffer
+from mafed_amd.methods.flat import require_native
+from mafed_amd.methods.memory import HBMReplayBuffer, dataset_len, take_samples
+from mafed_amd.methods.replay import make_memory_selection, select_memory_indices
 
 
 import os as _os
@@ -146,7 +148,7 @@ class FeatureDistillation(CLStrategy):
     def __init__(self, memory_size, opts, model_type, distillation_modality_weighing_strategy="equal",
                  distillation_layer_weighing_strategy="single", distillation_coeff=1.0, replay_coeff=1.0,
                  distillation_layer=-1, cls_distillation=False, distillation_loss="mse", gamma: float = 0.8,
-                 num_hidden_layers: int = 11, **kwargs):
+                 num_hidden_layers: int = 11, memory_selection=None, **kwargs):
         super().__init__(opts=opts, **{k: v for k, v in kwargs.items() if k in ("reg_lambda", "mask", "scaler")})
         self.memory_size = memory_size
         num_mem_tasks = len(opts.tasks) - 1
@@ -156,6 +158,8 @@ class FeatureDistillation(CLStrategy):
         self.seed = 1
         self.datasets: List = []
         self.rng = np.random.default_rng(opts.seed)  # memory sub-sampling stream, as upstream (distillation.py:45)
+        # None: that random subset.  "herding" / "kcenter" / a MemorySelection: chosen in the new teacher's pooled feature space
+        self.memory_selection = make_memory_selection(memory_selection)
         self.pin_mem = getattr(opts, "pin_mem", False)
         self.step = 0
         self.model_type = model_type
@@ -194,6 +198,10 @@ class FeatureDistillation(CLStrategy):
 
     # ---- between tasks -----------------------------------------------------------------------------------------------
     def update(self, dataset, model, dataloader, mask=None, **kwargs):
+        if self.memory_selection is not None:   # (raises before the teacher is replaced)
+            if model is None:
+                raise ValueError("FeatureDistillation: memory_selection needs the model that finished the task")
+            require_native(model, "FeatureDistillation", "memory_selection reads its pooled hidden states (model.pooled_features)")
         self._update_model(model)
         self._update_memory(dataset)
         self.loss_weights.update_weights(model, dataloader, self.task_id)
@@ -210,21 +218,20 @@ class FeatureDistillation(CLStrategy):
             p.requires_grad_(False)
 
     def _update_memory(self, dataset):
-        """Keep ``memory_per_task`` random samples of the finished task (distillation.py:182-209).
+        """Keep ``memory_per_task`` samples of the finished task: a random subset (distillation.py:182-209), or with ``memory_selection``
+        set the ones it picks in the new teacher's feature space.
 
         ``dataset`` may be (a) an ``HBMReplayBuffer``-compatible dict of collated tensors, (b) any map-style dataset
         whose items are dicts of tensors of equal text length (collated with torch.stack)."""
-        n = len(dataset["input_ids"]) if isinstance(dataset, dict) else len(dataset)
+        n = dataset_len(dataset)
         k = min(self.memory_per_task, n)
-        idx = self.rng.choice(np.arange(n), k, replace=False)
+        if self.memory_selection is None:
+            idx = self.rng.choice(np.arange(n), k, replace=False)
+        else:
+            idx = select_memory_indices(self.memory_selection, self.past_model, dataset, k, "FeatureDistillation")
         assert len(set(idx.tolist())) == k
         self.seed = 1
-        if isinstance(dataset, dict):
-            sel = torch.as_tensor(np.sort(idx))
-            samples = {key: dataset[key][sel] for key in HBMReplayBuffer.KEYS}
-        else:
-            items = [dataset[int(i)] for i in idx]
-            samples = {key: torch.stack([torch.as_tensor(it[key]) for it in items]) for key in HBMReplayBuffer.KEYS}
+        samples = take_samples(dataset, idx, HBMReplayBuffer.KEYS)
         self.datasets.append(samples)
         if not isinstance(self.mem_dataloader, HBMReplayBuffer):
             import torch.distributed as dist

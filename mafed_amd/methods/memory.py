@@ -10,7 +10,31 @@ from __future__ import annotations
 
 from typing import Dict, Iterator, List, Optional
 
+import numpy as np
 import torch
+
+
+def dataset_len(dataset) -> int:
+    """Samples of a task dataset in either form the plugins accept: a dict of collated tensors or a map-style dataset."""
+    return len(dataset["input_ids"]) if isinstance(dataset, dict) else len(dataset)
+
+
+def take_samples(dataset, idx, keys) -> Dict[str, torch.Tensor]:
+    """The samples ``idx`` (a numpy index array) of a task dataset, collated: a dict dataset is indexed in sorted order, the items
+    of a map-style one are stacked in the order given."""
+    if isinstance(dataset, dict):
+        sel = torch.as_tensor(np.sort(idx))
+        return {key: dataset[key][sel] for key in keys}
+    items = [dataset[int(i)] for i in idx]
+    return {key: torch.stack([torch.as_tensor(it[key]) for it in items]) for key in keys}
+
+
+def iter_batches(dataset, batch_size: int, keys) -> Iterator[Dict[str, torch.Tensor]]:
+    """The dataset front to back in collated batches of ``batch_size`` (the last one shorter); keys it does not have are left out."""
+    n = dataset_len(dataset)
+    have = [key for key in keys if key in (dataset if isinstance(dataset, dict) else dataset[0])] if n else []
+    for lo in range(0, n, batch_size):
+        yield take_samples(dataset, np.arange(lo, min(n, lo + batch_size)), have)
 
 
 class HBMReplayBuffer:

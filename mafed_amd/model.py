@@ -604,6 +604,33 @@ class VLPythiaForCausalLM(EngineMixin, GenerationMixin, nn.Module):
         return out
 
     @torch.no_grad()
+    def pooled_features(self, input_ids, attention_mask, pixel_values=None, patch_embeddings=None, layer: int = -1,
+                        out: Optional[torch.Tensor] = None, rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``modality_features(...)[:, layer]`` without the other layers: the inference forward stops behind decoder layer ``layer``
+        (0 .. L-1, negative from the end; the last one ends in the final LayerNorm, as hidden_states[L] does), no LM head, then one
+        pooling launch over that one hidden state.  out fp32 [2 (image, text), n, h] (allocated with n = B if None); sample b lands
+        in row rows[b] (default b).  The same launches as ``modality_features`` up to that layer, hence the same bits."""
+        feats = patch_embeddings if patch_embeddings is not None else self.get_patch_embeddings(pixel_values)
+        cfg, dev = self.config, self.flat_params.device
+        L = cfg.num_hidden_layers
+        if not -L <= int(layer) < L:
+            raise IndexError(f"layer {layer} outside [-{L}, {L})")
+        layer = int(layer) % L
+        input_ids = input_ids.to(dev, torch.int64).contiguous()
+        attention_mask = attention_mask.to(dev, torch.int64).contiguous()
+        B = input_ids.shape[0]
+        if out is None:
+            out = torch.empty((2, B, cfg.hidden_size), dtype=torch.float32, device=dev)
+        assert out.dim() == 3 and out.is_contiguous()
+        if rows is not None:
+            rows = rows.to(dev, torch.int64).contiguous()
+        last = layer == L - 1
+        st = self._engine_forward(feats.to(dev).contiguous(), input_ids, attention_mask, None, True, train=False,
+                                  n_hidden=None if last else layer + 2, skip_head=last)
+        ops.cka_pool(st["hidden"][-1:], attention_mask, cfg.num_vision_tokens, out.unsqueeze(1), rows)
+        return out
+
+    @torch.no_grad()
     def head_logits_rows(self, feats, input_ids, attention_mask, rows: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Inference logits of a batch that is already at its padded length (pad_text_batch), for a frozen teacher: the stack, the final
         LayerNorm and the LM head on the text rows ``rows`` only (int32 indices into the [B * T] text rows; a negative one gives a row

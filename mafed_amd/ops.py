@@ -1042,6 +1042,27 @@ def cka_hsic(products: Sequence[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, 
     return out
 
 
+SELECT_HERDING, SELECT_KCENTER = 0, 1
+
+
+def select_greedy(X: torch.Tensor, mean: torch.Tensor, mode: int, k: int, want_scores: bool = False):
+    """k greedy picks over the rows of X fp32 [n, d] (row stride >= d; read in place) with its fp64 column mean [d] (``cka_stats``):
+    herding (``SELECT_HERDING``) or k-center (``SELECT_KCENTER``), the rules of include/mafed_hip.h.
+    -> (picks int64 [k], values fp32 [k], last_scores fp32 [n] or None), all on the device; 2 k + 1 launches, no synchronisation."""
+    assert X.dtype == torch.float32 and X.dim() == 2 and X.stride(1) == 1
+    assert mean.dtype == torch.float64 and mean.shape == (X.shape[1],) and mean.is_contiguous()
+    n, d = X.shape
+    k = int(k)
+    lib = _lib.load()
+    picks = torch.empty(max(k, 0), dtype=torch.int64, device=X.device)
+    values = torch.empty(max(k, 0), dtype=torch.float32, device=X.device)
+    scores = torch.empty(n, dtype=torch.float32, device=X.device) if want_scores else None
+    ws = workspace(X.device).get(lib.mafed_select_workspace_bytes(n, d))
+    check(lib.mafed_select_greedy(_ptr(X), n, d, X.stride(0), _ptr(mean), int(mode), k, _ptr(picks), _ptr(values), _ptr(scores), _ptr(ws),
+                                  ws.numel(), _stream()), "mafed_select_greedy")
+    return picks, values, scores
+
+
 def gradnorm_clip(g: torch.Tensor, max_norm: float, out2: Optional[torch.Tensor] = None) -> torch.Tensor:
     """-> out[2] = {||g||, clip scale}"""
     _flat_f32(g)
