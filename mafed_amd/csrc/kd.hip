@@ -9,27 +9,19 @@
 // every accumulator an online, max-subtracted fp32 one.  Rows without a label (ignore_index, the last position) are not read at all.
 // A thread walks its columns in ascending order and the block combines the partials in one fixed tree: no atomics, no workspace, the
 // same bits on every call.
-#include "common.h"
+#include "head_rows.h"
 
 namespace mafed {
 
 template <typename T, int VEC>
 struct RowVec;
-template <>
-struct RowVec<float, 4> {
-  static __device__ __forceinline__ void load(const float* p, float (&v)[4]) {
-    const float4 r = *reinterpret_cast<const float4*>(p);
-    v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
-  }
-  static __device__ __forceinline__ void store(float* p, const float (&v)[4]) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
-};
-template <>
-struct RowVec<bf16_t, 4> {
-  static __device__ __forceinline__ void load(const bf16_t* p, float (&v)[4]) {
+template <typename T>
+struct RowVec<T, 4> {   // load4 / store4 of common.h
+  static __device__ __forceinline__ void load(const T* p, float (&v)[4]) {
     const float4 r = load4(p);
     v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
   }
-  static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[4]) { store4(p, make_float4(v[0], v[1], v[2], v[3])); }
+  static __device__ __forceinline__ void store(T* p, const float (&v)[4]) { store4(p, make_float4(v[0], v[1], v[2], v[3])); }
 };
 template <>
 struct RowVec<bf16_t, 8> {
@@ -99,10 +91,9 @@ __global__ __launch_bounds__(256) void ce_kd_fwd_kernel(const T* __restrict__ st
                                                         const int64_t* __restrict__ labels, int B, int Tn, int64_t V, float inv_tau,
                                                         float* __restrict__ lse3, float* __restrict__ row_ce, float* __restrict__ row_kd) {
   __shared__ float sm[32];
-  const int64_t r = blockIdx.x, R = (int64_t)B * Tn;
-  const int b = (int)(r / Tn), t = (int)(r - (int64_t)b * Tn);
-  int64_t lab = -100;
-  if (t < Tn - 1) lab = labels[(int64_t)b * Tn + t + 1];   // the last position predicts nothing (vl_pythia.py:91)
+  const HeadRow row(labels, Tn);
+  const int64_t r = row.r, R = (int64_t)B * Tn;
+  const int64_t lab = row.label();
   if (lab == -100) {   // block-uniform
     if (threadIdx.x == 0) { lse3[r] = 0.f; lse3[R + r] = 0.f; lse3[2 * R + r] = 0.f; row_ce[r] = 0.f; row_kd[r] = 0.f; }
     return;
@@ -147,59 +138,20 @@ __global__ __launch_bounds__(256) void ce_kd_fwd_kernel(const T* __restrict__ st
   }
 }
 
-// out3 = { CE + coef KD, CE, KD }, CE / KD = mean_b( sum_t row[b, t] / max(count_b, 1e-13) ) as in ce_finalize_kernel: one wave per
-// sample, fixed-order sums.  `poison` (may be null): a non-zero device flag turns the loss into NaN (mafed_ce_fwd_guarded).
-__global__ __launch_bounds__(256) void ce_kd_finalize_kernel(const float* __restrict__ row_ce, const float* __restrict__ row_kd,
-                                                             const int64_t* __restrict__ labels, int B, int Tn, float coef,
-                                                             float* __restrict__ out3, const int* __restrict__ poison) {
-  __shared__ float sm[8];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float acc_ce = 0.f, acc_kd = 0.f;
-  for (int b = wave; b < B; b += 4) {
-    float s = 0.f, k = 0.f, c = 0.f;
-    for (int t = lane; t < Tn - 1; t += 64) {
-      const int64_t lab = labels[(int64_t)b * Tn + t + 1];
-      if (lab != -100) { c += 1.f; s += row_ce[(int64_t)b * Tn + t]; k += row_kd[(int64_t)b * Tn + t]; }
-    }
-    s = wave_sum(s);
-    k = wave_sum(k);
-    c = wave_sum(c);
-    acc_ce += s / fmaxf(c, 1e-13f);
-    acc_kd += k / fmaxf(c, 1e-13f);
-  }
-  if (lane == 0) { sm[wave] = acc_ce; sm[4 + wave] = acc_kd; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const float ce = ((sm[0] + sm[1]) + (sm[2] + sm[3])) / (float)B;
-    const float kd = ((sm[4] + sm[5]) + (sm[6] + sm[7])) / (float)B;
-    out3[0] = (poison && poison[0] != 0) ? __int_as_float(0x7fc00000) : ce + coef * kd;
-    out3[1] = ce;
-    out3[2] = kd;
-  }
-}
-
 template <typename T, int VEC>
 __global__ __launch_bounds__(256) void ce_kd_bwd_kernel(const T* __restrict__ student, const T* __restrict__ teacher,
                                                         const int64_t* __restrict__ labels, const float* __restrict__ lse3, int B, int Tn,
                                                         int64_t V, float inv_tau, float lam_tau, const float* __restrict__ gloss,
                                                         T* __restrict__ dlogits) {
-  const int64_t r = blockIdx.x, R = (int64_t)B * Tn;
-  const int b = (int)(r / Tn), t = (int)(r - (int64_t)b * Tn);
+  const HeadRow row(labels, Tn);
+  const int64_t r = row.r, R = (int64_t)B * Tn;
   T* dx = dlogits + r * V;
-  int64_t lab = -100;
-  if (t < Tn - 1) lab = labels[(int64_t)b * Tn + t + 1];
-  if (lab == -100) {
-    float z[VEC];
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) z[k] = 0.f;
-    for (int64_t c = (int64_t)threadIdx.x * VEC; c < V; c += 256 * VEC) RowVec<T, VEC>::store(dx + c, z);
-    return;
-  }
+  const int64_t lab = row.label();
+  if (lab == -100) return zero_row<T, VEC>(dx, V);
   const T* xs = student + r * V;
   const T* xt = teacher + r * V;
-  float cnt = 0.f;
-  for (int tt = 1; tt < Tn; ++tt) cnt += (labels[(int64_t)b * Tn + tt] != -100) ? 1.f : 0.f;
-  const float g = gloss[0] / ((float)B * fmaxf(cnt, 1e-13f));
+  const float den = row.denominator(B);
+  const float g = gloss[0] / den;
   const float gk = g * lam_tau;
   const float l1 = lse3[r], l2 = lse3[R + r], l3 = lse3[2 * R + r];
   for (int64_t c = (int64_t)threadIdx.x * VEC; c < V; c += 256 * VEC) {
@@ -221,11 +173,11 @@ __global__ __launch_bounds__(256) void ce_kd_bwd_kernel(const T* __restrict__ st
 
 using namespace mafed;
 
-static bool kd_args_ok(const void* student, const void* teacher, int B, int T, int64_t V, float tau, float lambda, const char* who) {
-  if (!(B > 0 && T > 0 && V > 0 && V % 4 == 0)) { set_error("%s: bad shape (V must be a multiple of 4)", who); return false; }
-  if (!(tau > 0.f) || !(tau < INFINITY) || !(lambda == lambda) || fabsf(lambda) == INFINITY) { set_error("%s: tau must be positive and finite, lambda finite", who); return false; }
-  if ((((uintptr_t)student) | ((uintptr_t)teacher)) & 7) { set_error("%s: logits must be 8-byte aligned", who); return false; }
-  return true;
+static int kd_args_check(const void* student, const void* teacher, int B, int T, int64_t V, float tau, float lambda, const char* who) {
+  MAFED_HEAD_CHECK_SHAPE(B, T, V, who);
+  MAFED_CHECK_ARG(tau > 0.f && tau < INFINITY && lambda == lambda && fabsf(lambda) != INFINITY, "%s: tau must be positive and finite, lambda finite", who);
+  MAFED_CHECK_ARG(((((uintptr_t)student) | ((uintptr_t)teacher)) & 7) == 0, "%s: logits must be 8-byte aligned", who);
+  return MAFED_OK;
 }
 
 // 8 bf16 elements per load when every row of both matrices (and of the gradient) starts on a 16-byte boundary
@@ -233,47 +185,40 @@ static bool kd_wide(mafed_dtype dtype, int64_t V, const void* a, const void* b, 
   return dtype == MAFED_BF16 && V % 8 == 0 && ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) == 0;
 }
 
+// out3 = { CE + lambda tau^2 KD, CE, KD } (head_finalize_kernel)
 extern "C" int mafed_ce_kd_fwd(const void* student, const void* teacher, mafed_dtype dtype, const int64_t* labels, int B, int T, int64_t V,
                                float tau, float lambda, float* lse3, float* row_ce, float* row_kd, float* out3, const int* poison_flag,
                                void* stream) {
-  MAFED_CHECK_ARG(student && teacher && labels && lse3 && row_ce && row_kd && out3, "ce_kd_fwd: null pointer");
+  MAFED_HEAD_CHECK_PTRS(student && teacher && labels && lse3 && row_ce && row_kd && out3, "ce_kd_fwd");
   MAFED_CHECK_ARG(dtype == MAFED_F32 || dtype == MAFED_BF16, "ce_kd_fwd: dtype must be F32 or BF16");
-  if (!kd_args_ok(student, teacher, B, T, V, tau, lambda, "ce_kd_fwd")) return MAFED_EINVAL;
+  if (kd_args_check(student, teacher, B, T, V, tau, lambda, "ce_kd_fwd") != MAFED_OK) return MAFED_EINVAL;
   MAFED_CHECK_ARG(dtype == MAFED_BF16 || (((uintptr_t)student | (uintptr_t)teacher) & 15) == 0, "ce_kd_fwd: fp32 logits must be 16-byte aligned");
-  hipStream_t st = as_stream(stream);
-  dim3 grid((unsigned)((int64_t)B * T)), block(256);
+  const HeadPass pass(dtype, B, T, V, stream);
+  const bool wide = kd_wide(dtype, V, student, teacher, nullptr);
   const float inv_tau = 1.0f / tau;
-  const double bytes = 2.0 * B * T * V * (dtype == MAFED_F32 ? 4.0 : 2.0);  // student and teacher logits, each read once
-  if (dtype == MAFED_F32)
-    launch(K_CE_KD_FWD, bytes, ce_kd_fwd_kernel<float, 4>, grid, block, 0, st, (const float*)student, (const float*)teacher, labels, B, T, V, inv_tau, lse3, row_ce, row_kd);
-  else if (kd_wide(dtype, V, student, teacher, nullptr))
-    launch(K_CE_KD_FWD, bytes, ce_kd_fwd_kernel<bf16_t, 8>, grid, block, 0, st, (const bf16_t*)student, (const bf16_t*)teacher, labels, B, T, V, inv_tau, lse3, row_ce, row_kd);
-  else
-    launch(K_CE_KD_FWD, bytes, ce_kd_fwd_kernel<bf16_t, 4>, grid, block, 0, st, (const bf16_t*)student, (const bf16_t*)teacher, labels, B, T, V, inv_tau, lse3, row_ce, row_kd);
+  // student and teacher logits, each read once
+  pass.rows(K_CE_KD_FWD, 2.0, [wide](auto e) { using E = decltype(e); return wide ? ce_kd_fwd_kernel<E, 16 / sizeof(E)> : ce_kd_fwd_kernel<E, 4>; },
+            student, teacher, labels, B, T, V, inv_tau, lse3, row_ce, row_kd);
   MAFED_CHECK_LAUNCH("ce_kd_fwd");
-  launch(K_SMALL, 0.0, ce_kd_finalize_kernel, dim3(1), block, 0, st, row_ce, row_kd, labels, B, T, lambda * tau * tau, out3, poison_flag);
+  pass.finalize<2>(row_ce, row_kd, labels, B, T, lambda * tau * tau, out3, poison_flag);
   MAFED_CHECK_LAUNCH("ce_kd_fwd(finalize)");
   return MAFED_OK;
 }
 
 extern "C" int mafed_ce_kd_bwd(const void* student, const void* teacher, mafed_dtype dtype, const int64_t* labels, const float* lse3, int B,
                                int T, int64_t V, float tau, float lambda, const float* gloss_dev, void* dlogits, void* stream) {
-  MAFED_CHECK_ARG(student && teacher && labels && lse3 && gloss_dev && dlogits, "ce_kd_bwd: null pointer");
+  MAFED_HEAD_CHECK_PTRS(student && teacher && labels && lse3 && gloss_dev && dlogits, "ce_kd_bwd");
   MAFED_CHECK_ARG(dtype == MAFED_F32 || dtype == MAFED_BF16, "ce_kd_bwd: dtype must be F32 or BF16");
-  if (!kd_args_ok(student, teacher, B, T, V, tau, lambda, "ce_kd_bwd")) return MAFED_EINVAL;
+  if (kd_args_check(student, teacher, B, T, V, tau, lambda, "ce_kd_bwd") != MAFED_OK) return MAFED_EINVAL;
   MAFED_CHECK_ARG((((uintptr_t)dlogits) & 7) == 0, "ce_kd_bwd: dlogits must be 8-byte aligned");
   MAFED_CHECK_ARG(dtype == MAFED_BF16 || (((uintptr_t)student | (uintptr_t)teacher | (uintptr_t)dlogits) & 15) == 0,
                   "ce_kd_bwd: fp32 tensors must be 16-byte aligned");
-  hipStream_t st = as_stream(stream);
-  dim3 grid((unsigned)((int64_t)B * T)), block(256);
+  const bool wide = kd_wide(dtype, V, student, teacher, dlogits);
   const float inv_tau = 1.0f / tau, lam_tau = lambda * tau;
-  const double bytes = 3.0 * B * T * V * (dtype == MAFED_F32 ? 4.0 : 2.0);  // student and teacher logits in, gradient out
-  if (dtype == MAFED_F32)
-    launch(K_CE_KD_BWD, bytes, ce_kd_bwd_kernel<float, 4>, grid, block, 0, st, (const float*)student, (const float*)teacher, labels, lse3, B, T, V, inv_tau, lam_tau, gloss_dev, (float*)dlogits);
-  else if (kd_wide(dtype, V, student, teacher, dlogits))
-    launch(K_CE_KD_BWD, bytes, ce_kd_bwd_kernel<bf16_t, 8>, grid, block, 0, st, (const bf16_t*)student, (const bf16_t*)teacher, labels, lse3, B, T, V, inv_tau, lam_tau, gloss_dev, (bf16_t*)dlogits);
-  else
-    launch(K_CE_KD_BWD, bytes, ce_kd_bwd_kernel<bf16_t, 4>, grid, block, 0, st, (const bf16_t*)student, (const bf16_t*)teacher, labels, lse3, B, T, V, inv_tau, lam_tau, gloss_dev, (bf16_t*)dlogits);
+  // student and teacher logits in, gradient out
+  HeadPass(dtype, B, T, V, stream)
+      .rows(K_CE_KD_BWD, 3.0, [wide](auto e) { using E = decltype(e); return wide ? ce_kd_bwd_kernel<E, 16 / sizeof(E)> : ce_kd_bwd_kernel<E, 4>; },
+            student, teacher, labels, lse3, B, T, V, inv_tau, lam_tau, gloss_dev, dlogits);
   MAFED_CHECK_LAUNCH("ce_kd_bwd");
   return MAFED_OK;
 }

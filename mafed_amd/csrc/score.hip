@@ -1,9 +1,9 @@
 // Log-probability of GIVEN tokens (model.score; DESIGN.md section 4c''''): out[r] = logits[row(r), target[r]] - logsumexp(logits[row(r), :]),
 // the per-token term of the reference's shifted cross-entropy (mafed/model/vl_pythia.py:64-96) with the sign turned, and the per-candidate
-// sum / mean of those terms.  HBM-bound like ce.hip, whose row reduction this is: one 256-thread block per output row, 4-element vector
-// loads, online log-sum-exp in fp32.  Each thread walks its columns in ascending order and the block combines the 256 partial results
-// in one fixed tree, so a row's result is the same bits on every call and does not depend on R or on the other rows.
-#include "common.h"
+// sum / mean of those terms.  HBM-bound like ce.hip, whose row reduction this is (head_rows.h: row_lse4): one 256-thread block per
+// output row, 4-element vector loads, online log-sum-exp in fp32.  Each thread walks its columns in ascending order and the block combines
+// the 256 partial results in one fixed tree, so a row's result is the same bits on every call and does not depend on R or on the other rows.
+#include "head_rows.h"
 
 namespace mafed {
 
@@ -19,25 +19,19 @@ __global__ __launch_bounds__(256) void token_logprob_kernel(const T* __restrict_
     return;
   }
   const T* x = logits + (logits_row ? (int64_t)logits_row[r] : r) * ldl;
-  float m = -INFINITY, s = 0.f;
+  RowLse l;
   if (VEC) {
-    for (int64_t c = (int64_t)threadIdx.x * 4; c < V; c += 256 * 4) {
-      const float4 v = load4(x + c);
-      const float mx = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
-      if (mx > m) { s *= expf(m - mx); m = mx; }
-      s += (expf(v.x - m) + expf(v.y - m)) + (expf(v.z - m) + expf(v.w - m));
-    }
+    l = row_lse4(x, V, sm);
   } else {
+    float m = -INFINITY, s = 0.f;
     for (int64_t c = threadIdx.x; c < V; c += 256) {
       const float v = Elem<T>::load(x + c);
       if (v > m) { s *= expf(m - v); m = v; }
       s += expf(v - m);
     }
+    l = block_lse(m, s, sm);
   }
-  const float gm = block_max<256>(m, sm);
-  s = (m == -INFINITY) ? 0.f : s * expf(m - gm);
-  const float gs = block_sum<256>(s, sm);
-  if (threadIdx.x == 0) out[r] = Elem<T>::load(x + tgt) - (gm + logf(gs));
+  if (threadIdx.x == 0) out[r] = Elem<T>::load(x + tgt) - l.value();
 }
 
 // score[r] = sum_j mask[r, j] * tlp[r, j] in ascending j (mean: divided by the count); no token -> -inf.  One thread per candidate.

@@ -10,8 +10,10 @@ and tests index:
   hidden               [hidden_states[0] .. ] fp32 [B, S, h] views of the residual stream; [L] (post final LayerNorm) only when asked for
   logits, loss         [B, T, V] ([B, 1, V] ``last_only``, [n, V] ``head_rows``, [B, Rc, V] row-sparse) / loss [1]; None when not computed
   layers               per layer, training: {x, mean, rstd, ln1, ln2, qkv, ao, lse, u, a}; ``keep_qkv``: {qkv}; else empty
-  training only        proj = (fc, u0, a0) of the projector; final = (xt, lnf, fmean, frstd) of the final LayerNorm; x_last; ce_lse;
-                       sparse_head = (slot of every text row, compact labels); kd = (teacher logits, lse3, tau, lambda) under a logit teacher
+  training only        proj = (fc, u0, a0) of the projector; final = (xt, lnf, fmean, frstd) of the final LayerNorm; x_last;
+                       sparse_head = (slot of every text row, compact labels); head_loss = the backward of the loss ``_head_text`` chose:
+                       (logits, head labels, dloss [1]) -> dlogits, holding what it needs (CE: the lse; under a logit teacher: teacher
+                       logits, lse3, tau, lambda; squared norm: nothing); the backward sweep pops it
   inject, inject_cosine   written by the fused distillation node before the backward: {layer: (teacher hidden state, device [4] scales)}
 """
 from __future__ import annotations
@@ -206,13 +208,8 @@ class BackwardSweep:
         sp = sv.get("sparse_head")   # (slot of every text row, compact labels): the head ran on the labelled rows only
         n_head = logits.shape[0] * logits.shape[1]
         head_labels = sp[1] if sp is not None else sv["labels"]
-        kd = sv.pop("kd", None)   # (teacher logits, lse3, tau, lambda): the head loss was CE + lambda tau^2 KL (_head_kd_loss)
-        if sv.get("sqnorm"):   # the head loss was the squared norm of the labelled rows (_head_text)
-            dlog = ops.sqnorm_bwd(logits, head_labels, gl).view(n_head, V)
-        elif kd is not None:
-            dlog = ops.ce_kd_bwd(logits, kd[0], head_labels, kd[1], kd[2], kd[3], gl).view(n_head, V)
-        else:
-            dlog = ops.ce_bwd(logits, head_labels, sv["ce_lse"], gl).view(n_head, V)
+        # the backward of whichever loss _head_text chose; popped, so that what it holds (a teacher's logits) goes with this call
+        dlog = sv.pop("head_loss")(logits, head_labels, gl).view(n_head, V)
         self.wgrad(dlog, lnf, Go.embed_out)
         if cd == torch.bfloat16:
             # [rows, V] . [V, h]: few output tiles with K = 50304 -- accumulate-only fp32 output so that the GEMM splits K
@@ -499,30 +496,31 @@ class EngineMixin:
             lnf = ops.gather_rows(lnf, ros)
         logits = sv["logits"] = ops.gemm(lnf, self._tensors(0).outer.embed_out, False, True).view(B, Rc or T, self.config.vocab_size)
         # the loss, chosen here and nowhere else: the squared norm of the labelled rows' logits under ``head_objective = "sqnorm"``,
-        # CE + lambda tau^2 KL under a logit teacher, else CE
+        # CE + lambda tau^2 KL under a logit teacher, else CE.  Each leaves its own backward in sv["head_loss"] for BackwardSweep.head,
+        # which calls ops.<name> when it runs (not bound here)
         if sqnorm:
             sv["loss"], _ = ops.sqnorm_fwd(logits, labels, poison=ov)
-            sv["sqnorm"] = True
+            sv["head_loss"] = lambda lg, lab, gl: ops.sqnorm_bwd(lg, lab, gl)
         elif teacher is not None:
             self._head_kd_loss(sv, logits, labels, teacher, ov)
         elif labels is not None:
             sv["loss"], lse_ce = ops.ce_fwd(logits, labels, poison=ov)
             if train:
-                sv["ce_lse"] = lse_ce
+                sv["head_loss"] = lambda lg, lab, gl: ops.ce_bwd(lg, lab, lse_ce, gl)
         if train:
             sv["final"] = (xt, lnf, fmean, frstd)
             sv["x_last"] = x
 
     def _head_kd_loss(self, sv, logits, labels, teacher, poison) -> None:
         """Training head loss with a logit teacher: CE + lambda tau^2 KL against the teacher's logits of the same rows, one pass
-        (ops.ce_kd_fwd) -> sv["loss"], sv["kd"], ``last_head_losses``."""
+        (ops.ce_kd_fwd) -> sv["loss"], sv["head_loss"], ``last_head_losses``."""
         t_logits, tau, lam = teacher
         if t_logits.dtype != logits.dtype or t_logits.numel() != logits.numel():
             raise ValueError(f"logit_teacher returned {tuple(t_logits.shape)} {t_logits.dtype} for head rows {tuple(logits.shape)} {logits.dtype}")
         t_logits = t_logits.contiguous().view(logits.shape)
         out3, lse3 = ops.ce_kd_fwd(logits, t_logits, labels, tau, lam, poison=poison)
         sv["loss"] = out3[0:1]
-        sv["kd"] = (t_logits, lse3, tau, lam)
+        sv["head_loss"] = lambda lg, lab, gl: ops.ce_kd_bwd(lg, t_logits, lab, lse3, tau, lam, gl)
         self.last_head_losses = out3
 
     def _dw_group_fuses_squares(self, rows: int) -> bool:

@@ -9,7 +9,7 @@ reference's per-layer ``wandb.log(.item())``, distillation.py:165, becomes ``sel
 from __future__ import annotations
 
 from copy import deepcopy
-from typing import List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch

@@ -617,19 +617,25 @@ def embed_concat_bwd(dh0, input_ids, B, P, T, h, V, d_embed_in: Optional[torch.T
     return d_image
 
 
+def _head_args(logits: torch.Tensor, labels: torch.Tensor, poison: Optional[torch.Tensor] = None):
+    """What the head-loss wrappers share: ``logits`` [B,T,V] and int64 ``labels`` [B,T], both contiguous, and the optional ``poison`` flag
+    (int32 [1], device).  -> (B, T, V, rows), ``rows(*lead)`` a new fp32 [*lead, B, T] buffer on the logits' device."""
+    B, T, V = logits.shape
+    assert logits.is_contiguous() and labels.is_contiguous() and labels.dtype == torch.int64 and labels.shape == (B, T)
+    assert poison is None or (poison.dtype == torch.int32 and poison.numel() == 1)
+    return B, T, V, lambda *lead: torch.empty(lead + (B, T), dtype=torch.float32, device=logits.device)
+
+
 def ce_fwd(logits: torch.Tensor, labels: torch.Tensor, poison: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """logits [B,T,V] (text positions), labels [B,T] -> (loss[1], lse[B,T]).  ``poison`` (int32 [1], device): a non-zero flag turns the
     loss into NaN (mafed_ce_fwd_guarded: the row-sparse head's overflow flag)."""
-    B, T, V = logits.shape
-    assert logits.is_contiguous() and labels.is_contiguous() and labels.dtype == torch.int64
-    lse = torch.empty((B, T), dtype=torch.float32, device=logits.device)
-    row_loss = torch.empty((B, T), dtype=torch.float32, device=logits.device)
+    B, T, V, rows = _head_args(logits, labels, poison)
+    lse, row_loss = rows(), rows()
     loss = torch.empty(1, dtype=torch.float32, device=logits.device)
     if poison is None:
         check(_lib.load().mafed_ce_fwd(_ptr(logits), _dt(logits), _ptr(labels), B, T, V, _ptr(lse), _ptr(row_loss), _ptr(loss), _stream()),
               "mafed_ce_fwd")
     else:
-        assert poison.dtype == torch.int32 and poison.numel() == 1
         check(_lib.load().mafed_ce_fwd_guarded(_ptr(logits), _dt(logits), _ptr(labels), B, T, V, _ptr(lse), _ptr(row_loss), _ptr(loss),
                                                _ptr(poison), _stream()), "mafed_ce_fwd_guarded")
     return loss, lse
@@ -638,7 +644,7 @@ def ce_fwd(logits: torch.Tensor, labels: torch.Tensor, poison: Optional[torch.Te
 def ce_bwd(logits: torch.Tensor, labels: torch.Tensor, lse: torch.Tensor, gloss: torch.Tensor,
            out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dL/dlogits (pass out=logits for the in-place form)."""
-    B, T, V = logits.shape
+    B, T, V, _ = _head_args(logits, labels)
     if out is None:
         out = torch.empty_like(logits)
     check(_lib.load().mafed_ce_bwd(_ptr(logits), _dt(logits), _ptr(labels), _ptr(lse), B, T, V, _ptr(gloss), _ptr(out), _stream()),
@@ -649,10 +655,8 @@ def ce_bwd(logits: torch.Tensor, labels: torch.Tensor, lse: torch.Tensor, gloss:
 def sqnorm_fwd(logits: torch.Tensor, labels: torch.Tensor, poison: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Squared-norm head objective (mafed_sqnorm_fwd): logits [B,T,V], labels [B,T] -> (J[1], rowsq[B,T]); the rows and the normaliser
     of :func:`ce_fwd`, the label values unused.  ``poison`` as in :func:`ce_fwd`."""
-    B, T, V = logits.shape
-    assert logits.is_contiguous() and labels.is_contiguous() and labels.dtype == torch.int64 and labels.shape == (B, T)
-    assert poison is None or (poison.dtype == torch.int32 and poison.numel() == 1)
-    rowsq = torch.empty((B, T), dtype=torch.float32, device=logits.device)
+    B, T, V, rows = _head_args(logits, labels, poison)
+    rowsq = rows()
     out = torch.empty(1, dtype=torch.float32, device=logits.device)
     check(_lib.load().mafed_sqnorm_fwd(_ptr(logits), _dt(logits), _ptr(labels), B, T, V, _ptr(rowsq), _ptr(out), _ptr(poison), _stream()),
           "mafed_sqnorm_fwd")
@@ -661,8 +665,7 @@ def sqnorm_fwd(logits: torch.Tensor, labels: torch.Tensor, poison: Optional[torc
 
 def sqnorm_bwd(logits: torch.Tensor, labels: torch.Tensor, dloss: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dJ/dlogits in the logits' dtype, exact zeros on unlabelled rows (``out``: a buffer of its own)."""
-    B, T, V = logits.shape
-    assert logits.is_contiguous() and labels.is_contiguous() and labels.dtype == torch.int64 and labels.shape == (B, T)
+    B, T, V, _ = _head_args(logits, labels)
     assert dloss.dtype == torch.float32 and dloss.numel() == 1
     if out is None:
         out = torch.empty_like(logits)
@@ -671,35 +674,30 @@ def sqnorm_bwd(logits: torch.Tensor, labels: torch.Tensor, dloss: torch.Tensor, 
     return out
 
 
-def _kd_check(student: torch.Tensor, teacher: torch.Tensor, labels: torch.Tensor) -> Tuple[int, int, int]:
-    B, T, V = student.shape
+def _kd_args(student: torch.Tensor, teacher: torch.Tensor, labels: torch.Tensor, poison: Optional[torch.Tensor] = None):
+    """:func:`_head_args` of the student's logits, with a teacher of the same shape and dtype"""
     if teacher.shape != student.shape or teacher.dtype != student.dtype:
         raise ValueError(f"teacher logits {tuple(teacher.shape)} {teacher.dtype} do not match the student's {tuple(student.shape)} {student.dtype}")
-    assert student.is_contiguous() and teacher.is_contiguous() and labels.is_contiguous() and labels.dtype == torch.int64
-    assert labels.shape == (B, T)
-    return B, T, V
+    assert teacher.is_contiguous()
+    return _head_args(student, labels, poison)
 
 
 def ce_kd_fwd(student: torch.Tensor, teacher: torch.Tensor, labels: torch.Tensor, tau: float, lam: float,
               poison: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """LwF head loss (mafed_ce_kd_fwd): student / teacher logits [B,T,V] of the same rows, labels [B,T] ->
     (out3 = [CE + lam tau^2 KD, CE, KD], lse3 [3,B,T] = lse(s), lse(s / tau), lse(t / tau)).  ``poison`` as in :func:`ce_fwd`."""
-    B, T, V = _kd_check(student, teacher, labels)
-    dev = student.device
-    lse3 = torch.empty((3, B, T), dtype=torch.float32, device=dev)
-    rows = torch.empty((2, B, T), dtype=torch.float32, device=dev)
-    out3 = torch.empty(3, dtype=torch.float32, device=dev)
-    if poison is not None:
-        assert poison.dtype == torch.int32 and poison.numel() == 1
+    B, T, V, rows = _kd_args(student, teacher, labels, poison)
+    lse3, row = rows(3), rows(2)
+    out3 = torch.empty(3, dtype=torch.float32, device=student.device)
     check(_lib.load().mafed_ce_kd_fwd(_ptr(student), _ptr(teacher), _dt(student), _ptr(labels), B, T, V, float(tau), float(lam), _ptr(lse3),
-                                      _ptr(rows[0]), _ptr(rows[1]), _ptr(out3), _ptr(poison), _stream()), "mafed_ce_kd_fwd")
+                                      _ptr(row[0]), _ptr(row[1]), _ptr(out3), _ptr(poison), _stream()), "mafed_ce_kd_fwd")
     return out3, lse3
 
 
 def ce_kd_bwd(student: torch.Tensor, teacher: torch.Tensor, labels: torch.Tensor, lse3: torch.Tensor, tau: float, lam: float,
               gloss: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dL/d(student logits) of :func:`ce_kd_fwd`: the cross-entropy and the distillation gradient, one pass (``out``: a buffer of its own)."""
-    B, T, V = _kd_check(student, teacher, labels)
+    B, T, V, _ = _kd_args(student, teacher, labels)
     assert lse3.shape == (3, B, T) and lse3.dtype == torch.float32 and lse3.is_contiguous()
     if out is None:
         out = torch.empty_like(student)
