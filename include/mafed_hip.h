@@ -531,6 +531,33 @@ int mafed_ce_kd_fwd(const void* student, const void* teacher, mafed_dtype dtype,
 int mafed_ce_kd_bwd(const void* student, const void* teacher, mafed_dtype dtype, const int64_t* labels, const float* lse3, int B, int T,
                     int64_t V, float tau, float lambda, const float* gloss_dev, void* dlogits, void* stream);
 
+/* ---- DER++ head loss: the cross-entropy above + the squared distance to stored answer logits, one pass per direction ----
+ * No reference call site: the reference names the method (the `_der_` checkpoint suffix, mafed/utils/eval_utils.py:23) and ships none.
+ * student: logits [B,T,V] in `dtype` (F32 or BF16); labels as above.  store: [n_mem, A, V] of `dtype`, contiguous: the logits a model
+ * gave on the answer rows of the n_mem replay samples when they were stored.  mem_index int64 [B]: the stored sample of batch row b.
+ * A labelled row (b,t) (shifted label != -100, never the last position) is paired with z = store[mem_index[b], j, :], j = the number
+ * of labelled rows of sample b in front of t (its rank).  Per labelled row:
+ *   CE  = lse(s) - s[lab]
+ *   MSE = (1 / V) sum_c (s[c] - z[c])^2           (fp32; the difference first, so s == z gives exactly 0)
+ * each summed per sample / max(count_b, 1e-13) and averaged over B like mafed_ce_fwd; out3 fp32 [3] = { beta CE + alpha MSE, CE, MSE }.
+ * lse fp32 [B*T] saved for the backward (0 on unlabelled rows, which are not read); row_ce, row_mse: fp32 [B*T] scratch.
+ * poison_flag (may be NULL): a non-zero device flag turns out3[0] into NaN (mafed_ce_fwd_guarded).
+ * A labelled row with mem_index[b] outside [0, n_mem) or j >= A has no stored row: nothing of the store is read for it and its MSE
+ * (and with it out3[0] and out3[2]) is NaN -- the step fails loudly, without a host synchronisation.
+ * The log-sum-exp is mafed_ce_fwd's own: with store row == student row and beta == 1, out3[0] == out3[1], lse and the gradient are
+ * mafed_ce_fwd's / mafed_ce_bwd's bit for bit on the labelled rows; alpha == 0 likewise.
+ * V % 4 == 0, n_mem > 0, A > 0, alpha and beta finite; fp32 tensors 16-byte, bf16 tensors 8-byte aligned.  No atomics, no workspace:
+ * the same bits on every call. */
+int mafed_ce_mse_fwd(const void* student, const void* store, mafed_dtype dtype, const int64_t* labels, const int64_t* mem_index, int B,
+                     int T, int64_t V, int64_t n_mem, int A, float alpha, float beta, float* lse, float* row_ce, float* row_mse,
+                     float* out3, const int* poison_flag, void* stream);
+/* dlogits[b,t,:] = g_b (beta (softmax(s) - onehot(lab)) + alpha (2 / V) (s - z)), g_b = gloss / (B * count_b), for labelled rows; 0
+ * otherwise (incl. t = T-1); NaN on a labelled row without a stored row.  gloss_dev: device scalar (upstream dL/dloss).  dlogits:
+ * `dtype` [B,T,V], a buffer of its own. */
+int mafed_ce_mse_bwd(const void* student, const void* store, mafed_dtype dtype, const int64_t* labels, const int64_t* mem_index,
+                     const float* lse, int B, int T, int64_t V, int64_t n_mem, int A, float alpha, float beta, const float* gloss_dev,
+                     void* dlogits, void* stream);
+
 /* ---- MAFED per-modality masked distillation (mafed/methods/distillation.py:124-166, 226-257) -----------------
  * s, t: fp32 [B,S,h] student / frozen-teacher hidden state of one layer; attention_mask int64 [B,T]; P image tokens.
  * One pass serves both masks: out[4] = { sum_lang d, sum_vision d, n_lang, n_vision } with

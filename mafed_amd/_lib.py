@@ -104,6 +104,8 @@ SIGNATURES = {
     "mafed_sqnorm_bwd": (_i, [_p, _i, _p, _i, _i, _l, _p, _p, _p]),
     "mafed_ce_kd_fwd": (_i, [_p, _p, _i, _p, _i, _i, _l, _f, _f, _p, _p, _p, _p, _p, _p]),
     "mafed_ce_kd_bwd": (_i, [_p, _p, _i, _p, _p, _i, _i, _l, _f, _f, _p, _p, _p]),
+    "mafed_ce_mse_fwd": (_i, [_p, _p, _i, _p, _p, _i, _i, _l, _l, _i, _f, _f, _p, _p, _p, _p, _p, _p]),
+    "mafed_ce_mse_bwd": (_i, [_p, _p, _i, _p, _p, _p, _i, _i, _l, _l, _i, _f, _f, _p, _p, _p]),
     "mafed_distill_workspace_bytes": (_z, [_l]),
     "mafed_distill_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _z, _p]),
     "mafed_distill_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _i, _p]),

@@ -1,4 +1,5 @@
-// The one copy of what the fused head losses share (CE: ce.hip; CE + KL: kd.hip; squared norm: sqnorm.hip; token log-probability: score.hip).
+// The one copy of what the fused head losses share (CE: ce.hip; CE + KL: kd.hip; CE + MSE against stored logits: der.hip; squared norm:
+// sqnorm.hip; token log-probability: score.hip).
 // All are one-256-thread-block-per-row passes over a [B * Tn, V] logits matrix: the row -> (b, t) map with its shifted label, the
 // per-sample normaliser, the zero store of an unlabelled row's gradient, the float4 online log-sum-exp of a row, the one-block finalize
 // kernel and the entry points' refusals and launch dispatch.  A kernel's body shows its arithmetic and nothing else; a new head loss is
@@ -28,6 +29,13 @@ struct HeadRow {
     float cnt = 0.f;
     for (int tt = 1; tt < Tn; ++tt) cnt += (labels[r0 + tt] != -100) ? 1.f : 0.f;
     return (float)B * fmaxf(cnt, 1e-13f);
+  }
+  // the rank of this row among its sample's labelled rows (0 for the first one): the labelled rows in front of it.  The same number on
+  // the dense head and on the row-sparse head's compact labels, which list a sample's labelled rows in ascending t (der.hip).
+  __device__ __forceinline__ int rank() const {
+    int j = 0;
+    for (int tt = 1; tt <= t; ++tt) j += (labels[r0 + tt] != -100) ? 1 : 0;
+    return j;
   }
 };
 
@@ -68,13 +76,22 @@ __device__ __forceinline__ RowLse row_lse4(const T* x, int64_t V, float* sm) {
   return block_lse(m, s, sm);
 }
 
+// One trip of row_lse4's loop, for a kernel that walks a second matrix beside x in the same loop (der.hip): the statements above, word
+// for word, so that (m, s) -- and block_lse of them -- are row_lse4's bits.  row_lse4 keeps its own loop: routed through this function
+// the compiler schedules the cross-entropy forward differently.
+__device__ __forceinline__ void lse4_step(float& m, float& s, const float4 v) {
+  const float mx = fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w));
+  if (mx > m) { s *= expf(m - mx); m = mx; }
+  s += (expf(v.x - m) + expf(v.y - m)) + (expf(v.z - m) + expf(v.w - m));
+}
+
 // mean_b( sum_t rows[k][b, t] / max(count_b, 1e-13) ) over the labelled rows, for the N row arrays of a forward, each summed on its
 // own: one wave per sample, lanes over t, the four waves folded in fixed order; a single block.  N = 1 (CE, squared norm): out[0].
-// N = 2 (CE + KL): out[0 .. 3) = {ce + coef kd, ce, kd}.  `poison` (may be null): a device flag; non-zero turns out[0], and only it,
-// into NaN (mafed_ce_fwd_guarded: the row-sparse head's overflow flag).
+// N = 2: out[0 .. 3) = {w0 v0 + coef v1, v0, v1} (CE + KL: w0 = 1, which leaves v0's bits alone; CE + MSE: beta, alpha).  `poison` (may
+// be null): a device flag; non-zero turns out[0], and only it, into NaN (mafed_ce_fwd_guarded: the row-sparse head's overflow flag).
 template <int N>
 __global__ __launch_bounds__(256) void head_finalize_kernel(const float* __restrict__ rows0, const float* __restrict__ rows1,
-                                                            const int64_t* __restrict__ labels, int B, int Tn, float coef,
+                                                            const int64_t* __restrict__ labels, int B, int Tn, float w0, float coef,
                                                             float* __restrict__ out, const int* __restrict__ poison) {
   static_assert(N == 1 || N == 2, "one or two row arrays");
   __shared__ float sm[4 * N];
@@ -100,7 +117,7 @@ __global__ __launch_bounds__(256) void head_finalize_kernel(const float* __restr
     for (int k = 0; k < N; ++k) v[k] = ((sm[4 * k] + sm[4 * k + 1]) + (sm[4 * k + 2] + sm[4 * k + 3])) / (float)B;
     float first = v[0];
     if constexpr (N == 2) {
-      first = v[0] + coef * v[1];
+      first = fmaf(coef, v[1], __fmul_rn(w0, v[0]));   // (w0 == 1: the one fma that v0 + coef v1 has always compiled to)
       out[1] = v[0];
       out[2] = v[1];
     }
@@ -135,8 +152,9 @@ struct HeadPass {
 
   // the finalize kernel behind a forward (tag K_SMALL, no bytes worth counting)
   template <int N>
-  void finalize(const float* rows0, const float* rows1, const int64_t* labels, int B, int T, float coef, float* out, const int* poison) const {
-    launch(K_SMALL, 0.0, head_finalize_kernel<N>, dim3(1), block, 0, st, rows0, rows1, labels, B, T, coef, out, poison);
+  void finalize(const float* rows0, const float* rows1, const int64_t* labels, int B, int T, float coef, float* out, const int* poison,
+                float w0 = 1.0f) const {
+    launch(K_SMALL, 0.0, head_finalize_kernel<N>, dim3(1), block, 0, st, rows0, rows1, labels, B, T, w0, coef, out, poison);
   }
 };
 

@@ -487,6 +487,9 @@ class EngineMixin:
             raise ValueError(f"head_objective must be 'ce' or 'sqnorm', got {self.head_objective!r}")
         sqnorm = self.head_objective == "sqnorm" and train and sv["labels"] is not None   # the MAS importance pass
         teacher = None
+        anchor = self.logit_anchor if (train and sv["labels"] is not None and not sqnorm) else None
+        if anchor is not None and self.logit_teacher is not None:
+            raise ValueError("logit_teacher and logit_anchor are both set: one head loss per step (CE + KL or CE + MSE), not both")
         if train and sv["labels"] is not None and self.logit_teacher is not None and not sqnorm:
             # the teacher's logits on the padded batch of this forward and the head's row selection (the row-sparse head's ``row_of_slot``,
             # None = all text rows): on the caller's stream, in front of the student's head
@@ -496,13 +499,15 @@ class EngineMixin:
             lnf = ops.gather_rows(lnf, ros)
         logits = sv["logits"] = ops.gemm(lnf, self._tensors(0).outer.embed_out, False, True).view(B, Rc or T, self.config.vocab_size)
         # the loss, chosen here and nowhere else: the squared norm of the labelled rows' logits under ``head_objective = "sqnorm"``,
-        # CE + lambda tau^2 KL under a logit teacher, else CE.  Each leaves its own backward in sv["head_loss"] for BackwardSweep.head,
-        # which calls ops.<name> when it runs (not bound here)
+        # CE + lambda tau^2 KL under a logit teacher, beta CE + alpha MSE under a logit anchor, else CE.  Each leaves its own backward in
+        # sv["head_loss"] for BackwardSweep.head, which calls ops.<name> when it runs (not bound here)
         if sqnorm:
             sv["loss"], _ = ops.sqnorm_fwd(logits, labels, poison=ov)
             sv["head_loss"] = lambda lg, lab, gl: ops.sqnorm_bwd(lg, lab, gl)
         elif teacher is not None:
             self._head_kd_loss(sv, logits, labels, teacher, ov)
+        elif anchor is not None:
+            self._head_anchor_loss(sv, logits, labels, anchor, ov)
         elif labels is not None:
             sv["loss"], lse_ce = ops.ce_fwd(logits, labels, poison=ov)
             if train:
@@ -521,6 +526,24 @@ class EngineMixin:
         out3, lse3 = ops.ce_kd_fwd(logits, t_logits, labels, tau, lam, poison=poison)
         sv["loss"] = out3[0:1]
         sv["head_loss"] = lambda lg, lab, gl: ops.ce_kd_bwd(lg, t_logits, lab, lse3, tau, lam, gl)
+        self.last_head_losses = out3
+
+    def _head_anchor_loss(self, sv, logits, labels, anchor, poison) -> None:
+        """Training head loss with a logit anchor (DER++): beta CE + alpha MSE against the stored logits of the batch's memory samples, read
+        in place, one pass (ops.ce_mse_fwd) -> sv["loss"], sv["head_loss"], ``last_head_losses``.  ``labels`` are the head's own (dense or
+        compact): a labelled row's rank among its sample's labelled rows, which picks its stored row, is the same under both."""
+        store, mem_index, alpha, beta = anchor
+        alpha, beta = float(alpha), float(beta)
+        if not torch.is_tensor(store) or store.dim() != 3 or store.dtype != logits.dtype or store.shape[2] != logits.shape[2]:
+            raise ValueError(f"logit_anchor store {tuple(getattr(store, 'shape', ()))} {getattr(store, 'dtype', None)} does not match head logits "
+                             f"[.., {logits.shape[2]}] {logits.dtype}")
+        if not torch.is_tensor(mem_index) or mem_index.dtype != torch.int64 or mem_index.shape != (logits.shape[0],):
+            raise ValueError(f"logit_anchor mem_index must be int64 [{logits.shape[0]}], got {tuple(getattr(mem_index, 'shape', ()))} "
+                             f"{getattr(mem_index, 'dtype', None)}")
+        store, mem_index = store.detach(), mem_index.to(logits.device).contiguous()
+        out3, lse = ops.ce_mse_fwd(logits, store, mem_index, labels, alpha, beta, poison=poison)
+        sv["loss"] = out3[0:1]
+        sv["head_loss"] = lambda lg, lab, gl: ops.ce_mse_bwd(lg, store, mem_index, lab, lse, alpha, beta, gl)
         self.last_head_losses = out3
 
     def _dw_group_fuses_squares(self, rows: int) -> bool:

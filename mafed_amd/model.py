@@ -278,7 +278,12 @@ class VLPythiaForCausalLM(EngineMixin, GenerationMixin, nn.Module):
         # [B * Rc] int32, or None = all T text rows) and gets a frozen model's logits on exactly those rows, in compute dtype.  The head
         # loss is then CE + lambda tau^2 KL (ops.ce_kd_fwd) instead of CE.  None: nothing changes.  Not copied by deepcopy.
         self.logit_teacher = None
-        # device [3] = (loss, CE, KD) of the last training forward that had a logit teacher (written there; read by callers, no sync)
+        # Replay against stored logits (methods/der.py).  A tuple (store [n_mem, A, V] in compute dtype, mem_index int64 [B],
+        # alpha, beta): a training forward with labels then takes beta CE + alpha MSE (ops.ce_mse_fwd) as its head loss, labelled row (b, t)
+        # held against store[mem_index[b], rank of t among b's labelled rows].  None: nothing changes.  Not both with ``logit_teacher``.
+        self.logit_anchor = None
+        # device [3] = (loss, CE, KD) of the last training forward that had a logit teacher, or (loss, CE, MSE) under a logit anchor
+        # (written there; read by callers, no sync)
         self.last_head_losses: Optional[torch.Tensor] = None
         # The head loss of a training forward with labels: "ce" (with a logit teacher: CE + KL), or "sqnorm" = the squared norm of the logits
         # on the labelled rows, the objective of the MAS importance pass (methods/mas.py sets and restores it).  Anything else
@@ -641,6 +646,29 @@ class VLPythiaForCausalLM(EngineMixin, GenerationMixin, nn.Module):
         st = self._engine_forward(feats.to(dev).contiguous(), input_ids.to(dev, torch.int64).contiguous(),
                                   attention_mask.to(dev, torch.int64).contiguous(), None, False, train=False, head_rows=rows)
         return st["logits"]
+
+    @torch.no_grad()
+    def answer_logits(self, feats, input_ids, attention_mask, labels, A: int) -> torch.Tensor:
+        """Inference logits on the labelled rows of a batch, in rank order, for a store of answer logits (methods/der.py) -> [B, A, V] in
+        compute dtype: slot j of sample b holds the logits of b's j-th labelled row (the row whose shifted label is its j-th token), unused
+        slots hold zeros.  The engine's own text padding, the stack, then the final LayerNorm and the LM head on those rows only; no
+        activations are kept.  A sample with more than ``A`` labelled rows raises (one host read of a device flag: between tasks)."""
+        A = int(A)
+        if A < 1:
+            raise ValueError(f"answer_logits: A must be at least 1, got {A}")
+        input_ids, attention_mask, labels = self.pad_text_batch(input_ids, attention_mask, labels)
+        B = input_ids.shape[0]
+        ros, _, _, ov = ops.label_rows(labels, A + 1)   # (slots per sample incl. the unlabelled last one)
+        rows = ros.view(B, A + 1)[:, :A].reshape(-1)
+        n = B * A
+        if self.compute_dtype == torch.bfloat16 and n % 128:   # (whole MFMA tiles: the rest are rows of zeros, dropped below)
+            rows = torch.nn.functional.pad(rows, (0, 128 - n % 128), value=-1)
+        out = self.head_logits_rows(feats, input_ids, attention_mask, rows)[:n].view(B, A, self.config.vocab_size)
+        # (a negative row is a zero hidden state, whose logits are the final LayerNorm's bias through the head: not zeros yet)
+        out.masked_fill_((rows[:n] < 0).view(B, A, 1), 0)
+        if int(ov.item()):
+            raise ValueError(f"answer_logits: a sample has more than A = {A} labelled rows")
+        return out
 
     def hidden_grad_taps(self, batch: Dict[str, torch.Tensor], layers: Sequence[int]) -> Dict[int, torch.Tensor]:
         """dL_CE / d hidden_states[l] for every l in ``layers`` from ONE backward sweep (the adaptive-weights pass of

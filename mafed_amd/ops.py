@@ -707,6 +707,44 @@ def ce_kd_bwd(student: torch.Tensor, teacher: torch.Tensor, labels: torch.Tensor
     return out
 
 
+def _anchor_args(student: torch.Tensor, store: torch.Tensor, mem_index: torch.Tensor, labels: torch.Tensor, poison: Optional[torch.Tensor] = None):
+    """:func:`_head_args` of the student's logits, with a store [n_mem, A, V] of the same dtype and V and an int64 ``mem_index`` [B]
+    -> (B, T, V, rows, n_mem, A)"""
+    B, T, V, rows = _head_args(student, labels, poison)
+    if store.dim() != 3 or store.shape[2] != V or store.dtype != student.dtype or store.device != student.device or not store.is_contiguous():
+        raise ValueError(f"store {tuple(store.shape)} {store.dtype} does not match head logits {tuple(student.shape)} {student.dtype} "
+                         "(a contiguous [n_mem, A, V] tensor of the same dtype, V and device)")
+    if mem_index.dtype != torch.int64 or mem_index.shape != (B,) or mem_index.device != student.device or not mem_index.is_contiguous():
+        raise ValueError(f"mem_index must be a contiguous int64 [{B}] tensor on the logits' device, got {tuple(mem_index.shape)} {mem_index.dtype}")
+    return B, T, V, rows, store.shape[0], store.shape[1]
+
+
+def ce_mse_fwd(logits: torch.Tensor, store: torch.Tensor, mem_index: torch.Tensor, labels: torch.Tensor, alpha: float, beta: float,
+               poison: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """DER++ head loss (mafed_ce_mse_fwd): student logits [B,T,V], ``store`` [n_mem, A, V] of stored answer logits, ``mem_index`` int64 [B]
+    (the stored sample of each batch row), labels [B,T] -> (out3 = [beta CE + alpha MSE, CE, MSE], lse [B,T]).  Labelled row (b, t) is
+    held against ``store[mem_index[b], rank of t among b's labelled rows]``, read in place.  ``poison`` as in :func:`ce_fwd`."""
+    B, T, V, rows, n_mem, A = _anchor_args(logits, store, mem_index, labels, poison)
+    lse, row = rows(), rows(2)
+    out3 = torch.empty(3, dtype=torch.float32, device=logits.device)
+    check(_lib.load().mafed_ce_mse_fwd(_ptr(logits), _ptr(store), _dt(logits), _ptr(labels), _ptr(mem_index), B, T, V, n_mem, A, float(alpha),
+                                       float(beta), _ptr(lse), _ptr(row[0]), _ptr(row[1]), _ptr(out3), _ptr(poison), _stream()), "mafed_ce_mse_fwd")
+    return out3, lse
+
+
+def ce_mse_bwd(logits: torch.Tensor, store: torch.Tensor, mem_index: torch.Tensor, labels: torch.Tensor, lse: torch.Tensor, alpha: float,
+               beta: float, gloss: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dL/d(student logits) of :func:`ce_mse_fwd`: the cross-entropy and the squared-distance gradient, one pass (``out``: a buffer of its own)."""
+    B, T, V, _, n_mem, A = _anchor_args(logits, store, mem_index, labels)
+    assert lse.shape == (B, T) and lse.dtype == torch.float32 and lse.is_contiguous()
+    if out is None:
+        out = torch.empty_like(logits)
+    assert out.shape == logits.shape and out.dtype == logits.dtype and out.is_contiguous() and out.data_ptr() != logits.data_ptr()
+    check(_lib.load().mafed_ce_mse_bwd(_ptr(logits), _ptr(store), _dt(logits), _ptr(labels), _ptr(mem_index), _ptr(lse), B, T, V, n_mem, A,
+                                       float(alpha), float(beta), _ptr(gloss), _ptr(out), _stream()), "mafed_ce_mse_bwd")
+    return out
+
+
 def distill_fwd(s: torch.Tensor, t, attention_mask: torch.Tensor, P: int, cosine: bool = False,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """-> out[4] = {lang_sum, vision_sum, n_lang, n_vision}; ``t`` a dense fp32 [B, S, h] tensor or ``TeacherRows``"""
