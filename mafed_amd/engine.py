@@ -11,9 +11,10 @@ and tests index:
   logits, loss         [B, T, V] ([B, 1, V] ``last_only``, [n, V] ``head_rows``, [B, Rc, V] row-sparse) / loss [1]; None when not computed
   layers               per layer, training: {x, mean, rstd, ln1, ln2, qkv, ao, lse, u, a}; ``keep_qkv``: {qkv}; else empty
   training only        proj = (fc, u0, a0) of the projector; final = (xt, lnf, fmean, frstd) of the final LayerNorm; x_last;
-                       sparse_head = (slot of every text row, compact labels); head_loss = the backward of the loss ``_head_text`` chose:
-                       (logits, head labels, dloss [1]) -> dlogits, holding what it needs (CE: the lse; under a logit teacher: teacher
-                       logits, lse3, tau, lambda; squared norm: nothing); the backward sweep pops it
+                       sparse_head = (slot of every text row, compact labels); head_loss = the backward the forward's head loss returned
+                       (``model.head_loss``, mafed_amd/head_loss.py; cross-entropy when the slot is empty): (logits, head labels,
+                       dloss [1]) -> dlogits, a closure over what it needs (CE: the lse; logit distillation: teacher logits, lse3, tau,
+                       lambda; logit anchor: store, index, lse; squared norm: nothing); the backward sweep pops it
   inject, inject_cosine   written by the fused distillation node before the backward: {layer: (teacher hidden state, device [4] scales)}
 """
 from __future__ import annotations
@@ -25,6 +26,7 @@ import torch
 
 from mafed_amd import ops
 from mafed_amd._lib import EPI_GELU, EPI_GELU_BWD
+from mafed_amd.head_loss import CROSS_ENTROPY, HeadLoss
 
 
 def _trim(x: torch.Tensor, n: int) -> torch.Tensor:
@@ -208,7 +210,7 @@ class BackwardSweep:
         sp = sv.get("sparse_head")   # (slot of every text row, compact labels): the head ran on the labelled rows only
         n_head = logits.shape[0] * logits.shape[1]
         head_labels = sp[1] if sp is not None else sv["labels"]
-        # the backward of whichever loss _head_text chose; popped, so that what it holds (a teacher's logits) goes with this call
+        # the backward of this forward's head loss; popped, so that what it holds (a teacher's logits) goes with this call
         dlog = sv.pop("head_loss")(logits, head_labels, gl).view(n_head, V)
         self.wgrad(dlog, lnf, Go.embed_out)
         if cd == torch.bfloat16:
@@ -461,90 +463,55 @@ class EngineMixin:
     def _head_text(self, sv, x, feats, want_hidden: bool, train: bool, label_rows_hint: Optional[int]) -> None:
         """final LN (fp32 hidden state L only when asked for) + LM head on the T text positions (vl_pythia.py:89,310) + the loss: the
         row-sparse head where a training batch qualifies, else the dense one."""
-        cd, labels = self.compute_dtype, sv["labels"]
+        cd = self.compute_dtype
         B, T, P, S, h = sv["B"], sv["T"], sv["P"], sv["S"], self.config.hidden_size
         xt = x.view(B, S, h)[:, P:, :].reshape(B * T, h)
         lnf, _, fmean, frstd = self._final_ln(xt, cd, save_stats=train)
         if want_hidden:
             sv["hidden"].append(self._final_ln(x, torch.float32)[0].view(B, S, h))
-        # Row-sparse head (training, with the caller's bound on labelled positions per sample): only rows whose shifted label is a token
-        # enter the head GEMM, the CE and -- in the backward -- the head's two gradient GEMMs: 4 answer tokens of 32 text positions in
-        # the VQA batches, i.e. 256 of 1024 rows at B = 32 (Rc = slots per sample incl. the unlabelled last one, B * Rc a tile multiple)
-        Rc = None
-        if train and labels is not None and label_rows_hint is not None:
-            need = max(2, int(label_rows_hint) + 1)   # (slots per sample incl. the unlabelled last one; a hint of 0 still gets two)
-            Rc = need if cd == torch.float32 else next((r for r in range(need, T + 1) if (B * r) % 128 == 0), None)  # (the MFMA tiles want whole 128-row tiles)
-            if Rc is not None and Rc * 2 > T:
-                Rc = None   # not worth it
-        ros = ov = None
-        if Rc is not None:
-            ros, sor, labels, ov = ops.label_rows(labels, Rc)
-            # device flag: 1 if a sample had more labelled positions than the hint promised -- rows were dropped; the CE below then
-            # returns NaN (no host synchronisation: the step fails loudly instead of training on a wrong loss)
-            self.last_label_overflow = ov
-            sv["sparse_head"] = (sor, labels)
-        if self.head_objective not in ("ce", "sqnorm"):
-            raise ValueError(f"head_objective must be 'ce' or 'sqnorm', got {self.head_objective!r}")
-        sqnorm = self.head_objective == "sqnorm" and train and sv["labels"] is not None   # the MAS importance pass (DESIGN 4k)
-        teacher = None
-        anchor = self.logit_anchor if (train and sv["labels"] is not None and not sqnorm) else None
-        if anchor is not None and self.logit_teacher is not None:
-            raise ValueError("logit_teacher and logit_anchor are both set: one head loss per step (CE + KL or CE + MSE), not both")
-        if train and sv["labels"] is not None and self.logit_teacher is not None and not sqnorm:
-            # the teacher's logits on the padded batch of this forward and the head's row selection (the row-sparse head's ``row_of_slot``,
-            # None = all text rows): on the caller's stream, in front of the student's head
-            t_logits, tau, lam = self.logit_teacher(feats, sv["input_ids"], sv["attention_mask"], ros)
-            teacher = (t_logits.detach(), float(tau), float(lam))
+        ros, labels, ov = self._head_rows(sv, train, label_rows_hint)
+        # the loss: cross-entropy, or on a training forward with labels whatever ``head_loss`` holds (mafed_amd/head_loss.py).  Its
+        # ``prepare`` (a teacher's forward) runs on the caller's stream in front of the student's head; its backward goes to
+        # BackwardSweep.head through sv["head_loss"]
+        hl = None
+        if labels is not None:
+            hl = self.head_loss if (train and self.head_loss is not None) else CROSS_ENTROPY
+            if not isinstance(hl, HeadLoss):
+                raise ValueError(f"head_loss must be a mafed_amd.head_loss.HeadLoss or None, got {hl!r}")
+            prepared = hl.prepare(feats, sv["input_ids"], sv["attention_mask"], ros)
         if ros is not None:
             lnf = ops.gather_rows(lnf, ros)
-        logits = sv["logits"] = ops.gemm(lnf, self._tensors(0).outer.embed_out, False, True).view(B, Rc or T, self.config.vocab_size)
-        # the loss, chosen here and nowhere else: the squared norm of the labelled rows' logits under ``head_objective = "sqnorm"``,
-        # CE + lambda tau^2 KL under a logit teacher, beta CE + alpha MSE under a logit anchor, else CE.  Each leaves its own backward in
-        # sv["head_loss"] for BackwardSweep.head, which calls ops.<name> when it runs (not bound here)
-        if sqnorm:
-            sv["loss"], _ = ops.sqnorm_fwd(logits, labels, poison=ov)
-            sv["head_loss"] = lambda lg, lab, gl: ops.sqnorm_bwd(lg, lab, gl)
-        elif teacher is not None:
-            self._head_kd_loss(sv, logits, labels, teacher, ov)
-        elif anchor is not None:
-            self._head_anchor_loss(sv, logits, labels, anchor, ov)
-        elif labels is not None:
-            sv["loss"], lse_ce = ops.ce_fwd(logits, labels, poison=ov)
-            if train:
-                sv["head_loss"] = lambda lg, lab, gl: ops.ce_bwd(lg, lab, lse_ce, gl)
+        logits = sv["logits"] = ops.gemm(lnf, self._tensors(0).outer.embed_out, False, True).view(B, -1, self.config.vocab_size)
         if train:
             sv["final"] = (xt, lnf, fmean, frstd)
             sv["x_last"] = x
+        if hl is not None:
+            sv["loss"], parts, backward = hl.forward(logits, labels, ov, prepared)
+            if train:
+                sv["head_loss"] = backward
+            if parts is not None:
+                self.last_head_losses = parts
 
-    def _head_kd_loss(self, sv, logits, labels, teacher, poison) -> None:
-        """Training head loss with a logit teacher: CE + lambda tau^2 KL against the teacher's logits of the same rows, one pass
-        (ops.ce_kd_fwd) -> sv["loss"], sv["head_loss"], ``last_head_losses``."""
-        t_logits, tau, lam = teacher
-        if t_logits.dtype != logits.dtype or t_logits.numel() != logits.numel():
-            raise ValueError(f"logit_teacher returned {tuple(t_logits.shape)} {t_logits.dtype} for head rows {tuple(logits.shape)} {logits.dtype}")
-        t_logits = t_logits.contiguous().view(logits.shape)
-        out3, lse3 = ops.ce_kd_fwd(logits, t_logits, labels, tau, lam, poison=poison)
-        sv["loss"] = out3[0:1]
-        sv["head_loss"] = lambda lg, lab, gl: ops.ce_kd_bwd(lg, t_logits, lab, lse3, tau, lam, gl)
-        self.last_head_losses = out3
-
-    def _head_anchor_loss(self, sv, logits, labels, anchor, poison) -> None:
-        """Training head loss with a logit anchor (DER++): beta CE + alpha MSE against the stored logits of the batch's memory samples, read
-        in place, one pass (ops.ce_mse_fwd) -> sv["loss"], sv["head_loss"], ``last_head_losses``.  ``labels`` are the head's own (dense or
-        compact): a labelled row's rank among its sample's labelled rows, which picks its stored row, is the same under both."""
-        store, mem_index, alpha, beta = anchor
-        alpha, beta = float(alpha), float(beta)
-        if not torch.is_tensor(store) or store.dim() != 3 or store.dtype != logits.dtype or store.shape[2] != logits.shape[2]:
-            raise ValueError(f"logit_anchor store {tuple(getattr(store, 'shape', ()))} {getattr(store, 'dtype', None)} does not match head logits "
-                             f"[.., {logits.shape[2]}] {logits.dtype}")
-        if not torch.is_tensor(mem_index) or mem_index.dtype != torch.int64 or mem_index.shape != (logits.shape[0],):
-            raise ValueError(f"logit_anchor mem_index must be int64 [{logits.shape[0]}], got {tuple(getattr(mem_index, 'shape', ()))} "
-                             f"{getattr(mem_index, 'dtype', None)}")
-        store, mem_index = store.detach(), mem_index.to(logits.device).contiguous()
-        out3, lse = ops.ce_mse_fwd(logits, store, mem_index, labels, alpha, beta, poison=poison)
-        sv["loss"] = out3[0:1]
-        sv["head_loss"] = lambda lg, lab, gl: ops.ce_mse_bwd(lg, store, mem_index, lab, lse, alpha, beta, gl)
-        self.last_head_losses = out3
+    def _head_rows(self, sv, train: bool, label_rows_hint: Optional[int]):
+        """The rows the head runs on -> (row of every slot or None = all T text rows, the head's labels, overflow flag or None).
+        Row-sparse head (training, with the caller's bound on labelled positions per sample): only rows whose shifted label is a token
+        enter the head GEMM, the loss and -- in the backward -- the head's two gradient GEMMs: 4 answer tokens of 32 text positions in
+        the VQA batches, i.e. 256 of 1024 rows at B = 32 (Rc = slots per sample incl. the unlabelled last one, B * Rc a tile multiple)"""
+        labels, B, T = sv["labels"], sv["B"], sv["T"]
+        Rc = None
+        if train and labels is not None and label_rows_hint is not None:
+            need = max(2, int(label_rows_hint) + 1)   # (slots per sample incl. the unlabelled last one; a hint of 0 still gets two)
+            Rc = need if self.compute_dtype == torch.float32 else next((r for r in range(need, T + 1) if (B * r) % 128 == 0), None)  # (the MFMA tiles want whole 128-row tiles)
+            if Rc is not None and Rc * 2 > T:
+                Rc = None   # not worth it
+        if Rc is None:
+            return None, labels, None
+        ros, sor, labels, ov = ops.label_rows(labels, Rc)
+        # device flag: 1 if a sample had more labelled positions than the hint promised -- rows were dropped; the loss then
+        # returns NaN (no host synchronisation: the step fails loudly instead of training on a wrong loss)
+        self.last_label_overflow = ov
+        sv["sparse_head"] = (sor, labels)
+        return ros, labels, ov
 
     def _dw_group_fuses_squares(self, rows: int) -> bool:
         """Will a grouped weight-gradient launch of this model (``dw_group_layers`` layers x four matrices, K = rows) emit the squares of

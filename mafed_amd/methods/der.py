@@ -20,6 +20,7 @@ from typing import Optional
 
 import torch
 
+from mafed_amd.head_loss import LogitAnchor
 from mafed_amd.methods.flat import require_native
 from mafed_amd.methods.replay import ER
 
@@ -41,7 +42,7 @@ class DER(ER):
         """``ER.update``, then the answer logits of the samples it added, from ``model`` (the model that just finished the task)."""
         if model is None:   # (raises before anything of the plugin's has changed)
             raise ValueError("DER: update needs the model that finished the task (update(dataset, model=...))")
-        require_native(model, "DER", "the stored logits are its own head's (model.answer_logits) and the replay loss is computed inside its head (model.logit_anchor)")
+        require_native(model, "DER", "the stored logits are its own head's (model.answer_logits) and the replay loss is computed inside its head (model.head_loss)")
         n0 = 0 if self.mem_dataloader is None else len(self.mem_dataloader)
         super().update(dataset, model=model, **kwargs)
         buf = self.mem_dataloader
@@ -66,15 +67,19 @@ class DER(ER):
 
     # ---- inside a step ---------------------------------------------------------------------------------------------------
     def replay(self, model):
-        """One memory batch, one student forward: beta CE + alpha MSE against the batch's stored logits (``model.logit_anchor``)."""
+        """One memory batch, one student forward: beta CE + alpha MSE against the batch's stored logits (a ``LogitAnchor`` in
+        ``model.head_loss`` for that forward).  A model whose slot is taken is refused before anything is launched."""
+        if model.head_loss is not None:
+            raise ValueError(f"DER: model.head_loss already holds a {type(model.head_loss).__name__} and the replay step needs the slot for "
+                             "its LogitAnchor: one head loss per step, not both")
         batch = next(iter(self.mem_dataloader))
         index = batch.pop("memory_index")
         n_ex = batch["input_ids"].size(0)
-        model.logit_anchor = (self.logits, index, self.alpha, self.beta)
+        model.head_loss = LogitAnchor(self.logits, index, self.alpha, self.beta)
         try:
             loss = model(**batch, compute_loss=True, return_dict=True).loss
         finally:
-            model.logit_anchor = None
+            model.head_loss = None
         out3 = model.last_head_losses
         self.last_ce, self.last_mse = out3[1], out3[2]
         return loss, n_ex

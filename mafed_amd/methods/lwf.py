@@ -6,9 +6,9 @@ arithmetic is this project's: while task k > 0 is learnt,
 
     loss = CE + reg_lambda * temperature^2 * KL(softmax(t / temperature) || softmax(s / temperature))
 
-over the rows that carry a label, normalised like the cross-entropy.  The term lives inside the model's own step: ``update`` installs
-``model.logit_teacher``, the engine asks it for the teacher's logits on the rows its head runs on and the fused kernels of
-``csrc/kd.hip`` do the rest, so the step stays one autograd node and every parameter gradient comes out of the model's sweep.
+over the rows that carry a label, normalised like the cross-entropy.  The term lives inside the model's own step: ``update`` puts a
+``LogitDistillation`` into ``model.head_loss``, the engine asks it for the teacher's logits on the rows its head runs on and the fused
+kernels of ``csrc/kd.hip`` do the rest, so the step stays one autograd node and every parameter gradient comes out of the model's sweep.
 """
 from __future__ import annotations
 
@@ -17,6 +17,7 @@ from typing import Optional
 
 import torch
 
+from mafed_amd.head_loss import LogitDistillation
 from mafed_amd.methods.base import CLStrategy
 
 
@@ -39,25 +40,24 @@ class LwF(CLStrategy):
     def update(self, model, **kwargs):
         """Teacher := frozen copy of the finished task's model; from now on the model's training head loss carries the KL term."""
         if not hasattr(model, "head_logits_rows"):
-            raise TypeError("LwF needs the native model: the distillation term is computed inside its head (model.logit_teacher)")
-        self.past_model = deepcopy(model)   # (VLPythiaForCausalLM.__deepcopy__: the frozen vision tower is shared; no logit_teacher on the copy)
+            raise TypeError("LwF needs the native model: the distillation term is computed inside its head (model.head_loss)")
+        self.past_model = deepcopy(model)   # (VLPythiaForCausalLM.__deepcopy__: the frozen vision tower is shared; the copy's head_loss is empty)
         self.past_model.eval()
         for p in self.past_model.parameters():
             p.requires_grad_(False)
-        model.logit_teacher = self._teacher_logits
+        model.head_loss = LogitDistillation(self._teacher_logits)
         self.task_id += 1
 
     def _teacher_logits(self, feats, input_ids, attention_mask, rows):
-        """``model.logit_teacher``: the frozen model's logits on the text rows the student's head runs on (None = all) + (tau, lambda)."""
+        """The teacher of ``LogitDistillation``: the frozen model's logits on the text rows the student's head runs on (None = all) + (tau, lambda)."""
         return self.past_model.head_logits_rows(feats, input_ids, attention_mask, rows), self.temperature, float(self.reg_lambda)
 
     # ---- inside a step ---------------------------------------------------------------------------------------------------
     def compute_loss(self, model, loss, batch=None, **kwargs):
         """The term is already inside ``loss`` (the model's head computed CE + lambda tau^2 KL): returned unchanged.  ``last_ce`` /
         ``last_kd`` are the two parts of the step, for logging."""
-        out3 = getattr(model, "last_head_losses", None)
-        if self.task_id > 0 and getattr(model, "logit_teacher", None) is not None and out3 is not None:
-            self.last_ce, self.last_kd = out3[1], out3[2]
+        if self.task_id > 0 and isinstance(model.head_loss, LogitDistillation):   # (task 0: any model, plain cross-entropy)
+            self.last_ce, self.last_kd = model.last_head_losses[1], model.last_head_losses[2]
         else:
             self.last_ce = loss.detach()
             self.last_kd = model._hook_zero().view(()) if hasattr(model, "_hook_zero") else torch.zeros((), device=loss.device)

@@ -5,7 +5,7 @@ laid out like ``model.flat_params``: the importance Omega (``omega``) and the an
 accumulator, lives only while an importance pass runs.  With c = ``reg_lambda`` and a = ``alpha``:
 
     update  between tasks, over a dataloader of the task just learnt
-            per batch of n samples:  zero_grad, forward with the squared-norm head objective J (``model.head_objective = "sqnorm"``:
+            per batch of n samples:  zero_grad, forward with the squared-norm head objective J (``model.head_loss = SquaredNorm()``:
             mean_b of sum_t |logits[b,t]|^2 / count_b over the answer rows -- the label values are never read), backward,
             acc += n |g|;  then  Omega_new = acc / N,  Omega = Omega_new (first task) or a Omega + (1 - a) Omega_new,  p* = p,
             task_id += 1
@@ -26,6 +26,7 @@ from typing import Optional, Tuple
 import torch
 
 from mafed_amd import ops
+from mafed_amd.head_loss import SquaredNorm
 from mafed_amd.methods.base import CLStrategy
 from mafed_amd.methods.flat import FlatDict, behind_optimizer, require_native
 
@@ -74,14 +75,14 @@ class MAS(CLStrategy):
 
     # ---- between tasks -----------------------------------------------------------------------------------------------------
     def _importance_sums(self, model, dataloader) -> Tuple[torch.Tensor, float]:
-        """(acc = sum over batches of n |grad J|, N = samples seen).  ``head_objective`` is put back whatever happens."""
+        """(acc = sum over batches of n |grad J|, N = samples seen).  What ``model.head_loss`` held is put back whatever happens."""
         p = self._native(model)
         if dataloader is None:
             raise ValueError("MAS needs the dataloader of the task just learnt to measure the importance")
         model.train()
         behind_optimizer(model)   # (zero_grad below writes the buffer a pipelined update may still be zeroing)
         acc, seen = torch.zeros_like(p), 0
-        previous, model.head_objective = model.head_objective, "sqnorm"
+        previous, model.head_loss = model.head_loss, SquaredNorm()
         try:
             for batch in dataloader:
                 model.zero_grad()
@@ -90,7 +91,7 @@ class MAS(CLStrategy):
                 ops.mas_accumulate_(model.flat_grads, acc, float(n))
                 seen += n
         finally:
-            model.head_objective = previous
+            model.head_loss = previous
             model.zero_grad()
         if seen == 0:
             raise ValueError("MAS: the importance dataloader is empty")

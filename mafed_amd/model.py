@@ -34,6 +34,7 @@ from torch import nn
 from mafed_amd import ops
 from mafed_amd.engine import EngineMixin, SweepRecord, _ModelFn, _trim  # noqa: F401  (SweepRecord re-exported)
 from mafed_amd.generation import BeamSearchOutput, GenerationMixin, _DecodeCache, _GraphedDecode  # noqa: F401  (re-exported)
+from mafed_amd.head_loss import HeadLoss
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -273,22 +274,13 @@ class VLPythiaForCausalLM(EngineMixin, GenerationMixin, nn.Module):
         self.sparse_lm_head = True          # batches that carry ``max_label_rows`` get the row-sparse LM head in training
         # device flag of the last row-sparse training forward (written there; read by callers / tests): 1 = rows were dropped, the loss is NaN
         self.last_label_overflow: Optional[torch.Tensor] = None
-        # Logit distillation (methods/lwf.py).  A callable (feats, input_ids, attention_mask, rows) -> (teacher logits, tau, lambda):
-        # a training forward with labels hands it the padded batch and the head's row selection (the row-sparse head's ``row_of_slot``
-        # [B * Rc] int32, or None = all T text rows) and gets a frozen model's logits on exactly those rows, in compute dtype.  The head
-        # loss is then CE + lambda tau^2 KL (ops.ce_kd_fwd) instead of CE.  None: nothing changes.  Not copied by deepcopy.
-        self.logit_teacher = None
-        # Replay against stored logits (methods/der.py).  A tuple (store [n_mem, A, V] in compute dtype, mem_index int64 [B],
-        # alpha, beta): a training forward with labels then takes beta CE + alpha MSE (ops.ce_mse_fwd) as its head loss, labelled row (b, t)
-        # held against store[mem_index[b], rank of t among b's labelled rows].  None: nothing changes.  Not both with ``logit_teacher``.
-        self.logit_anchor = None
-        # device [3] = (loss, CE, KD) of the last training forward that had a logit teacher, or (loss, CE, MSE) under a logit anchor
-        # (written there; read by callers, no sync)
+        # The head loss of a training forward with labels (mafed_amd/head_loss.py): None = cross-entropy, else one HeadLoss --
+        # LogitDistillation (methods/lwf.py), LogitAnchor (methods/der.py, for one forward), SquaredNorm (methods/mas.py, for its importance
+        # pass) or a caller's own.  No other forward looks at it; anything else in it raises in that forward.  Not copied by deepcopy.
+        self.head_loss: Optional[HeadLoss] = None
+        # device [3] = (loss, CE, KD) of the last training forward under LogitDistillation, or (loss, CE, MSE) under LogitAnchor: the
+        # ``parts`` of a head loss that reports some (written there; read by callers, no sync)
         self.last_head_losses: Optional[torch.Tensor] = None
-        # The head loss of a training forward with labels: "ce" (with a logit teacher: CE + KL), or "sqnorm" = the squared norm of the logits
-        # on the labelled rows, the objective of the MAS importance pass (methods/mas.py sets and restores it).  Anything else
-        # raises in the forward.
-        self.head_objective = "ce"
         self.defer_ln_param_reduce = True   # LayerNorm parameter-gradient reduction on a side stream (needs overlap_param_grads)
         # generation (mafed_amd/generation.py)
         self.beam_trace: Optional[List[Any]] = None   # a list: generate(num_beams > 1) appends every step's candidate lists to it

@@ -85,7 +85,7 @@ def mas_importances_fp64(cfg, sd, batches):
 # ---- the twin plugin ------------------------------------------------------------------------------------------------------------
 def make_torch_mas():
     """``TorchMAS``: the plugin's hooks with torch ops in float64 rounded to fp32, on whatever device the model lives.  The importance
-    pass runs the model's own forward and backward under ``head_objective = "sqnorm"``; everything behind the gradient is torch.  No norm
+    pass runs the model's own forward and backward under ``head_loss = SquaredNorm()``; everything behind the gradient is torch.  No norm
     hand-over: the clip takes the one-pass norm."""
     from mafed_amd.methods.base import CLStrategy
 
@@ -102,15 +102,18 @@ def make_torch_mas():
             return loss
 
         def update(self, model, dataloader=None, **kwargs):
+            from mafed_amd.head_loss import SquaredNorm
             acc, seen = torch.zeros_like(model.flat_params, dtype=torch.float64), 0
-            model.head_objective = "sqnorm"
-            for batch in dataloader:
-                model.zero_grad()
-                n = batch["input_ids"].size(0)
-                model(**batch, compute_loss=True, return_dict=True).loss.backward()
-                acc += n * model.flat_grads.double().abs()
-                seen += n
-            model.head_objective = "ce"
+            previous, model.head_loss = model.head_loss, SquaredNorm()
+            try:
+                for batch in dataloader:
+                    model.zero_grad()
+                    n = batch["input_ids"].size(0)
+                    model(**batch, compute_loss=True, return_dict=True).loss.backward()
+                    acc += n * model.flat_grads.double().abs()
+                    seen += n
+            finally:
+                model.head_loss = previous
             model.zero_grad()
             new = acc / seen
             self.omega = (new if self.task_id == 0 else self.alpha * self.omega.double() + (1.0 - self.alpha) * new).float()

@@ -126,7 +126,7 @@ def test_der_step_vs_oracle_autograd(name, monkeypatch):
     loss_got, n_ex = der.replay(model)
     loss_got.backward()
     torch.cuda.synchronize()
-    assert n_ex == N and len(seen) == 1 and model.logit_anchor is None
+    assert n_ex == N and len(seen) == 1 and model.head_loss is None
     idx = seen[0]["mem_index"].cpu()
     assert sorted(idx.tolist()) == list(range(N))
 
@@ -169,6 +169,7 @@ def test_sparse_head_equals_dense_head_with_a_logit_anchor(dtype, B, T, n_ans, m
     tests/test_gpu_lwf.py::test_sparse_head_equals_dense_head_with_a_logit_teacher); the sparse run's head ran on the B * Rc compact rows.
     The store is the model's own recording in a shuffled order, addressed through ``mem_index``."""
     from mafed_amd import VLPythiaConfig, VLPythiaForCausalLM
+    from mafed_amd.head_loss import LogitAnchor
     cfg = VLPythiaConfig(vocab_size=512, hidden_size=64, num_hidden_layers=2, num_attention_heads=2, intermediate_size=256,
                          vision_hidden_size=32, num_vision_tokens=8)
     model = VLPythiaForCausalLM(cfg, compute_dtype=dtype, device=DEV, seed=5)
@@ -183,7 +184,7 @@ def test_sparse_head_equals_dense_head_with_a_logit_anchor(dtype, B, T, n_ans, m
         model.flat_params.add_(torch.randn(model.flat_params.shape, generator=gen, device=DEV) * 1e-2)
     model._shadow_dirty = True
     seen = _spy_ce_mse(monkeypatch)
-    model.logit_anchor = (store, perm, 0.5, 1.0)
+    model.head_loss = LogitAnchor(store, perm, 0.5, 1.0)
 
     def run(hint):
         model.zero_grad()
@@ -195,7 +196,7 @@ def test_sparse_head_equals_dense_head_with_a_logit_anchor(dtype, B, T, n_ans, m
 
     l0, g0, h0 = run(None)
     l1, g1, h1 = run(n_ans)
-    model.logit_anchor = None
+    model.head_loss = None
     assert int(model.last_label_overflow) == 0 and float(h0[2]) > 0
     Rc = n_ans + 1 if dtype == torch.float32 else next(r for r in range(n_ans + 1, T + 1) if (B * r) % 128 == 0)
     V = cfg.vocab_size
@@ -207,12 +208,12 @@ def test_sparse_head_equals_dense_head_with_a_logit_anchor(dtype, B, T, n_ans, m
     print(f"[der] sparse vs dense head, {dtype}: loss {l0} / {l1}, gradient relative difference {rel:.3e}")
     assert rel <= (1e-5 if dtype == torch.float32 else 1e-2), f"gradients: relative difference {rel:.3e}"
     # against the store in its recorded order the MSE is another number: the index is what pairs the rows
-    model.logit_anchor = (z, perm, 0.5, 1.0)
+    model.head_loss = LogitAnchor(z, perm, 0.5, 1.0)
     try:
         with torch.enable_grad():
             model(**batch, return_dict=True)
     finally:
-        model.logit_anchor = None
+        model.head_loss = None
     assert abs(float(model.last_head_losses[2]) - float(h0[2])) > 1e-2 * float(h0[2])
 
 
@@ -241,14 +242,14 @@ def test_der_before_the_first_update_is_naive():
         assert all(r["branch"] == "task" for r in recs)
         res[key] = ([float(r["loss"]) for r in recs], _checksum(model))
         if key == "der":
-            assert model.logit_anchor is None and method.logits is None and method.last_mse is None
+            assert model.head_loss is None and method.logits is None and method.last_mse is None
     assert res["der"][0] == res["naive"][0], res
     assert res["der"][1] == res["naive"][1], res
 
 
 def test_der_in_the_trainer_after_update(monkeypatch):
     """replay_interval = 1 in task 1: every step is a replay step -- the ce_mse kernels run, ce_fwd does not, loss == beta CE + alpha MSE,
-    and ``logit_anchor`` is cleared afterwards, also when the forward raises.  With replay_interval = 2 the step in between is a task
+    and ``head_loss`` is emptied afterwards, also when the forward raises.  With replay_interval = 2 the step in between is a task
     step: plain cross-entropy, the ce_mse kernels do not run."""
     from mafed_amd import Trainer, ops
     cfg, batches = _t64_batches(3, seed=320)
@@ -265,7 +266,7 @@ def test_der_in_the_trainer_after_update(monkeypatch):
     tr.join()
     torch.cuda.synchronize()
     monkeypatch.setattr(ops, "ce_fwd", real["ce_fwd"])
-    assert rec["branch"] == "replay" and rec["stepped"] and model.logit_anchor is None
+    assert rec["branch"] == "replay" and rec["stepped"] and model.head_loss is None
     ce, mse = float(der.last_ce), float(der.last_mse)
     assert mse > 0.0
     assert abs(float(rec["loss"]) - (beta * ce + alpha * mse)) <= 1e-5 * max(1.0, ce), (float(rec["loss"]), ce, mse)
@@ -278,12 +279,12 @@ def test_der_in_the_trainer_after_update(monkeypatch):
     torch.cuda.synchronize()
     for n in ("ce_mse_fwd", "ce_mse_bwd"):
         monkeypatch.setattr(ops, n, real[n])
-    assert rec["branch"] == "task" and rec["stepped"] and model.logit_anchor is None
+    assert rec["branch"] == "task" and rec["stepped"] and model.head_loss is None
     # a forward that raises (a store of another dtype) leaves no anchor behind
     der.logits = der.logits.to(torch.bfloat16)
     with pytest.raises(ValueError):
         der.replay(model)
-    assert model.logit_anchor is None
+    assert model.head_loss is None
 
 
 def _bf16_steps(overwrite, accumulate=2, n_micro=8):
@@ -413,7 +414,10 @@ def test_state_round_trip():
         other.load_state_dict({"logits": sd["logits"]})
 
 
-def test_conflicting_and_mismatched_hooks_raise():
+def test_conflicting_and_mismatched_hooks_raise(monkeypatch):
+    from mafed_amd import MAS, ops
+    from mafed_amd.head_loss import LogitAnchor, LogitDistillation
+    from mafed_amd.profiler import KernelProfile
     cfg, _, tsd, batch, _ = golden_setup("t64")
     model = _model(cfg, tsd)
     B, V = batch["input_ids"].shape[0], cfg.vocab_size
@@ -427,21 +431,35 @@ def test_conflicting_and_mismatched_hooks_raise():
         finally:
             torch.cuda.synchronize()
 
-    model.logit_anchor = (store, idx, 0.5, 1.0)
+    model.head_loss = LogitAnchor(store, idx, 0.5, 1.0)
     assert forward().loss is not None
-    model.logit_teacher = lambda *a, **k: pytest.fail("the logit teacher ran beside a logit anchor")
-    with pytest.raises(ValueError, match="logit_teacher and logit_anchor"):
-        forward()
-    model.logit_teacher = None
+    model.head_loss = None
+    # one head loss per step: a replay on a model whose slot is taken is refused before anything is launched, and the slot stays as it was
+    der = _der(batch_size=B, memory_size=B)
+    der.update(batch, model=model)
+    torch.cuda.synchronize()
+    taken = model.head_loss = LogitDistillation(lambda *a, **k: pytest.fail("the logit teacher ran beside a logit anchor"))
+    real = {n: getattr(ops, n) for n in ("ce_mse_fwd", "ce_kd_fwd")}
+    for n in real:
+        monkeypatch.setattr(ops, n, lambda *a, _n=n, **k: pytest.fail(f"{_n} ran in a refused replay"))
+    with KernelProfile() as prof:
+        with pytest.raises(ValueError, match="LogitDistillation.*LogitAnchor.*one head loss per step"):
+            der.replay(model)
+    assert prof.records() == [] and model.head_loss is taken
+    for n in real:
+        monkeypatch.setattr(ops, n, real[n])
     for bad in ((store.to(torch.bfloat16), idx), (store[..., : V // 2].contiguous(), idx), (store, idx.to(torch.int32)), (store, idx[:-1])):
-        model.logit_anchor = bad + (0.5, 1.0)
+        model.head_loss = LogitAnchor(*bad, 0.5, 1.0)
         with pytest.raises(ValueError):
             forward()
-    # an inference forward and the squared-norm objective do not look at the anchor
-    model.logit_anchor = (store.to(torch.bfloat16), idx, 0.5, 1.0)
+    # an inference forward and the MAS importance pass do not look at the anchor
+    malformed = model.head_loss = LogitAnchor(store.to(torch.bfloat16), idx, 0.5, 1.0)
     with torch.no_grad():
         assert forward().loss is not None
-    model.head_objective = "sqnorm"
-    assert forward().loss is not None
-    model.head_objective = "ce"
-    model.logit_anchor = None
+    for n in ("ce_mse_fwd", "ce_mse_bwd"):
+        monkeypatch.setattr(ops, n, lambda *a, _n=n, **k: pytest.fail(f"{_n} ran in the MAS importance pass"))
+    mas = MAS()
+    mas.update(model, dataloader=[dev])
+    torch.cuda.synchronize()
+    assert mas.task_id == 1 and model.head_loss is malformed
+    model.head_loss = None

@@ -37,10 +37,11 @@ def _conf(lr=1e-3, accumulate=1):
 def _lwf_pair(cfg, teacher_sd, student_sd, dtype, lam, tau):
     """A model that finished a task with ``teacher_sd`` (LwF.update snapshots it) and then moved on to ``student_sd``."""
     from mafed_amd import CLMethod
+    from mafed_amd.head_loss import LogitDistillation
     model = _model(cfg, teacher_sd, dtype)
     lwf = CLMethod["lwf"](reg_lambda=lam, temperature=tau)
     lwf.update(model)
-    assert lwf.task_id == 1 and model.logit_teacher is not None and lwf.past_model.logit_teacher is None
+    assert lwf.task_id == 1 and isinstance(model.head_loss, LogitDistillation) and lwf.past_model.head_loss is None
     assert not lwf.past_model.training and lwf.past_model is not model
     model.load_state_dict(student_sd, strict=True)
     return model, lwf
@@ -114,14 +115,14 @@ def test_sparse_head_equals_dense_head_with_a_logit_teacher(dtype, B, T, n_ans):
     model._shadow_dirty = True
     batch = _ragged_batch(cfg, B, T, n_ans, seed=B + T)
     seen = []
-    inner = model.logit_teacher
+    inner = model.head_loss.teacher
 
     def spy(feats, ids, am, rows):
         out = inner(feats, ids, am, rows)
         seen.append((None if rows is None else rows.numel(), tuple(out[0].shape), out[0].dtype))
         return out
 
-    model.logit_teacher = spy
+    model.head_loss.teacher = spy
 
     def run(hint):
         model.zero_grad()
@@ -170,7 +171,7 @@ def test_lwf_before_the_first_update_is_naive():
         torch.cuda.synchronize()
         res[key] = ([float(x) for x in losses], _checksum(model))
         if key == "lwf":
-            assert model.logit_teacher is None and float(method.last_kd) == 0.0 and float(method.last_ce) == res[key][0][-1]
+            assert model.head_loss is None and float(method.last_kd) == 0.0 and float(method.last_ce) == res[key][0][-1]
     assert res["lwf"][0] == res["naive"][0], res
     assert res["lwf"][1] == res["naive"][1], res
 
@@ -198,7 +199,7 @@ def test_lwf_in_the_trainer_after_update():
     # a second task: the teacher is replaced by a snapshot without a teacher of its own
     old = lwf.past_model
     lwf.update(model)
-    assert lwf.task_id == 2 and lwf.past_model is not old and lwf.past_model.logit_teacher is None
+    assert lwf.task_id == 2 and lwf.past_model is not old and lwf.past_model.head_loss is None
 
 
 def _bf16_steps(overwrite, accumulate=2, n_micro=8):

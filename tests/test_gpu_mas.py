@@ -213,10 +213,12 @@ def _ragged_batch(cfg, B, T, n_ans, seed):
 
 @pytest.mark.parametrize("dtype,B,T,n_ans", [(torch.float32, 6, 12, 3), (torch.bfloat16, 32, 16, 3)])
 def test_sparse_head_equals_dense_head_under_sqnorm(dtype, B, T, n_ans, monkeypatch):
-    """The same batch with and without ``max_label_rows`` under ``head_objective = "sqnorm"``: equal J and gradients (the shapes and
+    """The same batch with and without ``max_label_rows`` under ``head_loss = SquaredNorm()``: equal J and gradients (the shapes and
     bounds of tests/test_gpu_lwf.py::test_sparse_head_equals_dense_head_with_a_logit_teacher), the sparse run on the B * Rc compact rows;
-    the cross-entropy kernels and a logit teacher are not called."""
-    from mafed_amd import VLPythiaConfig, VLPythiaForCausalLM, ops
+    the cross-entropy kernels are not called.  Then ``MAS.update`` on the model with LwF installed: its teacher and the CE + KL kernels are
+    not called during the importance pass, and LwF's object is back in the slot afterwards."""
+    from mafed_amd import CLMethod, MAS, VLPythiaConfig, VLPythiaForCausalLM, ops
+    from mafed_amd.head_loss import LogitDistillation, SquaredNorm
     cfg = VLPythiaConfig(vocab_size=512, hidden_size=64, num_hidden_layers=2, num_attention_heads=2, intermediate_size=256,
                          vision_hidden_size=32, num_vision_tokens=8)
     model = VLPythiaForCausalLM(cfg, compute_dtype=dtype, device=DEV, seed=5)
@@ -228,9 +230,8 @@ def test_sparse_head_equals_dense_head_under_sqnorm(dtype, B, T, n_ans, monkeypa
         return fwd(logits, labels, poison=poison)
     monkeypatch.setattr(ops, "sqnorm_fwd", spy)
     for name in ("ce_fwd", "ce_bwd", "ce_kd_fwd", "ce_kd_bwd"):
-        monkeypatch.setattr(ops, name, lambda *a, _n=name, **k: pytest.fail(f"{_n} ran under head_objective = 'sqnorm'"))
-    model.logit_teacher = lambda *a, **k: pytest.fail("the logit teacher ran under head_objective = 'sqnorm'")
-    model.head_objective = "sqnorm"
+        monkeypatch.setattr(ops, name, lambda *a, _n=name, **k: pytest.fail(f"{_n} ran under the squared-norm head loss"))
+    model.head_loss = SquaredNorm()
 
     def run(hint):
         model.zero_grad()
@@ -251,6 +252,17 @@ def test_sparse_head_equals_dense_head_under_sqnorm(dtype, B, T, n_ans, monkeypa
     rel = float((g1 - g0).norm() / g0.norm())
     print(f"[mas] sparse vs dense head, {dtype}: J {l0} / {l1}, gradient relative difference {rel:.3e}")
     assert rel <= (1e-5 if dtype == torch.float32 else 1e-2), f"gradients: relative difference {rel:.3e}"
+    # the teacher does not run in the importance pass (ce_kd_fwd / ce_kd_bwd still fail the test if called)
+    model.head_loss = None
+    lwf = CLMethod["lwf"]()
+    lwf.update(model)
+    installed = model.head_loss
+    assert isinstance(installed, LogitDistillation)
+    installed.teacher = lambda *a, **k: pytest.fail("the logit teacher ran in the MAS importance pass")
+    mas = MAS()
+    mas.update(model, dataloader=[batch])
+    torch.cuda.synchronize()
+    assert mas.task_id == 1 and model.head_loss is installed and len(shapes) == 3
 
 
 # ---- plugin level ---------------------------------------------------------------------------------------------------------------
@@ -276,7 +288,7 @@ def _conf(lr=1e-3, accumulate=1, grad_norm=2.0):
 def test_mas_importance_pass_matches_oracle_autograd():
     """Omega_new from compute_importances on the golden t64 model in fp32, over the golden batch (3 samples) and the first 2 samples of a
     second one, per parameter tensor against the oracle model under autograd in float64 with the same objective.  Around the pass:
-    ``head_objective`` is back to "ce", also when a batch raises, the gradient buffer is zero, and a forward under the default objective
+    ``head_loss`` is empty again, also when a batch raises, the gradient buffer is zero, and a forward under the default objective
     gives the same bits for logits and loss as before."""
     from mafed_amd import MAS
     from oracle import vlpythia_ref as R
@@ -294,7 +306,7 @@ def test_mas_importance_pass_matches_oracle_autograd():
     mas = MAS()
     got = mas.compute_importances(model, [_to_dev(b) for b in loader])
     torch.cuda.synchronize()
-    assert model.head_objective == "ce" and not bool(model.flat_grads.any()) and mas.omega is None and mas.task_id == 0
+    assert model.head_loss is None and not bool(model.flat_grads.any()) and mas.omega is None and mas.task_id == 0
     loss1, logits1 = probe()
     assert torch.equal(_bits(loss0), _bits(loss1)) and torch.equal(_bits(logits0), _bits(logits1))
     ref = mas_importances_fp64(cfg, sd, loader)
@@ -309,7 +321,7 @@ def test_mas_importance_pass_matches_oracle_autograd():
         raise RuntimeError("loader failed")
     with pytest.raises(RuntimeError, match="loader failed"):
         mas.compute_importances(model, broken())
-    assert model.head_objective == "ce" and not bool(model.flat_grads.any())
+    assert model.head_loss is None and not bool(model.flat_grads.any())
     with pytest.raises(ValueError, match="empty"):
         mas.compute_importances(model, [])
 
@@ -375,7 +387,7 @@ def _mas_run(cls, c, dtype=torch.float32, overwrite=True, pipeline=False, checks
         if i == k["update_after"]:
             tr.join()
             mas.update(model, dataloader=[_to_dev(b) for b in mas_loader(batches)])
-            assert model.head_objective == "ce"
+            assert model.head_loss is None
         rec = tr.step(_to_dev(batches[i][0]), i)
         assert rec["branch"] == "task" and rec["stepped"] and torch.is_tensor(rec["loss"]) and rec["loss"].is_cuda
         losses.append(rec["loss"])
@@ -508,8 +520,8 @@ def test_mas_refusals():
         mas.update(model)
     with pytest.raises(ValueError, match="alpha"):
         MAS(alpha=1.5)
-    model.head_objective = "mse"
-    with pytest.raises(ValueError, match="head_objective"):
+    model.head_loss = "mse"   # (not a HeadLoss)
+    with pytest.raises(ValueError, match="head_loss"):
         model(**_to_dev(batch), return_dict=True)
-    model.head_objective = "ce"
+    model.head_loss = None
     assert float(model(**_to_dev(batch), return_dict=True).loss.detach()) > 0

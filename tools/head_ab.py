@@ -7,15 +7,18 @@
 Each tree is a checkout with its library built (TREE/mafed_amd/libmafed_hip.so).  Its package and library are loaded in a fresh child
 process of their own -- this process never opens the GPU -- which runs
 
-  * the six head ops (ce_fwd / ce_bwd, sqnorm_fwd / sqnorm_bwd, ce_kd_fwd / ce_kd_bwd) and token_logprob on fp32 and bf16 logits at
+  * the eight head ops (ce_fwd / ce_bwd, sqnorm_fwd / sqnorm_bwd, ce_kd_fwd / ce_kd_bwd, ce_mse_fwd / ce_mse_bwd) and token_logprob on fp32 and bf16 logits at
     (B, T, V) = (2, 3, 512), (3, 5, 1028) (V % 8 != 0: the narrow bf16 KD kernels), (2, 4, 50304), (5, 66, 512) (a second trip of both
     loops of the finalize kernel) and (1, 1, 512) (no row predicts anything), and on bf16 logits at V = 512 that start 8 bytes past a
     16-byte boundary (the narrow KD kernels at V % 8 == 0); the labels are the full / one / none samples of tests/test_gpu_kd.py in
     their three rotations, with the labels V - 1, 0 and V + 5 in a full sample; poison absent, 0 and 1; tau in {0.5, 1, 2}, lambda in
-    {0, 0.3};
-  * one forward + backward of a tiny model in fp32 and bf16, dense and with ``max_label_rows``, under plain CE, under
-    ``head_objective = "sqnorm"`` and under a logit teacher (LwF after one ``update``): the loss, the head's ``dlogits`` as the
-    backward sweep receives them (the ``ops.*_bwd`` wrappers are looked up on the module when the sweep runs) and ``flat_grads``.
+    {0, 0.3}; for ce_mse a store of A = T rows per sample (the teacher logits) behind a fixed permutation, (alpha, beta) in
+    {(0.5, 1), (0, 1), (0.5, 0)};
+  * one forward + backward of a tiny model in fp32 and bf16, dense and with ``max_label_rows``, under plain CE, under the squared-norm
+    objective, under a logit teacher (LwF after one ``update``) and under a logit anchor (DER++: the store is the model's own
+    ``answer_logits`` in a shuffled order, recorded before the parameters move).  The head loss is installed through ``model.head_loss``
+    where the tree's model has that slot, else through the three attributes it replaced, so one copy of this script drives both
+    trees.  Emitted: the loss, the head's ``dlogits`` as the backward sweep receives them (the ``ops.*_bwd`` wrappers are looked up on the module when the sweep runs) and ``flat_grads``.
     bf16 ``flat_grads`` have been seen to differ from run to run of one tree (give the same tree twice to see which lines do):
     there the loss and ``dlogits`` are the comparison.
 
@@ -93,6 +96,7 @@ def child(tree):
     cases = [(shape, dtype, False) for shape in SHAPES for dtype in (torch.float32, torch.bfloat16)] + [((3, 5, 512), torch.bfloat16, True)]
     for (B, T, V), dtype, offset in cases:
         s, t = logits_pair(B, T, V, dtype, 1000 + B * T + V, offset)
+        mem_index = torch.randperm(B, generator=torch.Generator().manual_seed(7)).to(dev)   # store = t [B, A = T, V]
         for first in range(3):
             labels = _labels(torch, B, T, V, first, seed=first).to(dev)
             tag = f"{B}x{T}x{V} {str(dtype)[6:]}{' offset' if offset else ''} labels{first}"
@@ -106,6 +110,12 @@ def child(tree):
                 out3, lse3 = ops.ce_kd_fwd(s, t, labels, 2.0, 0.3, poison=poison)
                 emit(f"{tag} ce_kd_fwd tau=2 lam=0.3 poison={pname} out3", out3)
                 emit(f"{tag} ce_kd_fwd tau=2 lam=0.3 poison={pname} lse3", lse3)
+                for alpha, beta in ((0.5, 1.0), (0.0, 1.0), (0.5, 0.0)):
+                    out3, lse_a = ops.ce_mse_fwd(s, t, mem_index, labels, alpha, beta, poison=poison)
+                    emit(f"{tag} ce_mse_fwd alpha={alpha} beta={beta} poison={pname} out3", out3)
+                    emit(f"{tag} ce_mse_fwd alpha={alpha} beta={beta} poison={pname} lse", lse_a)
+                    if poison is None:
+                        emit(f"{tag} ce_mse_bwd alpha={alpha} beta={beta}", ops.ce_mse_bwd(s, t, mem_index, labels, lse_a, alpha, beta, gl))
             emit(f"{tag} ce_bwd", ops.ce_bwd(s, labels, lse, gl))
             emit(f"{tag} sqnorm_bwd", ops.sqnorm_bwd(s, labels, gl))
             for tau in (0.5, 1.0, 2.0):
@@ -123,8 +133,17 @@ def child(tree):
     cfg = VLPythiaConfig(vocab_size=512, hidden_size=64, num_hidden_layers=2, num_attention_heads=2, intermediate_size=256,
                          vision_hidden_size=32, num_vision_tokens=8)
     seen = []   # what the head's backward returned
-    for name in ("ce_bwd", "sqnorm_bwd", "ce_kd_bwd"):
+    for name in ("ce_bwd", "sqnorm_bwd", "ce_kd_bwd", "ce_mse_bwd"):
         setattr(ops, name, lambda *a, _f=getattr(ops, name), **k: seen.append(_f(*a, **k)) or seen[-1])
+
+    def install(model, sqnorm=False, anchor=None):
+        """The head loss of the model's next steps: cross-entropy, the squared norm or an anchor (store, mem_index, alpha, beta)."""
+        if hasattr(model, "head_loss"):
+            from mafed_amd.head_loss import LogitAnchor, SquaredNorm
+            model.head_loss = SquaredNorm() if sqnorm else LogitAnchor(*anchor) if anchor is not None else None
+        else:   # a tree from before the slot: three attributes
+            model.head_objective, model.logit_teacher, model.logit_anchor = "sqnorm" if sqnorm else "ce", None, anchor
+
     for dtype, B, T, n_ans in ((torch.float32, 6, 12, 3), (torch.bfloat16, 32, 16, 3)):
         model = VLPythiaForCausalLM(cfg, compute_dtype=dtype, device=dev, seed=5)
         batch = _ragged_batch(torch, cfg, B, T, n_ans, B + T, dev)
@@ -140,13 +159,19 @@ def child(tree):
                 assert len(seen) == 1
                 emit(f"{tag} dlogits", seen[0])
                 emit(f"{tag} flat_grads", model.flat_grads)
-                if mode == "lwf":
+                if mode in ("lwf", "der"):
                     emit(f"{tag} last_head_losses", model.last_head_losses)
 
         step("ce")
-        model.head_objective = "sqnorm"
+        install(model, sqnorm=True)
         step("sqnorm")
-        model.head_objective = "ce"
+        install(model)
+        # DER++'s store: the model's own answer logits, sample b in row perm[b] (tests/test_gpu_der.py), before the parameters move
+        z = model.answer_logits(batch["patch_embeddings"], batch["input_ids"], batch["attention_mask"], batch["labels"], n_ans)
+        perm = torch.randperm(B, generator=torch.Generator().manual_seed(1)).to(dev)
+        store = torch.empty_like(z)
+        store[perm] = z
+        emit(f"step {str(dtype)[6:]} der store", store)
         lwf = CLMethod["lwf"](reg_lambda=1.0, temperature=2.0)
         lwf.update(model)
         gen = torch.Generator(device=dev).manual_seed(6)
@@ -154,6 +179,8 @@ def child(tree):
             model.flat_params.add_(torch.randn(model.flat_params.shape, generator=gen, device=dev) * 1e-2)
         model._shadow_dirty = True
         step("lwf")
+        install(model, anchor=(store, perm, 0.5, 1.0))
+        step("der")
 
 
 def run(tree):

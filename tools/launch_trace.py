@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch
 
-from mafed_amd import CLMethod, FeatureDistillation, Naive, Trainer, VLPythiaConfig, VLPythiaForCausalLM
+from mafed_amd import CLMethod, DER, FeatureDistillation, MAS, Naive, Trainer, VLPythiaConfig, VLPythiaForCausalLM
 from mafed_amd.profiler import KernelProfile
 
 DEV = "cuda:0"
@@ -121,6 +121,27 @@ def scenario_h():   # generate over a shared-image prefill, one score call
     def run():
         m.generate(max_new_tokens=4, eos_token_id=None, **kw)
         m.score(candidate_ids=cand, **kw)
+    return run
+
+
+def scenario_i():   # DER++: one replay step (the memory batch under the row-sparse head) after update
+    m = model(torch.bfloat16)
+    opts = types.SimpleNamespace(tasks=["a", "b"], seed=11, batch_size=16, accumulate_grad_batches=1)
+    der = DER(opts, memory_size=16, model_type="vlpythia")
+    der.update({k: v.cpu() for k, v in batch(16, 24, 71, hint=False).items()}, model=m)
+    tr = Trainer(m, der, conf(), task_id=1)
+    return lambda: steps(tr, [batch(16, 24, 72)])
+
+
+def scenario_j():   # MAS: the importance pass over two batches, consolidation, then one step with the penalty
+    m = model(torch.bfloat16)
+    mas = MAS(reg_lambda=4.0)
+    tr = Trainer(m, mas, conf(), task_id=0)
+    loader = [batch(16, 24, 81), batch(16, 24, 82, hint=False)]
+
+    def run():
+        mas.update(m, dataloader=loader)
+        steps(tr, [batch(16, 24, 83)])
     return run
 
 
