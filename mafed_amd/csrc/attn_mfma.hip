@@ -125,7 +125,7 @@ __device__ __forceinline__ void load_col_frags(bf16x8 (&f)[D / 32], const bf16_t
 
 // Two-phase form of load_col_frags for software pipelining across slices: issue the raw 16-byte loads (and the rotary
 // partner chunk + cos/sin rows where needed) for the NEXT slice before computing the current one; finish (rotate, cast)
-// when the slice starts, a whole slice of MFMAs later.
+// when the slice starts, a whole slice of MFMAs later.  col_raw_issue fetches one partner chunk and col_raw_finish rotates x[0] only (g * 8 < rot, dims 0 .. 31): rot <= 32 (attn_resident_fits).
 template <int D>
 struct ColRaw {
   uint4 x[D / 32];
@@ -1250,7 +1250,9 @@ static double attn_fwd_flops(const AttnShape& sh) { return 4.0 * sh.D * ((double
 static bool attn_resident_fits(const AttnShape& sh, size_t* bytes) {
   const size_t nrows = (size_t)(sh.S + 31) / 32 * 32;
   *bytes = nrows * sh.D * 2 * 2 + nrows * 4 * 2 + (size_t)sh.D * 4 * 2;  // two operand images + two fp32 rows (key bias | LSE, delta) + the column-sum row
-  return sh.D <= 128 && *bytes <= 160 * 1024;  // (D = 256: 295 KiB at S = 288 -- K / V go through LDS in 64-row tiles instead)
+  // (D = 256: 295 KiB at S = 288 -- K / V go through LDS in 64-row tiles instead.  rot = 64: col_raw_finish rotates the column operand's
+  // first k-step only, i.e. rotary dims 0 .. 31; with 64 of them the second rotary half of q (k in dK / dV) would stay un-rotated)
+  return sh.D <= 128 && sh.rot <= 32 && *bytes <= 160 * 1024;
 }
 static int g_attn_variant = 0;  // 0 automatic, 1 force the tiled kernels (tests)
 
