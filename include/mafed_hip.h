@@ -424,6 +424,31 @@ int mafed_packnet_scan(const uint32_t* hist, int n_segments, int pass, double fr
 int mafed_packnet_apply(float* p, void* shadow, uint8_t* owner, float* anchor, int64_t n, const int64_t* segments, int n_segments,
                         int blocks_per_segment, int task, const int64_t* state, int64_t* stats, void* stream);
 
+/* ---- task-vector model merging: task arithmetic, MagMax, TIES -------------------------------------------
+ * On flat fp32 buffers laid out like the parameters: theta (the fine-tuned parameters), base (theta_0) and the streaming state.  Base
+ * pointers must be 16-byte aligned.  tau = fl(theta - base), one IEEE subtraction; every sum, product and quotient below is rounded on its
+ * own (no FMA), counts are integers: the same bits on every run.
+ *   fold:       MAFED_MERGE_SUM: acc = fl(acc + tau).  MAFED_MERGE_MAGMAX: acc = |tau| > |acc| ? tau : acc (strict; a NaN tau never wins, a
+ *               NaN acc never leaves).
+ *   ties_hist:  pass 0, 1, 2 of the radix select of mafed_packnet_hist (same segments table, digits, 2048-bin histograms, state) on the
+ *               31-bit pattern of |tau|, over every element of a segment.  The scan between two passes is mafed_packnet_scan with
+ *               fraction = 1 - density: m = the segment's length, r = floor(fraction * m), tau_bits = the r-th smallest pattern.
+ *   ties_fold:  with the state the third scan left: element i of a segment is kept iff r == 0 or pattern(|tau|) > tau_bits.  Kept and
+ *               tau > 0: pos += tau, counts[2 i] += 1; kept and tau < 0: neg += tau, counts[2 i + 1] += 1 (byte counters: 255 folds at
+ *               most); tau == 0 or NaN: nothing.  stats[s][2] = the number kept.  Elements outside every segment are not touched.
+ *   apply:      d = acc (sum, magmax; neg and counts NULL) or, for MAFED_MERGE_TIES with acc = pos and s = fl(pos + neg):
+ *               s > 0: pos / npos, s < 0: neg / nneg, else +0.0.  p = fl(base + fl(scaling * d)); shadow (bf16 bits, or NULL) = bf16(p),
+ *               round to nearest even.
+ * The host reads nothing back. */
+enum { MAFED_MERGE_SUM = 0, MAFED_MERGE_MAGMAX = 1, MAFED_MERGE_TIES = 2 };
+int mafed_merge_fold(const float* theta, const float* base, float* acc, int64_t n, int rule, void* stream);
+int mafed_merge_ties_hist(const float* theta, const float* base, int64_t n, const int64_t* segments, int n_segments, int blocks_per_segment,
+                          int pass, const int64_t* state, uint32_t* hist, void* stream);
+int mafed_merge_ties_fold(const float* theta, const float* base, float* pos, float* neg, uint8_t* counts, int64_t n, const int64_t* segments,
+                          int n_segments, int blocks_per_segment, const int64_t* state, int64_t* stats, void* stream);
+int mafed_merge_apply(float* p, void* shadow, const float* base, const float* acc, const float* neg, const uint8_t* counts, int64_t n, int rule,
+                      float scaling, void* stream);
+
 /* ---- representation-drift analysis: per-layer, per-modality linear CKA (mafed/analysis/) --------------------------
  * Modality pooling of one forward's hidden states (mafed/analysis/get_average_CKA_per_layer.py:107-118): for sample b and
  * layer l (hidden_host[l] = hidden_states[l + 1], fp32 [B, S, h], S = P + T)

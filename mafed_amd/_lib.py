@@ -73,6 +73,10 @@ SIGNATURES = {
     "mafed_packnet_hist": (_i, [_p, _p, _l, _p, _i, _i, _i, _i, _p, _p, _p]),
     "mafed_packnet_scan": (_i, [_p, _i, _i, _d, _p, _p, _p]),
     "mafed_packnet_apply": (_i, [_p, _p, _p, _p, _l, _p, _i, _i, _i, _p, _p, _p]),
+    "mafed_merge_fold": (_i, [_p, _p, _p, _l, _i, _p]),
+    "mafed_merge_ties_hist": (_i, [_p, _p, _l, _p, _i, _i, _i, _p, _p, _p]),
+    "mafed_merge_ties_fold": (_i, [_p, _p, _p, _p, _p, _l, _p, _i, _i, _p, _p, _p]),
+    "mafed_merge_apply": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _f, _p]),
     "mafed_cka_pool": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _l, _p, _p]),
     "mafed_cka_stats_workspace_bytes": (_z, [_l, _l, _l]),
     "mafed_cka_stats": (_i, [_p, _l, _l, _l, _l, _l, _p, _p, _p, _z, _p]),

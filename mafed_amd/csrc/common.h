@@ -38,7 +38,7 @@ void set_error(const char* fmt, ...);
 enum KernelTag {
   K_GEMM_BF16 = 0, K_GEMM_F32, K_GEMM_SKINNY, K_ATTN_FWD, K_ATTN_BWD_DQ, K_ATTN_BWD_DKV, K_ATTN_EXACT, K_LN_FWD, K_LN_BWD, K_LN_BWD_REDUCE,
   K_CE_FWD, K_CE_BWD, K_DISTILL_FWD, K_DISTILL_BWD, K_ADAMW, K_GRADNORM, K_EMBED_FWD, K_EMBED_BWD, K_COLSUM, K_CAST, K_EWC, K_SMALL, K_GEMM_PP,
-  K_CE_KD_FWD, K_CE_KD_BWD, K_SI, K_MAS, K_SQNORM, K_PACKNET, K_CE_MSE_FWD, K_CE_MSE_BWD, K_TAG_COUNT
+  K_CE_KD_FWD, K_CE_KD_BWD, K_SI, K_MAS, K_SQNORM, K_PACKNET, K_MERGE, K_CE_MSE_FWD, K_CE_MSE_BWD, K_TAG_COUNT
 };
 extern std::atomic<bool> g_prof_on;   // read on every launch (caller thread and autograd's backward thread), written under the profiler's mutex
 bool prof_events(int tag, double work, hipEvent_t* e0, hipEvent_t* e1);

@@ -9,7 +9,7 @@
 // The mask pass gives a thread 16 consecutive elements: one 16-byte owner load beside four 16-byte fp32 vectors.  The prune is
 // a three-pass radix select (11 + 10 + 10 bits) on the 31-bit pattern of |p|: integer counts only, so the same bits on every run, and
 // every scalar (m, k, tau, the number pruned) stays on the device.
-#include "flat_pass.h"
+#include "radix_select.h"
 
 namespace mafed {
 
@@ -118,43 +118,22 @@ __global__ __launch_bounds__(256) void packnet_hold_kernel(float* __restrict__ p
 }
 
 // ---- the prune: radix select per segment ---------------------------------------------------------------------------------------------
-constexpr int SELECT_BINS = 2048;   // bins of the first digit (11 bits), and the stride of a segment's histogram; the other two use 1024
-
-__device__ __forceinline__ uint32_t mag_bits(float v) { return __float_as_uint(v) & 0x7fffffffu; }
-
-// This block's share of segment blockIdx.y: f(i, pattern of |p[i]|, owner[i]) for each of its elements inside [0, n).  The segment may
-// begin and end anywhere: the buffer's aligned fp32 vectors that lie wholly inside it are read as vectors (with their owner word), the
-// two that straddle an end element by element.  Every element of a vector goes to the same thread.
+// This block's share of segment blockIdx.y (the walk, the pattern and its digits: radix_select.h): f(i, pattern of |p[i]|, owner[i]) for each of
+// its elements inside [0, n).  The aligned fp32 vectors that lie wholly inside the segment are read as vectors (with their owner word),
+// the two that straddle an end element by element.
 template <class F>
 __device__ __forceinline__ void segment_pass(const float* p, const uint8_t* owner, int64_t n, const int64_t* __restrict__ segments, F f) {
-  int64_t lo = segments[2 * blockIdx.y], hi = lo + segments[2 * blockIdx.y + 1];
-  lo = lo < 0 ? 0 : lo;
-  hi = hi > n ? n : hi;
-  if (hi <= lo) return;
-  const int64_t v_hi = (hi + 3) / 4, stride = (int64_t)gridDim.x * flat_block_dim();
-  for (int64_t v = lo / 4 + (int64_t)blockIdx.x * flat_block_dim() + threadIdx.x; v < v_hi; v += stride) {
-    const int64_t base = v * 4;
-    if (base >= lo && base + 4 <= hi) {
-      const float4 a = load4(p + base);
-      const uint32_t w = *reinterpret_cast<const uint32_t*>(owner + base);
-      f(base, mag_bits(a.x), w & 0xffu);
-      f(base + 1, mag_bits(a.y), (w >> 8) & 0xffu);
-      f(base + 2, mag_bits(a.z), (w >> 16) & 0xffu);
-      f(base + 3, mag_bits(a.w), w >> 24);
-    } else {
-      for (int e = 0; e < 4; ++e) {
-        const int64_t i = base + e;
-        if (i >= lo && i < hi) f(i, mag_bits(p[i]), (uint32_t)owner[i]);
-      }
-    }
-  }
+  segment_walk(n, segments,
+               [&](int64_t base) {
+                 const float4 a = load4(p + base);
+                 const uint32_t w = *reinterpret_cast<const uint32_t*>(owner + base);
+                 f(base, mag_bits(a.x), w & 0xffu);
+                 f(base + 1, mag_bits(a.y), (w >> 8) & 0xffu);
+                 f(base + 2, mag_bits(a.z), (w >> 16) & 0xffu);
+                 f(base + 3, mag_bits(a.w), w >> 24);
+               },
+               [&](int64_t i) { f(i, mag_bits(p[i]), (uint32_t)owner[i]); });
 }
-
-// digit PASS of a pattern and the bits above it: 11 | 10 | 10
-template <int PASS>
-__device__ __forceinline__ uint32_t digit(uint32_t bits) { return PASS == 0 ? bits >> 20 : PASS == 1 ? (bits >> 10) & 1023u : bits & 1023u; }
-template <int PASS>
-__device__ __forceinline__ uint32_t above(uint32_t bits) { return PASS == 0 ? 0u : PASS == 1 ? bits >> 20 : bits >> 10; }
 
 template <int PASS>
 __global__ __launch_bounds__(256) void packnet_hist_kernel(const float* __restrict__ p, const uint8_t* __restrict__ owner, int64_t n,
@@ -295,10 +274,6 @@ extern "C" int mafed_packnet_view(float* p, void* shadow, const uint8_t* owner, 
          as_stream(stream), p, (bf16_t*)shadow, owner, (const float*)nullptr, n, (uint32_t)k);
   MAFED_CHECK_LAUNCH("packnet_view");
   return MAFED_OK;
-}
-
-static bool select_grid_ok(int n_segments, int blocks_per_segment) {
-  return n_segments >= 0 && n_segments <= 65535 && blocks_per_segment >= 1 && blocks_per_segment <= 65535;
 }
 
 extern "C" int mafed_packnet_hist(const float* p, const uint8_t* owner, int64_t n, const int64_t* segments, int n_segments, int blocks_per_segment,

@@ -28,7 +28,7 @@ size_t g_prof_cap = 0;
 const char* const kTagNames[K_TAG_COUNT] = {
     "gemm_bf16", "gemm_f32", "gemm_skinny", "attn_fwd", "attn_bwd_dq", "attn_bwd_dkv", "attn_exact", "layernorm_fwd", "layernorm_bwd",
     "layernorm_bwd_reduce", "ce_fwd", "ce_bwd", "distill_fwd", "distill_bwd", "adamw", "gradnorm", "embed_concat_fwd", "embed_concat_bwd",
-    "colsum", "cast", "ewc", "small", "gemm_pp", "ce_kd_fwd", "ce_kd_bwd", "si", "mas", "sqnorm", "packnet", "ce_mse_fwd",
+    "colsum", "cast", "ewc", "small", "gemm_pp", "ce_kd_fwd", "ce_kd_bwd", "si", "mas", "sqnorm", "packnet", "merge", "ce_mse_fwd",
     "ce_mse_bwd"};
 }  // namespace
 

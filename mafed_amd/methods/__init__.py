@@ -3,7 +3,7 @@
 ``ewc`` is a different method from MAFED; it is built as the first "next" row.  ``lwf`` has no reference
 implementation (only the checkpoint suffix, mafed/utils/eval_utils.py:23): its arithmetic is DESIGN.md section 4h, and it is an
 extension of the registry, not one of the reference's entries.  ``AGEM`` has no reference implementation either; it is
-exported here and constructed directly -- it is not in the registry yet.  The same holds for ``SI``, ``MAS`` (section 4k), ``PackNet`` (section 4l) and ``DER`` (section 4n).
+exported here and constructed directly -- it is not in the registry yet.  The same holds for ``SI``, ``MAS`` (section 4k), ``PackNet`` (section 4l), ``DER`` (section 4n) and ``TaskMerging`` (section 4p).
 How ``ER``, ``DER``, ``AGEM`` and ``FeatureDistillation`` fill their replay memory is their ``memory_selection`` argument (``mafed_amd.selection``, section 4m).
 """
 from mafed_amd.methods.agem import AGEM
@@ -15,6 +15,7 @@ from mafed_amd.methods.ewc import EWC
 from mafed_amd.methods.lwf import LwF
 from mafed_amd.methods.mas import MAS
 from mafed_amd.methods.memory import HBMReplayBuffer
+from mafed_amd.methods.merging import TaskMerging
 from mafed_amd.methods.packnet import PackNet
 from mafed_amd.methods.replay import ER
 from mafed_amd.methods.si import SI

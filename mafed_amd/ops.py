@@ -1025,6 +1025,88 @@ def packnet_prune_(p: torch.Tensor, shadow: Optional[torch.Tensor], owner: torch
     return stats
 
 
+MERGE_RULES = {"sum": 0, "magmax": 1, "ties": 2}   # MAFED_MERGE_* of include/mafed_hip.h
+
+
+def _merge_flat(*ts: Optional[torch.Tensor], shadow: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None) -> int:
+    """fp32 buffers of one length n, the bf16 shadow [n] and the byte counters [n, 2]: contiguous.  A mismatch is refused with
+    ``MafedHipError`` in front of any launch, like a misaligned pointer."""
+    ts = [t for t in ts if t is not None]
+    n = ts[0].numel()
+    ok = all(t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 1 and t.numel() == n for t in ts)
+    ok = ok and (shadow is None or (shadow.dtype == torch.bfloat16 and shadow.is_contiguous() and shadow.dim() == 1 and shadow.numel() == n))
+    ok = ok and (counts is None or (counts.dtype == torch.uint8 and counts.is_contiguous() and counts.shape == (n, 2)))
+    if not ok:
+        raise _lib.MafedHipError("merge: the flat buffers must be contiguous, one-dimensional and of one length (fp32; bf16 shadow [n]; "
+                                 "uint8 counts [n, 2])")
+    return n
+
+
+def merge_select_blocks(max_length: int) -> int:
+    """Blocks per segment of the TIES launches: one per 1024 fp32 vectors of the longest segment, 512 at most.  Unlike PackNet's layer
+    matrices the tensors of a model differ in length by orders of magnitude; a block with no vector of its segment leaves at once."""
+    return max(1, min((int(max_length) // 4 + 1 + 1023) // 1024, 512))
+
+
+def merge_fold_(theta: torch.Tensor, base: torch.Tensor, acc: torch.Tensor, rule: str) -> None:
+    """tau = theta - base; ``"sum"``: acc += tau; ``"magmax"``: acc = |tau| > |acc| ? tau : acc.  Each operation rounded once."""
+    if rule not in ("sum", "magmax"):
+        raise ValueError("merge_fold_: rule must be 'sum' or 'magmax', not %r" % (rule,))
+    n = _merge_flat(theta, base, acc)
+    check(_lib.load().mafed_merge_fold(_ptr(theta), _ptr(base), _ptr(acc), n, MERGE_RULES[rule], _stream()), "mafed_merge_fold")
+
+
+def merge_ties_hist(theta: torch.Tensor, base: torch.Tensor, segments: torch.Tensor, blocks_per_segment: int, radix_pass: int,
+                    state: torch.Tensor, hist: torch.Tensor) -> None:
+    """hist[s][bin] = number of elements of segment s whose pattern of |theta - base| has the prefix in state above digit ``radix_pass``."""
+    n = _merge_flat(theta, base)
+    n_seg = _packnet_tables(segments, state, hist=hist)
+    check(_lib.load().mafed_merge_ties_hist(_ptr(theta), _ptr(base), n, _ptr(segments), n_seg, int(blocks_per_segment), int(radix_pass), _ptr(state),
+                                            _ptr(hist), _stream()), "mafed_merge_ties_hist")
+
+
+def merge_ties_fold_pass_(theta: torch.Tensor, base: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, counts: torch.Tensor,
+                           segments: torch.Tensor, blocks_per_segment: int, state: torch.Tensor, stats: torch.Tensor) -> None:
+    """The fold pass alone, with the threshold the third scan left in ``state``: on kept elements pos / neg += tau and their counter += 1;
+    stats[s][2] = the number kept."""
+    n = _merge_flat(theta, base, pos, neg, counts=counts)
+    n_seg = _packnet_tables(segments, state, stats)
+    check(_lib.load().mafed_merge_ties_fold(_ptr(theta), _ptr(base), _ptr(pos), _ptr(neg), _ptr(counts), n, _ptr(segments), n_seg,
+                                            int(blocks_per_segment), _ptr(state), _ptr(stats), _stream()), "mafed_merge_ties_fold")
+
+
+def merge_ties_fold_(theta: torch.Tensor, base: torch.Tensor, pos: torch.Tensor, neg: torch.Tensor, counts: torch.Tensor, segments: torch.Tensor,
+                     blocks_per_segment: int, drop: float, state: Optional[torch.Tensor] = None, hist: Optional[torch.Tensor] = None,
+                     stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One TIES fold of every segment (int64 [S, 2] = {offset, length} on the device): three histogram + scan passes find the
+    floor(drop * m)-th smallest |theta - base| of each, then the fold pass; seven launches, nothing read back.
+    -> stats, int64 [S, 4] = {m, r, kept, pattern of the threshold} on the device."""
+    _merge_flat(theta, base, pos, neg, counts=counts)   # (in front of the first launch)
+    n_seg, dev = segments.size(0), theta.device
+    state = torch.zeros(n_seg, 4, dtype=torch.int64, device=dev) if state is None else state
+    stats = torch.zeros(n_seg, 4, dtype=torch.int64, device=dev) if stats is None else stats
+    hist = torch.zeros(n_seg, PACKNET_BINS, dtype=torch.int32, device=dev) if hist is None else hist
+    for radix_pass in range(3):
+        merge_ties_hist(theta, base, segments, blocks_per_segment, radix_pass, state, hist)
+        packnet_scan(hist, n_seg, radix_pass, drop, state, stats)
+    merge_ties_fold_pass_(theta, base, pos, neg, counts, segments, blocks_per_segment, state, stats)
+    return stats
+
+
+def merge_apply_(p: torch.Tensor, shadow: Optional[torch.Tensor], base: torch.Tensor, acc: torch.Tensor, rule: str, scaling: float,
+                 neg: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None) -> None:
+    """p = base + scaling * d (product and sum rounded separately), shadow = bf16(p).  d = acc for ``"sum"`` and ``"magmax"``; for
+    ``"ties"`` (acc = pos, with ``neg`` and ``counts``) the mean of the elected sign: pos / npos where pos + neg > 0, neg / nneg where
+    it is < 0, +0.0 otherwise."""
+    if rule not in MERGE_RULES:
+        raise ValueError("merge_apply_: unknown rule %r" % (rule,))
+    if (rule == "ties") != (neg is not None and counts is not None) or (neg is None) != (counts is None):
+        raise _lib.MafedHipError("merge_apply_: neg and counts come with the ties rule, and only with it")
+    n = _merge_flat(p, base, acc, neg, shadow=shadow, counts=counts)
+    check(_lib.load().mafed_merge_apply(_ptr(p), _ptr(shadow), _ptr(base), _ptr(acc), _ptr(neg), _ptr(counts), n, MERGE_RULES[rule], float(scaling),
+                                        _stream()), "mafed_merge_apply")
+
+
 def cka_pool(hidden: Sequence[torch.Tensor], attention_mask: torch.Tensor, P: int, out: torch.Tensor, rows: Optional[torch.Tensor] = None) -> None:
     """out[0, l, rows[b]] = mean of hidden[l][b, :P]; out[1, l, rows[b]] = mean of the last sum(attention_mask[b]) rows of hidden[l][b]
     (fp32 hidden states [B, S, h], text mask [B, T], out fp32 [2, L, n, h])."""
