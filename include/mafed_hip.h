@@ -358,6 +358,28 @@ int mafed_agem_blocks(int64_t n);
 int mafed_agem_dots(const float* g, const float* r, int64_t n, float* stats4, void* workspace, size_t workspace_bytes, void* stream);
 int mafed_agem_project(const float* g, const float* r, float* out, int64_t n, const float* stats4, float* sumsq_partials, void* stream);
 
+/* ---- GEM gradient constraints (Lopez-Paz & Ranzato, 2017) ------------------------------------------
+ * On flat fp32 buffers, g = the step's gradient, refs[0 .. K) = the gradients of one memory batch per finished task at the same
+ * parameters, 1 <= K <= 8.  refs is a HOST array of K device pointers; they travel by value in the kernel arguments.
+ *   gram:    gram64[(K + 1) x (K + 1)] (device, fp64, symmetric to the bit) = sum_i x_a[i] x_b[i] with x_0 = g, x_k = refs[k - 1].  Products and
+ *            per-thread sums in fp32, (K + 1)(K + 2) / 2 partials per block in the workspace (mafed_gem_workspace_bytes), folded in
+ *            double by one block: no atomics, the same bits on every run.
+ *   solve:   q_k = gram[0][k], P = gram[1..K][1..K] + eps I.  Every q_k >= 0: stats12 = 0.  Else v = argmin 1/2 v'Pv + q'v subject to
+ *            v_k >= margin, exactly, by enumerating the supports in fp64; stats12[0 .. 7] = v (zeros behind K),
+ *            stats12[8] = violated (0 / 1), stats12[9] = size of the chosen support, stats12[10 .. 11] = 0.  A non-finite Gram entry
+ *            (or no feasible support) gives v_k = NaN and violated = 1: nothing is hidden.
+ *   project: stats12[8] == 0: out = g bit for bit and no ref is read.  Else out[i] = g[i] + sum_k stats12[k] refs[k][i], one fma per
+ *            k in ascending order.  out may alias g or any ref.  sumsq_partials (or NULL) receives mafed_gem_blocks(n) sum-of-squares
+ *            partials of out, which mafed_gradnorm_finish folds into the clip norm.
+ * n == 0: gram writes a zero matrix, project writes one zero partial. */
+size_t mafed_gem_workspace_bytes(int64_t n, int K);
+int mafed_gem_blocks(int64_t n);
+int mafed_gem_gram(const float* g, const float* const* refs, int K, int64_t n, double* gram64, void* workspace, size_t workspace_bytes,
+                   void* stream);
+int mafed_gem_solve(const double* gram64, int K, float margin, float eps, float* stats12, void* stream);
+int mafed_gem_project(const float* g, const float* const* refs, int K, float* out, int64_t n, const float* stats12, float* sumsq_partials,
+                      void* stream);
+
 /* ---- Synaptic Intelligence (Zenke, Poole, Ganguli 2017) ------------------------------------------
  * On flat fp32 buffers laid out like the parameters p: the step gradient g, the path integral w, the importance omega, the anchor
  * and the stash pair (stash_g, stash_p).

@@ -57,6 +57,11 @@ SIGNATURES = {
     "mafed_agem_blocks": (_i, [_l]),
     "mafed_agem_dots": (_i, [_p, _p, _l, _p, _p, _z, _p]),
     "mafed_agem_project": (_i, [_p, _p, _p, _l, _p, _p, _p]),
+    "mafed_gem_workspace_bytes": (_z, [_l, _i]),
+    "mafed_gem_blocks": (_i, [_l]),
+    "mafed_gem_gram": (_i, [_p, _p, _i, _l, _p, _p, _z, _p]),
+    "mafed_gem_solve": (_i, [_p, _i, _f, _f, _p, _p]),
+    "mafed_gem_project": (_i, [_p, _p, _i, _p, _l, _p, _p, _p]),
     "mafed_si_blocks": (_i, [_l]),
     "mafed_si_stash": (_i, [_p, _p, _p, _p, _l, _f, _p, _p, _p, _p, _p]),
     "mafed_si_penalty_finish": (_i, [_p, _i, _f, _p, _p]),

@@ -3,8 +3,8 @@
 ``ewc`` is a different method from MAFED; it is built as the first "next" row.  ``lwf`` has no reference
 implementation (only the checkpoint suffix, mafed/utils/eval_utils.py:23): its arithmetic is DESIGN.md section 4h, and it is an
 extension of the registry, not one of the reference's entries.  ``AGEM`` has no reference implementation either; it is
-exported here and constructed directly -- it is not in the registry yet.  The same holds for ``SI``, ``MAS`` (section 4k), ``PackNet`` (section 4l), ``DER`` (section 4n) and ``TaskMerging`` (section 4p).
-How ``ER``, ``DER``, ``AGEM`` and ``FeatureDistillation`` fill their replay memory is their ``memory_selection`` argument (``mafed_amd.selection``, section 4m).
+exported here and constructed directly -- it is not in the registry yet.  The same holds for ``SI``, ``MAS`` (section 4k), ``PackNet`` (section 4l), ``DER`` (section 4n), ``TaskMerging`` (section 4p) and ``GEM`` (section 4q: A-GEM's parent method, one constraint per finished task).
+How ``ER``, ``DER``, ``AGEM``, ``GEM`` and ``FeatureDistillation`` fill their replay memory is their ``memory_selection`` argument (``mafed_amd.selection``, section 4m).
 """
 from mafed_amd.methods.agem import AGEM
 from mafed_amd.methods.base import CLStrategy, Naive
@@ -12,6 +12,7 @@ from mafed_amd.methods.der import DER
 from mafed_amd.methods.distillation import FeatureDistillation
 from mafed_amd.methods.distillation_loss_weights import DistillationWeights
 from mafed_amd.methods.ewc import EWC
+from mafed_amd.methods.gem import GEM
 from mafed_amd.methods.lwf import LwF
 from mafed_amd.methods.mas import MAS
 from mafed_amd.methods.memory import HBMReplayBuffer

@@ -863,6 +863,62 @@ def agem_project(g: torch.Tensor, r: torch.Tensor, stats4: torch.Tensor, out: Op
     return out
 
 
+GEM_MAX_REFS = 8
+
+
+def gem_blocks(n: int) -> int:
+    """Number of sum-of-squares partials ``gem_project`` writes for n elements."""
+    return int(_lib.load().mafed_gem_blocks(int(n)))
+
+
+def _gem_refs(g: torch.Tensor, refs: Sequence[torch.Tensor]):
+    """The host array of K device pointers the GEM passes take.  K outside 1 .. 8 is left to the library to refuse."""
+    refs = list(refs)
+    _flat_f32(g, *refs)
+    return (C.c_void_p * max(len(refs), 1))(*[_ptr(r) for r in refs]), len(refs)
+
+
+def gem_gram(g: torch.Tensor, refs: Sequence[torch.Tensor], gram64: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> gram64 [(K + 1), (K + 1)] fp64 on the device: the inner products of x_0 = g and x_k = refs[k - 1] over flat fp32 buffers."""
+    arr, K = _gem_refs(g, refs)
+    lib = _lib.load()
+    if gram64 is None:
+        gram64 = torch.empty((K + 1, K + 1), dtype=torch.float64, device=g.device)
+    assert gram64.dtype == torch.float64 and gram64.numel() == (K + 1) * (K + 1) and gram64.is_contiguous()
+    ws = workspace(g.device).get(lib.mafed_gem_workspace_bytes(g.numel(), K))
+    check(lib.mafed_gem_gram(_ptr(g), arr, K, g.numel(), _ptr(gram64), _ptr(ws), ws.numel(), _stream()), "mafed_gem_gram")
+    return gram64
+
+
+def gem_solve(gram64: torch.Tensor, K: int, margin: float, eps: float, stats12: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> stats12 = {v_0 .. v_7, violated, support size, 0, 0}: GEM's dual quadratic programme on the Gram of ``gem_gram``, solved
+    exactly on the device (v_k >= margin, eps on the diagonal of P)."""
+    K = int(K)
+    assert gram64.dtype == torch.float64 and gram64.is_contiguous() and (not 1 <= K <= GEM_MAX_REFS or gram64.numel() == (K + 1) * (K + 1))
+    if stats12 is None:
+        stats12 = torch.empty(12, dtype=torch.float32, device=gram64.device)
+    assert stats12.dtype == torch.float32 and stats12.numel() == 12 and stats12.is_contiguous()
+    check(_lib.load().mafed_gem_solve(_ptr(gram64), K, float(margin), float(eps), _ptr(stats12), _stream()), "mafed_gem_solve")
+    return stats12
+
+
+def gem_project(g: torch.Tensor, refs: Sequence[torch.Tensor], stats12: torch.Tensor, out: Optional[torch.Tensor] = None,
+                sumsq_partials: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = g + sum_k stats12[k] * refs[k] where stats12[8] says violated (read on the device), else g bit for bit; ``out`` may be
+    ``g`` or any of ``refs``.  ``sumsq_partials`` [>= gem_blocks(n)] receives the sum-of-squares partials of ``out`` for
+    ``gradnorm_finish``."""
+    arr, K = _gem_refs(g, refs)
+    if out is None:
+        out = torch.empty_like(g)
+    _flat_f32(g, out)
+    assert stats12.dtype == torch.float32 and stats12.numel() == 12 and stats12.is_contiguous()
+    if sumsq_partials is not None:
+        assert sumsq_partials.dtype == torch.float32 and sumsq_partials.is_contiguous() and sumsq_partials.numel() >= gem_blocks(g.numel())
+    check(_lib.load().mafed_gem_project(_ptr(g), arr, K, _ptr(out), g.numel(), _ptr(stats12), _ptr(sumsq_partials), _stream()),
+          "mafed_gem_project")
+    return out
+
+
 def si_blocks(n: int) -> int:
     """Number of partials of each kind ``si_stash`` writes for n elements."""
     return int(_lib.load().mafed_si_blocks(int(n)))
