@@ -12,58 +12,72 @@ over the flat gradient buffer in two passes of ``csrc/agem.hip``; dot, rsq, alph
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import Callable, Iterable, Optional
 
 import torch
 
 from mafed_amd import ops
-from mafed_amd.methods.flat import require_native
+from mafed_amd.methods.flat import FlatPlugin
 from mafed_amd.methods.replay import ER
 
 
-class AGEM(ER):
-    """A-GEM.  The memory, the constructor arguments and ``update(dataset, model=...)`` are ER's; the work is in
-    ``update_after_backward`` (Lightning's on_before_optimizer_step)."""
-    grads_only_through_model = False   # (ER's is True) the projection rewrites the gradient buffer behind the model's backward: one-pass / handed-over clip norm
-    single_process_only = True         # under DDP the projection would have to act on the reduced gradients (Trainer refuses a reducer)
-
-    def __init__(self, opts, memory_size, model_type, **kwargs):
-        super().__init__(opts, memory_size, model_type, **kwargs)
-        self._stash: Optional[torch.Tensor] = None      # g while flat_grads receives r; allocated once
-        self._stats: Optional[torch.Tensor] = None      # device {dot, rsq, alpha, violated} of the last projection
-        self._partials: Optional[torch.Tensor] = None   # sum-of-squares partials of g' for the clip norm
-        # views of ``_stats`` (no host synchronisation); None until the first projection
-        self.last_dot = self.last_ref_sq = self.last_alpha = self.last_projected = None
-
+class MemoryProjection(FlatPlugin, ER):
+    """What A-GEM and GEM share: the memory, the constructor arguments and ``update(dataset, model=...)`` are ER's; the work is in the
+    subclass's ``update_after_backward`` (Lightning's on_before_optimizer_step), which compares the window's gradient with gradients
+    of the model's ordinary loss on memory batches and leaves the projected gradient in ``flat_grads``."""
+    # (ER's grads_only_through_model is True; FlatPlugin's False is in front of it)
     _WHY_NATIVE = "the projection runs on its flat gradient buffer (model.flat_grads)"
+    _stash: Optional[torch.Tensor] = None   # g while flat_grads receives the memory gradients; allocated once
 
     def update(self, dataset, model=None, **kwargs):
         if model is not None:
-            require_native(model, "AGEM", self._WHY_NATIVE)
+            self._native(model)
         super().update(dataset, model=model, **kwargs)
 
     def replay(self, model, **kwargs):
         """Never a replay step: the Trainer falls through to the task branch."""
         return None, 0
 
-    def compute_loss(self, model, loss, **kwargs):
-        return loss
+    def _new_buffers(self, model, blocks: Callable[[int], int]) -> bool:
+        """The stash and the clip partials of the projected gradient: allocated once.  True when they are new (the first projection, or
+        another gradient buffer), for the subclass to allocate its own beside them."""
+        self._native(model)
+        g = model.flat_grads
+        if self._stash is not None and self._stash.shape == g.shape and self._stash.device == g.device:
+            return False
+        self._stash, self._partials = torch.empty_like(g), None
+        self._clip_partials(g, blocks)
+        return True
+
+    def _memory_gradients(self, model, loaders: Iterable, then: Optional[Callable[[int], None]] = None) -> None:
+        """g goes to the stash; then one batch of every loader in turn leaves its gradient in ``flat_grads``, and ``then(k)`` runs
+        behind the k-th backward."""
+        self._stash.copy_(model.flat_grads)
+        for k, loader in enumerate(loaders):
+            model.zero_grad()
+            batch = next(iter(loader))
+            model(**batch, compute_loss=True, return_dict=True).loss.backward()   # flat_grads now holds r_k
+            if then is not None:
+                then(k)
+
+
+class AGEM(MemoryProjection):
+    """A-GEM: one reference gradient, from a batch of the mixed memory."""
+
+    def __init__(self, opts, memory_size, model_type, **kwargs):
+        super().__init__(opts, memory_size, model_type, **kwargs)
+        self._stats: Optional[torch.Tensor] = None      # device {dot, rsq, alpha, violated} of the last projection
+        # views of ``_stats`` (no host synchronisation); None until the first projection
+        self.last_dot = self.last_ref_sq = self.last_alpha = self.last_projected = None
 
     def update_after_backward(self, model=None, **kwargs) -> None:
         if self.task_id == 0 or self.mem_dataloader is None or len(self.mem_dataloader) == 0:
             return
-        require_native(model, "AGEM", self._WHY_NATIVE)
-        g = model.flat_grads
-        if self._stash is None or self._stash.shape != g.shape or self._stash.device != g.device:
-            self._stash = torch.empty_like(g)
-            self._stats = torch.zeros(4, dtype=torch.float32, device=g.device)
-            self._partials = torch.zeros(ops.agem_blocks(g.numel()), dtype=torch.float32, device=g.device)
+        if self._new_buffers(model, ops.agem_blocks):
+            self._stats = torch.zeros(4, dtype=torch.float32, device=model.flat_grads.device)
             self.last_dot, self.last_ref_sq, self.last_alpha, self.last_projected = (self._stats[i] for i in range(4))
-        self._stash.copy_(g)
-        model.zero_grad()
-        batch = next(iter(self.mem_dataloader))
-        model(**batch, compute_loss=True, return_dict=True).loss.backward()   # flat_grads now holds r
+        self._memory_gradients(model, [self.mem_dataloader])
         r = model.flat_grads
         ops.agem_dots(self._stash, r, self._stats)
         ops.agem_project(self._stash, r, self._stats, out=r, sumsq_partials=self._partials)
-        model.final_grad_sumsq = self._partials   # FlatAdamW.clip_grad_norm_ folds these instead of reading the buffer again
+        self._hand_over(model)

@@ -28,14 +28,13 @@ import torch
 from mafed_amd import ops
 from mafed_amd.head_loss import SquaredNorm
 from mafed_amd.methods.base import CLStrategy
-from mafed_amd.methods.flat import FlatDict, behind_optimizer, require_native
+from mafed_amd.methods.flat import FlatDict, FlatPlugin, behind_optimizer
 
 
-class MAS(CLStrategy):
+class MAS(FlatPlugin, CLStrategy):
     """``MAS(reg_lambda=1.0, alpha=0.5)``.  ``alpha`` weighs the old importance against the new one at a task boundary (0.5 is Avalanche's
     default); neither it nor ``reg_lambda`` has been tuned for this model."""
-    # grads_only_through_model stays False: the penalty pass rewrites the gradient buffer behind the model's backward (handed-over clip norm)
-    single_process_only = True         # under a reducer the hook runs before the reduced gradients exist (Trainer refuses one)
+    _STATE = (("omega", torch.float32), ("anchor", torch.float32))
 
     def __init__(self, reg_lambda=1.0, alpha=0.5, **kwargs):
         super().__init__(reg_lambda, **{k: v for k, v in kwargs.items() if k in ("mask", "scaler", "opts")})
@@ -44,34 +43,18 @@ class MAS(CLStrategy):
         self.alpha = float(alpha)
         self.omega: Optional[torch.Tensor] = None         # consolidated importance; None until the first update
         self.anchor: Optional[torch.Tensor] = None        # parameters at the last consolidation
-        self._sumsq = self._pen = None
+        self._pen = None
         self.last_penalty: Optional[torch.Tensor] = None  # device scalar c sum Omega (p - p*)^2 of the last penalty pass; None until the first
 
     # ---- buffers -----------------------------------------------------------------------------------------------------------
-    def _native(self, model):
-        require_native(model, "MAS", "its passes run on the flat buffers (model.flat_params / model.flat_grads)")
-        return model.flat_params
-
     def _ensure(self, model) -> None:
-        """Allocate once: the state at the first update, the partials at the first penalty pass."""
-        p = self._native(model)
+        """Allocate once: the state and the partials, at the first update (or the first penalty pass after a checkpoint)."""
+        p = self._place_state(model)
         if self.omega is None:
             self.omega, self.anchor = torch.zeros_like(p), p.detach().clone()
-        if self.omega.shape != p.shape:
-            raise ValueError("MAS's state was built for another model (%d elements, this one has %d)" % (self.omega.numel(), p.numel()))
-        if self.omega.device != p.device:   # a checkpoint loaded on another device
-            self.omega, self.anchor = self.omega.to(p.device), self.anchor.to(p.device)
-        if self._sumsq is None:
-            nb = ops.mas_blocks(p.numel())
-            self._sumsq, self._pen = torch.zeros(nb, dtype=torch.float32, device=p.device), torch.zeros(nb, dtype=torch.float32, device=p.device)
+        if self._pen is None:
+            self._pen = torch.zeros_like(self._clip_partials(p, ops.mas_blocks))
             self.last_penalty = torch.zeros(1, dtype=torch.float32, device=p.device)[0]
-
-    def named(self, model, which: str = "omega") -> FlatDict:
-        """name -> view of ``omega`` / ``anchor``, like EWC's ``fisher[0]``."""
-        if which not in ("omega", "anchor"):
-            raise KeyError(which)
-        self._ensure(model)
-        return FlatDict(model, getattr(self, which))
 
     # ---- between tasks -----------------------------------------------------------------------------------------------------
     def _importance_sums(self, model, dataloader) -> Tuple[torch.Tensor, float]:
@@ -112,9 +95,6 @@ class MAS(CLStrategy):
         self.task_id += 1   # (acc is dropped here: the state is omega and anchor)
 
     # ---- inside a step -----------------------------------------------------------------------------------------------------
-    def compute_loss(self, model, loss, **kwargs):
-        return loss
-
     def update_after_backward(self, model=None, **kwargs) -> None:
         """The penalty pass.  Trainer calls this only on the micro-batch that closes a window; on task 0 it does nothing."""
         self._native(model)
@@ -122,20 +102,16 @@ class MAS(CLStrategy):
             return
         self._ensure(model)
         c = float(self.reg_lambda)
-        ops.mas_penalty_(model.flat_grads, model.flat_params, self.omega, self.anchor, 2.0 * c, self._sumsq, self._pen)
+        ops.mas_penalty_(model.flat_grads, model.flat_params, self.omega, self.anchor, 2.0 * c, self._partials, self._pen)
         ops.si_penalty_finish(self._pen, c, self.last_penalty)
-        model.final_grad_sumsq = self._sumsq   # FlatAdamW.clip_grad_norm_ folds these instead of reading the buffer again
+        self._hand_over(model)
 
     # ---- checkpoints between tasks -----------------------------------------------------------------------------------------
     def state_dict(self):
-        return {"omega": self.omega, "anchor": self.anchor, "task_id": self.task_id}
+        return {**self._state_tensors(), "task_id": self.task_id}
 
     def load_state_dict(self, sd) -> None:
-        missing = [k for k in ("omega", "anchor", "task_id") if k not in sd]
-        if missing:
-            raise ValueError("MAS state without %s" % missing)
-        if sd["omega"] is None or sd["anchor"] is None:
-            self.omega = self.anchor = None
-        else:
-            self.omega, self.anchor = (sd[k].detach().to(torch.float32).clone().contiguous() for k in ("omega", "anchor"))
+        self._require_keys(sd, ("task_id",))
+        names = ("omega", "anchor")
+        self._load_tensors(sd, () if any(sd[k] is None for k in names) else names)   # without one of them there is no state
         self.task_id = int(sd["task_id"])

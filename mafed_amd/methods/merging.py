@@ -25,19 +25,21 @@ import torch
 
 from mafed_amd import ops
 from mafed_amd.methods.base import CLStrategy
-from mafed_amd.methods.flat import FlatDict, behind_optimizer, require_native
+from mafed_amd.methods.flat import FlatDict, FlatPlugin, behind_optimizer
 
 RULES = ("sum", "magmax", "ties")
 MAX_TASKS = 255   # the TIES counters are bytes
-_BUFFERS = ("base", "acc", "pos", "neg", "counts")
 
 
-class TaskMerging(CLStrategy):
+class TaskMerging(FlatPlugin, CLStrategy):
     """``TaskMerging(rule="magmax", scaling=1.0, density=0.2, independent=False)``.  ``rule``: ``"sum"`` (task arithmetic), ``"magmax"`` or
     ``"ties"``; ``scaling``: the lambda of the merged model (``merged_view`` and ``merge_`` take another); ``density``: the share of every
     tensor's task vector that TIES keeps, in (0, 1]; ``independent``: every task starts from ``theta_0`` again (``update`` puts it back;
     the optimiser's state stays the caller's business) instead of MagMax's sequential fine-tuning."""
     grads_only_through_model = True    # no hook touches the gradients: Trainer collects the clip norm as it does for Naive
+    single_process_only = False        # and nothing of it depends on whose gradients they are
+    _WHY_NATIVE = "its passes run on the flat buffers (model.flat_params / model.flat_shadow)"
+    _STATE = (("base", torch.float32), ("acc", torch.float32), ("pos", torch.float32), ("neg", torch.float32), ("counts", torch.uint8))
 
     def __init__(self, rule: str = "magmax", scaling: float = 1.0, density: float = 0.2, independent: bool = False, **kwargs):
         super().__init__(**{k: v for k, v in kwargs.items() if k in ("reg_lambda", "mask", "scaler", "opts")})
@@ -49,8 +51,6 @@ class TaskMerging(CLStrategy):
         self.neg: Optional[torch.Tensor] = None       #       and the negative one
         self.counts: Optional[torch.Tensor] = None    # uint8 [n, 2]: TIES, the number of tasks in pos and in neg
         self.last_trim_stats: Optional[torch.Tensor] = None   # device int64 [tensors, 4] = {m, r, kept, pattern of the threshold}
-        self._segments = self._segment_names = self._select = None
-        self._in_view = False
 
     @staticmethod
     def _check(rule, density) -> None:
@@ -60,46 +60,18 @@ class TaskMerging(CLStrategy):
             raise ValueError("TaskMerging: density must lie in (0, 1], not %r" % (density,))
 
     # ---- buffers -----------------------------------------------------------------------------------------------------------
-    def _native(self, model):
-        require_native(model, "TaskMerging", "its passes run on the flat buffers (model.flat_params / model.flat_shadow)")
-        return model.flat_params
-
-    def _state(self, model):
+    def _ensure(self, model) -> torch.Tensor:
         """The buffers, on the model's device; raises before ``begin`` and for another model."""
-        p = self._native(model)
+        self._native(model)
         if self.base is None:
             raise RuntimeError("TaskMerging: begin(model) has not run (it captures theta_0)")
-        if self.base.numel() != p.numel():
-            raise ValueError("TaskMerging's state was built for another model (%d elements, this one has %d)" % (self.base.numel(), p.numel()))
-        for name in _BUFFERS:
-            t = getattr(self, name)
-            if t is not None and t.device != p.device:   # a checkpoint loaded on another device
-                setattr(self, name, t.to(p.device))
-        return p
-
-    def _tables(self, model):
-        """The device table {offset, length} of every tensor of the model and the selection's workspaces, built at the first TIES fold."""
-        names = list(model._offsets)
-        dev = model.flat_params.device
-        if self._segment_names != names or self._segments.device != dev:
-            rows = [[model._offsets[name][0], model._offsets[name][1]] for name in names]
-            if any(n >= 2 ** 32 for _, n in rows):
-                raise ValueError("TaskMerging trims tensors of fewer than 2^32 elements")
-            self._segments = torch.tensor(rows, dtype=torch.int64, device=dev).reshape(len(rows), 2)
-            self._segment_names = names
-            s = len(rows)
-            self._select = (ops.merge_select_blocks(max([n for _, n in rows], default=0)),
-                            torch.zeros(s, 4, dtype=torch.int64, device=dev), torch.zeros(s, ops.PACKNET_BINS, dtype=torch.int32, device=dev))
-        return self._segments, self._select
+        return self._place_state(model)
 
     def named(self, model, which: str = "base") -> FlatDict:
-        """name -> view of ``base`` / ``acc`` / ``pos`` / ``neg``, like EWC's ``fisher[0]``."""
-        if which not in ("base", "acc", "pos", "neg"):
+        """name -> view of ``base`` / ``acc`` / ``pos`` / ``neg``, where the rule keeps it."""
+        if which == "counts":   # (two to an element: not laid out like the parameters)
             raise KeyError(which)
-        self._state(model)
-        if getattr(self, which) is None:
-            raise RuntimeError("TaskMerging(rule=%r) has no %s" % (self.rule, which))
-        return FlatDict(model, getattr(self, which))
+        return super().named(model, which)
 
     # ---- between tasks -----------------------------------------------------------------------------------------------------
     def begin(self, model) -> None:
@@ -117,14 +89,15 @@ class TaskMerging(CLStrategy):
 
     def update(self, model, **kwargs) -> None:
         """Fold the task vector of the task that ended."""
-        p = self._state(model)
+        p = self._ensure(model)
         if self._in_view:
             raise RuntimeError("TaskMerging: no update inside a merged_view (the parameters are the merged model, not a task's)")
         if self.rule == "ties" and self.task_id >= MAX_TASKS:
             raise RuntimeError("TaskMerging's TIES counters are bytes: %d tasks at most" % MAX_TASKS)
         behind_optimizer(model)
         if self.rule == "ties":
-            segments, (blocks, state, hist) = self._tables(model)
+            # every tensor of the model is a segment; the table and the workspaces are built at the first TIES fold
+            segments, (blocks, state, hist) = self._segment_tables(model, list(model._offsets), lambda longest, s: ops.merge_select_blocks(longest))
             drop = 1.0 - self.density
             self.last_trim_stats = ops.merge_ties_fold_(p, self.base, self.pos, self.neg, self.counts, segments, blocks, drop, state=state, hist=hist)
         else:
@@ -172,24 +145,13 @@ class TaskMerging(CLStrategy):
     def merged_view(self, model, scaling: Optional[float] = None):
         """Inside the block the model is ``theta_0 + scaling * merge(tau_1 .. tau_T)`` (``scaling=None``: the constructor's) for
         ``model(**batch)``, ``generate``, ``sample`` and ``score``.  On exit the parameters and the shadow are put back bit for bit."""
-        p = self._state(model)
-        if self._in_view:
-            raise RuntimeError("TaskMerging: merged_view does not nest")
-        behind_optimizer(model)
-        saved = p.detach().clone()
-        self._in_view = True
-        try:
-            self._apply(model, scaling)
+        self._ensure(model)
+        with self._view(model, "TaskMerging: merged_view does not nest", lambda: self._apply(model, scaling)):
             yield model
-        finally:
-            self._in_view = False
-            with torch.no_grad():
-                p.copy_(saved)
-            model.sync_shadow()
 
     def merge_(self, model, scaling: Optional[float] = None) -> None:
         """Write the merged model into the parameters and the shadow for good."""
-        self._state(model)
+        self._ensure(model)
         if self._in_view:
             raise RuntimeError("TaskMerging: no merge_ inside a merged_view")
         behind_optimizer(model)
@@ -197,20 +159,14 @@ class TaskMerging(CLStrategy):
 
     # ---- checkpoints between tasks -----------------------------------------------------------------------------------------
     def state_dict(self):
-        return {"base": self.base, "acc": self.acc, "pos": self.pos, "neg": self.neg, "counts": self.counts, "task_id": self.task_id,
-                "rule": self.rule, "density": self.density}
+        return {**self._state_tensors(), "task_id": self.task_id, "rule": self.rule, "density": self.density}
 
     def load_state_dict(self, sd) -> None:
-        missing = [k for k in _BUFFERS + ("task_id", "rule", "density") if k not in sd]
-        if missing:
-            raise ValueError("TaskMerging state without %s" % missing)
+        self._require_keys(sd, ("task_id", "rule", "density"))
         self._check(sd["rule"], sd["density"])
         need = ("base", "pos", "neg", "counts") if sd["rule"] == "ties" else ("base", "acc")
         if sd["base"] is not None and any(sd[k] is None for k in need):
             raise ValueError("TaskMerging state of rule %r without %s" % (sd["rule"], [k for k in need if sd[k] is None]))
         self.rule, self.density, self.task_id = sd["rule"], float(sd["density"]), int(sd["task_id"])
-        for name in _BUFFERS:
-            t = sd[name] if sd["base"] is not None and name in need else None
-            dtype = torch.uint8 if name == "counts" else torch.float32
-            setattr(self, name, None if t is None else t.detach().to(dtype).clone().contiguous())
+        self._load_tensors(sd, need if sd["base"] is not None else ())   # (what the rule does not keep is dropped)
         self.last_trim_stats = None

@@ -28,19 +28,19 @@ import torch
 
 from mafed_amd import ops
 from mafed_amd.methods.base import CLStrategy
-from mafed_amd.methods.flat import FlatDict, behind_optimizer, require_native
+from mafed_amd.methods.flat import FlatPlugin, behind_optimizer
 
 MAX_TASKS = 255   # the owner map is a byte and a prune in task t writes t + 1
 
 
-class PackNet(CLStrategy):
+class PackNet(FlatPlugin, CLStrategy):
     """``PackNet(prune_fraction=0.5, prunable=None)``.  ``prune_fraction`` of a task's free weights goes to the next task at each prune
     (0.5 is the lowest setting of the paper; it is untuned for this model).  ``prunable``: callable(name) -> bool choosing the tensors
     that are pruned; default: the four weight matrices of every decoder layer."""
     # grads_only_through_model is False for the class: the mask pass rewrites the gradient buffer behind the model's backward (handed-over
     # clip norm).  An instance makes the promise while it launches nothing -- task 0 before its prune -- so that Trainer, which reads it
     # step by step, lets the sweep collect the clip norm as it does for Naive: the run is then Naive's whatever the clip does.
-    single_process_only = True         # under a reducer the hook runs before the reduced gradients exist (Trainer refuses one)
+    _STATE = (("owner", torch.uint8), ("anchor", torch.float32))
 
     def __init__(self, prune_fraction=0.5, prunable: Optional[Callable[[str], bool]] = None, **kwargs):
         super().__init__(**{k: v for k, v in kwargs.items() if k in ("reg_lambda", "mask", "scaler", "opts")})
@@ -52,30 +52,16 @@ class PackNet(CLStrategy):
         self.anchor: Optional[torch.Tensor] = None    # fp32: what a held element is put back to; None until the first prune
         self.pruned = False                           # the current task has been pruned
         self.last_prune_stats: Optional[torch.Tensor] = None   # device int64 [tensors, 4] = {m, k, pruned, pattern of tau} of the last prune
-        self._sumsq = None
-        self._segments = self._segment_names = self._select = None
         self._pending = False                         # a mask pass whose hold pass has not run yet
-        self._in_view = False
         self._promise()
 
     # ---- buffers -----------------------------------------------------------------------------------------------------------
-    def _native(self, model):
-        require_native(model, "PackNet", "its passes run on the flat buffers (model.flat_params / model.flat_grads)")
-        return model.flat_params
-
     def _ensure(self, model) -> None:
         """Allocate once: the owner map and the mask pass's partials."""
-        p = self._native(model)
+        p = self._place_state(model)
         if self.owner is None:
             self.owner = torch.zeros(p.numel(), dtype=torch.uint8, device=p.device)
-        if self.owner.shape != p.shape or (self.anchor is not None and self.anchor.shape != p.shape):
-            raise ValueError("PackNet's state was built for another model (%d elements, this one has %d)" % (self.owner.numel(), p.numel()))
-        if self.owner.device != p.device:   # a checkpoint loaded on another device
-            self.owner = self.owner.to(p.device)
-        if self.anchor is not None and self.anchor.device != p.device:
-            self.anchor = self.anchor.to(p.device)
-        if self._sumsq is None or self._sumsq.device != p.device:
-            self._sumsq = torch.zeros(ops.packnet_blocks(p.numel()), dtype=torch.float32, device=p.device)
+        self._clip_partials(p, ops.packnet_blocks)
 
     def prunable_names(self, model) -> List[str]:
         """The tensors a prune selects in, in the order of the flat layout."""
@@ -84,30 +70,6 @@ class PackNet(CLStrategy):
             return [name for name in model._offsets if self.prunable(name)]
         ranges = [model.layer_matrix_range(i) for i in range(model.config.num_hidden_layers)]
         return [name for name, (o, n, _) in model._offsets.items() if any(lo <= o and o + n <= hi for lo, hi in ranges)]
-
-    def _tables(self, model):
-        """The device table of segments {offset, length} and the selection's workspaces, built at the first prune."""
-        names = self.prunable_names(model)
-        dev = model.flat_params.device
-        if self._segment_names != names or self._segments.device != dev:
-            rows = [[model._offsets[name][0], model._offsets[name][1]] for name in names]
-            if any(n >= 2 ** 32 for _, n in rows):
-                raise ValueError("PackNet prunes tensors of fewer than 2^32 elements")
-            self._segments = torch.tensor(rows, dtype=torch.int64, device=dev).reshape(len(rows), 2)
-            self._segment_names = names
-            s = len(rows)
-            self._select = (ops.packnet_select_blocks(max([n for _, n in rows], default=0), s),
-                            torch.zeros(s, 4, dtype=torch.int64, device=dev), torch.zeros(s, ops.PACKNET_BINS, dtype=torch.int32, device=dev))
-        return self._segments, self._select
-
-    def named(self, model, which: str = "owner") -> FlatDict:
-        """name -> view of ``owner`` / ``anchor``, like EWC's ``fisher[0]``."""
-        if which not in ("owner", "anchor"):
-            raise KeyError(which)
-        self._ensure(model)
-        if getattr(self, which) is None:
-            raise RuntimeError("PackNet has no anchor before the first prune")
-        return FlatDict(model, getattr(self, which))
 
     # ---- between tasks -----------------------------------------------------------------------------------------------------
     def prune(self, model) -> None:
@@ -124,7 +86,7 @@ class PackNet(CLStrategy):
         behind_optimizer(model)
         if self.anchor is None:
             self.anchor = torch.zeros_like(model.flat_params)   # (read only where owner != task_id: written by this prune or by update)
-        segments, (blocks, state, hist) = self._tables(model)
+        segments, (blocks, state, hist) = self._segment_tables(model, self.prunable_names(model), ops.packnet_select_blocks)   # (built here first)
         self.last_prune_stats = ops.packnet_prune_(model.flat_params, model.flat_shadow, self.owner, self.anchor, segments, blocks, self.task_id,
                                                    self.prune_fraction, state=state, hist=hist)
         self.pruned = True
@@ -155,9 +117,6 @@ class PackNet(CLStrategy):
         self._promise()
 
     # ---- inside a step -----------------------------------------------------------------------------------------------------
-    def compute_loss(self, model, loss, **kwargs):
-        return loss
-
     def _all_trainable(self) -> bool:
         return self.task_id == 0 and not self.pruned
 
@@ -172,8 +131,8 @@ class PackNet(CLStrategy):
         if self._all_trainable():
             return
         self._ensure(model)
-        ops.packnet_mask_grad_(model.flat_grads, self.owner, self.task_id, self._sumsq)
-        model.final_grad_sumsq = self._sumsq   # FlatAdamW.clip_grad_norm_ folds these instead of reading the buffer again
+        ops.packnet_mask_grad_(model.flat_grads, self.owner, self.task_id, self._partials)
+        self._hand_over(model)
         self._pending = True
 
     def update_after_step(self, model=None, **kwargs) -> None:
@@ -193,39 +152,27 @@ class PackNet(CLStrategy):
         owned by a task <= k is frozen since).  ``0 <= k <=`` the number of finished tasks; that number itself gives the current weights.
         On exit the parameters and the shadow are put back bit for bit."""
         p = self._native(model)
-        if self._in_view:
-            raise RuntimeError("PackNet: task_view does not nest")
-        if not 0 <= int(k) <= self.task_id:
-            raise ValueError("task_view: k = %r outside 0 .. %d (the tasks finished so far)" % (k, self.task_id))
-        if self._pending:
-            self.update_after_step(model=model)
-        behind_optimizer(model)
-        saved = p.detach().clone()
-        self._in_view = True
-        try:
+
+        def prepare():
+            if not 0 <= int(k) <= self.task_id:
+                raise ValueError("task_view: k = %r outside 0 .. %d (the tasks finished so far)" % (k, self.task_id))
+            if self._pending:
+                self.update_after_step(model=model)
+
+        def apply():
             if self.owner is not None:
                 self._ensure(model)
                 ops.packnet_view_(p, model.flat_shadow, self.owner, int(k))
+        with self._view(model, "PackNet: task_view does not nest", apply, prepare):
             yield model
-        finally:
-            self._in_view = False
-            with torch.no_grad():
-                p.copy_(saved)
-            model.sync_shadow()
 
     # ---- checkpoints between tasks -----------------------------------------------------------------------------------------
     def state_dict(self):
-        return {"owner": self.owner, "anchor": self.anchor, "task_id": self.task_id, "pruned": self.pruned}
+        return {**self._state_tensors(), "task_id": self.task_id, "pruned": self.pruned}
 
     def load_state_dict(self, sd) -> None:
-        missing = [k for k in ("owner", "anchor", "task_id", "pruned") if k not in sd]
-        if missing:
-            raise ValueError("PackNet state without %s" % missing)
-        if sd["owner"] is None:
-            self.owner = self.anchor = None
-        else:
-            self.owner = sd["owner"].detach().to(torch.uint8).clone().contiguous()
-            self.anchor = None if sd["anchor"] is None else sd["anchor"].detach().to(torch.float32).clone().contiguous()
+        self._require_keys(sd, ("task_id", "pruned"))
+        self._load_tensors(sd, () if sd["owner"] is None else ("owner", "anchor"))   # (the anchor alone may be None: before the first prune)
         self._pending = False
         self.task_id, self.pruned = int(sd["task_id"]), bool(sd["pruned"])
         self._promise()

@@ -24,14 +24,13 @@ import torch
 
 from mafed_amd import ops
 from mafed_amd.methods.base import CLStrategy
-from mafed_amd.methods.flat import FlatDict, behind_optimizer, require_native
+from mafed_amd.methods.flat import FlatPlugin, behind_optimizer
 
 
-class SI(CLStrategy):
+class SI(FlatPlugin, CLStrategy):
     """``SI(reg_lambda=1.0, xi=1e-3)``.  ``xi`` damps the division where a parameter barely moved; 1e-3 is the paper's CIFAR value and has
     not been tuned for this model."""
-    # grads_only_through_model stays False: pass A rewrites the gradient buffer behind the model's backward (handed-over clip norm)
-    single_process_only = True         # under a reducer the hook runs before the reduced gradients exist (Trainer refuses one)
+    _STATE = (("omega", torch.float32), ("anchor", torch.float32), ("small_omega", torch.float32))
 
     def __init__(self, reg_lambda=1.0, xi=1e-3, **kwargs):
         super().__init__(reg_lambda, **{k: v for k, v in kwargs.items() if k in ("mask", "scaler", "opts")})
@@ -41,61 +40,40 @@ class SI(CLStrategy):
         self.small_omega: Optional[torch.Tensor] = None   # w: the running path integral of the task being learnt
         self.omega: Optional[torch.Tensor] = None         # consolidated importance
         self.anchor: Optional[torch.Tensor] = None        # parameters at the last consolidation (task 0: at the first pass A)
-        self._stash_g = self._stash_p = self._sumsq = self._pen = None
+        self._stash_g = self._stash_p = self._pen = None
         self.last_penalty: Optional[torch.Tensor] = None  # device scalar c sum Omega (p - p*)^2 of the last pass A; None until the first
         self._pending = False                             # a pass A whose pass B has not run yet
 
     # ---- buffers -----------------------------------------------------------------------------------------------------------
-    def _native(self, model):
-        require_native(model, "SI", "its passes run on the flat buffers (model.flat_params / model.flat_grads)")
-        return model.flat_params
-
     def _ensure(self, model) -> None:
         """Allocate once: the state at the first pass A (or update), the stash and the partials beside it."""
-        p = self._native(model)
+        p = self._place_state(model)
         if self.small_omega is None:
             self.small_omega, self.omega, self.anchor = torch.zeros_like(p), torch.zeros_like(p), p.detach().clone()
-        if self.small_omega.shape != p.shape:
-            raise ValueError("SI's state was built for another model (%d elements, this one has %d)" % (self.small_omega.numel(), p.numel()))
-        if self.small_omega.device != p.device:   # a checkpoint loaded on another device
-            self.small_omega, self.omega, self.anchor = (t.to(p.device) for t in (self.small_omega, self.omega, self.anchor))
         if self._stash_g is None:
             self._stash_g, self._stash_p = torch.empty_like(p), torch.empty_like(p)
-            nb = ops.si_blocks(p.numel())
-            self._sumsq, self._pen = torch.zeros(nb, dtype=torch.float32, device=p.device), torch.zeros(nb, dtype=torch.float32, device=p.device)
+            self._pen = torch.zeros_like(self._clip_partials(p, ops.si_blocks))
             self.last_penalty = torch.zeros(1, dtype=torch.float32, device=p.device)[0]
-
-    def named(self, model, which: str = "omega") -> FlatDict:
-        """name -> view of ``omega`` / ``small_omega`` / ``anchor``, like EWC's ``fisher[0]``."""
-        if which not in ("omega", "small_omega", "anchor"):
-            raise KeyError(which)
-        self._ensure(model)
-        return FlatDict(model, getattr(self, which))
-
-    _behind_optimizer = staticmethod(behind_optimizer)
 
     # ---- between tasks -----------------------------------------------------------------------------------------------------
     def update(self, model, **kwargs) -> None:
         self._ensure(model)
         if self._pending:
             self.update_after_step(model=model)
-        self._behind_optimizer(model)
+        behind_optimizer(model)
         ops.si_consolidate_(model.flat_params, self.anchor, self.small_omega, self.omega, self.xi)
         self.task_id += 1
 
     # ---- inside a step -----------------------------------------------------------------------------------------------------
-    def compute_loss(self, model, loss, **kwargs):
-        return loss
-
     def update_after_backward(self, model=None, **kwargs) -> None:
         """Pass A.  Trainer calls this only on the micro-batch that closes a window."""
         self._ensure(model)
         reg = self.task_id > 0
         ops.si_stash(model.flat_grads, model.flat_params, self.omega if reg else None, self.anchor if reg else None, 2.0 * float(self.reg_lambda),
-                     self._stash_g, self._stash_p, self._sumsq, self._pen)
+                     self._stash_g, self._stash_p, self._partials, self._pen)
         if reg:
             ops.si_penalty_finish(self._pen, float(self.reg_lambda), self.last_penalty)
-        model.final_grad_sumsq = self._sumsq   # FlatAdamW.clip_grad_norm_ folds these instead of reading the buffer again
+        self._hand_over(model)
         self._pending = True
 
     def update_after_step(self, model=None, **kwargs) -> None:
@@ -105,20 +83,16 @@ class SI(CLStrategy):
         if not self._pending:
             return
         self._pending = False
-        self._behind_optimizer(model)
+        behind_optimizer(model)
         ops.si_accumulate_(self._stash_g, self._stash_p, model.flat_params, self.small_omega)
 
     # ---- checkpoints between tasks -----------------------------------------------------------------------------------------
     def state_dict(self):
-        return {"omega": self.omega, "anchor": self.anchor, "small_omega": self.small_omega, "task_id": self.task_id}
+        return {**self._state_tensors(), "task_id": self.task_id}
 
     def load_state_dict(self, sd) -> None:
-        missing = [k for k in ("omega", "anchor", "small_omega", "task_id") if k not in sd]
-        if missing:
-            raise ValueError("SI state without %s" % missing)
-        if any(sd[k] is None for k in ("omega", "anchor", "small_omega")):
-            self.small_omega = self.omega = self.anchor = None
-        else:
-            self.omega, self.anchor, self.small_omega = (sd[k].detach().to(torch.float32).clone().contiguous() for k in ("omega", "anchor", "small_omega"))
+        self._require_keys(sd, ("task_id",))
+        names = ("omega", "anchor", "small_omega")
+        self._load_tensors(sd, () if any(sd[k] is None for k in names) else names)   # without one of them there is no state
         self._pending = False
         self.task_id = int(sd["task_id"])
