@@ -17,32 +17,16 @@ There is no speed gate: the table is reported as measured.
 import os
 import statistics
 import sys
-import time
 import types
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
+from benchlib import run_steps, samples, step_conf, timed, to_dev  # noqa: E402
 from mafed_amd import AGEM, Naive, Trainer, VLPythiaConfig, VLPythiaForCausalLM, ops  # noqa: E402
 
 REPS = 15
 dev = "cuda"
-
-
-def timed(fn, reps=REPS, warmup=3):
-    """[us per call] from device events around each call."""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1) * 1e3)
-    return out
 
 
 def kernel_table(n):
@@ -68,41 +52,24 @@ def kernel_table(n):
     ]
     print(f"{'pass':>26s} {'B/param':>8s} {'median us':>10s} {'min':>8s} {'max':>8s} {'MB':>8s} {'TB/s':>6s}")
     for name, bpp, fn in rows:
-        us = timed(fn)
+        us = timed(fn, REPS)
         med = statistics.median(us)
         print(f"{name:>26s} {bpp:8d} {med:10.1f} {min(us):8.1f} {max(us):8.1f} {n * bpp / 1e6:8.1f} {n * bpp / med / 1e6:6.2f}", flush=True)
 
 
 def step_times(method_name, cfg, B, P, T, steps=12, warmup=4):
     student = VLPythiaForCausalLM(cfg, compute_dtype=torch.bfloat16, device=dev, seed=1234)
-    gcpu = torch.Generator().manual_seed(1235)
     n = 8 * B
-    ids = torch.randint(1, cfg.vocab_size, (n, T), generator=gcpu)
-    labels = torch.full((n, T), -100, dtype=torch.int64)
-    labels[:, -4:] = ids[:, -4:]
-    feats = torch.randn(n, P, cfg.vision_hidden_size, generator=gcpu).to(torch.bfloat16)
-    samples = {"input_ids": ids, "attention_mask": torch.ones(n, T, dtype=torch.int64), "labels": labels, "patch_embeddings": feats}
+    mem = samples(cfg, n, P, T, torch.Generator().manual_seed(1235))
     opts = types.SimpleNamespace(tasks=["t0", "t1"], batch_size=B, seed=1236, pin_mem=False, accumulate_grad_batches=1)
     if method_name == "agem":
         method = AGEM(opts, memory_size=n, model_type="vlpythia")
-        method.update(samples, model=student)
+        method.update(mem, model=student)
     else:
         method = Naive()
-    conf = types.SimpleNamespace(accumulate_grad_batches=1, replay_interval=1, grad_norm=2.0, learning_rate=5e-5, betas=(0.9, 0.98),
-                                 weight_decay=0.01, optim="adamw", warmup_perc=0.1)
-    tr = Trainer(student, method, conf, task_id=1, n_batches_per_epoch=1000, pipeline_optimizer=True)
-    sel = torch.arange(B)
-    batch = {k: v[sel].to(dev) for k, v in samples.items()}
-    batch["max_label_rows"] = 4   # the loader's hint: the row-sparse head (256 of 1024 rows), as the memory batches carry it
-    ts, rec = [], None
-    for i in range(warmup + steps):
-        t0 = time.perf_counter()
-        rec = tr.step(dict(batch), i)
-        torch.cuda.synchronize()
-        if i >= warmup:
-            ts.append((time.perf_counter() - t0) * 1e3)
-    tr.join()
-    torch.cuda.synchronize()
+    tr = Trainer(student, method, step_conf("warmup_perc"), task_id=1, n_batches_per_epoch=1000, pipeline_optimizer=True)
+    batch = to_dev({k: v[:B] for k, v in mem.items()}, sparse_head=True)   # the row-sparse head, as the memory batches carry it
+    ts, _, rec = run_steps(tr, batch, steps, warmup)
     parts = ""
     if method_name == "agem":
         parts = (f"  (last step: dot {float(method.last_dot):.3e}, rsq {float(method.last_ref_sq):.3e}, alpha {float(method.last_alpha):.3e}, "

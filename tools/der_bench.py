@@ -21,18 +21,14 @@ reported as measured.
     python tools/der_bench.py --parent-lib ../parent/mafed_amd/libmafed_hip.so [--head SHA] > profiles/der_step.txt
     python tools/der_bench.py --resources        # no GPU: registers, scratch and LDS of the kernels, from the hipcc gfx950 build
 """
-import datetime
 import os
-import re
 import statistics
-import subprocess
 import sys
-import tempfile
 import time
 import types
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from benchlib import header, parent_lib_ab, resources, run_steps, samples, step_conf, to_dev  # noqa: E402
 
 V = 50304
 REPS = 9
@@ -40,28 +36,8 @@ SETS = 3
 N_MEM, A = 4000, 4
 dev = "cuda"
 
-
-def resources():
-    """VGPRs, SGPRs, scratch, LDS and occupancy of every kernel in der.hip, beside those of ce.hip and kd.hip, as hipcc reports them."""
-    from mafed_amd import build
-    print("# hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage")
-    print(f"{'kernel':>52s} {'VGPRs':>6s} {'SGPRs':>6s} {'scratch B/lane':>15s} {'LDS B/block':>12s} {'waves/SIMD':>11s}")
-    for src in ("der.hip", "ce.hip", "kd.hip"):
-        with tempfile.TemporaryDirectory() as tmp:
-            r = subprocess.run([build._hipcc()] + build.FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(build.CSRC, src), "-o",
-                                os.path.join(tmp, "o.o")], capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(r.stderr[-2000:])
-        field = lambda block, key: re.search(key + r": (\d+)", block).group(1)
-        for block in r.stderr.split("Function Name: ")[1:]:
-            name = subprocess.run(["c++filt", block.split()[0]], capture_output=True, text=True).stdout.strip() or block.split()[0]
-            name = re.sub(r"\(.*", "", name).replace("void ", "").replace("mafed::", "").replace("unsigned short", "bf16")
-            cols = [field(block, key) for key in (" VGPRs", "TotalSGPRs", r"ScratchSize \[bytes/lane\]", r"LDS Size \[bytes/block\]", r"Occupancy \[waves/SIMD\]")]
-            print(f"{src + ': ' + name:>52s} {cols[0]:>6s} {cols[1]:>6s} {cols[2]:>15s} {cols[3]:>12s} {cols[4]:>11s}")
-
-
 if "--resources" in sys.argv[1:]:
-    resources()
+    resources(("der.hip", "ce.hip", "kd.hip"), 52, renames=(("unsigned short", "bf16"),))   # der.hip beside the kernels it is measured against
     sys.exit(0)
 
 import torch  # noqa: E402
@@ -109,51 +85,30 @@ def kernel_times(rows, store):
     return out, B * T
 
 
-def _samples(cfg, n, P, T, seed):
-    gcpu = torch.Generator().manual_seed(seed)
-    ids = torch.randint(1, cfg.vocab_size, (n, T), generator=gcpu)
-    labels = torch.full((n, T), -100, dtype=torch.int64)
-    labels[:, -4:] = ids[:, -4:]
-    feats = torch.randn(n, P, cfg.vision_hidden_size, generator=gcpu).to(torch.bfloat16)
-    return {"input_ids": ids, "attention_mask": torch.ones(n, T, dtype=torch.int64), "labels": labels, "patch_embeddings": feats}
-
-
 def step_times(method_name, cfg, B, P, T, steps=12, warmup=4):
     from mafed_amd import DER, ER
     student = VLPythiaForCausalLM(cfg, compute_dtype=torch.bfloat16, device=dev, seed=1234)
     n = 8 * B
-    samples = _samples(cfg, n, P, T, 1235)
+    mem = samples(cfg, n, P, T, torch.Generator().manual_seed(1235))
     opts = types.SimpleNamespace(tasks=["t0", "t1"], batch_size=B, seed=1236, pin_mem=False, accumulate_grad_batches=1)
     if method_name == "naive":
         method = CLMethod["naive"]()
     else:
         method = (DER if method_name == "der" else ER)(opts, memory_size=n, model_type="vlpythia")
-        method.update(samples, model=student)
+        method.update(mem, model=student)
         gen = torch.Generator(device=dev).manual_seed(1237)   # the student has moved away from the model that recorded the store
         with torch.no_grad():
             student.flat_params.add_(torch.randn(student.flat_params.shape, generator=gen, device=dev) * 1e-3)
         student._shadow_dirty = True
-    conf = types.SimpleNamespace(accumulate_grad_batches=1, replay_interval=1, grad_norm=2.0, learning_rate=5e-5, betas=(0.9, 0.98),
-                                 weight_decay=0.01, optim="adamw", warmup_perc=0.1)
-    tr = Trainer(student, method, conf, task_id=0 if method_name == "naive" else 1, n_batches_per_epoch=1000, pipeline_optimizer=True)
-    batch = {k: v[:B].to(dev) for k, v in samples.items()}
-    batch["max_label_rows"] = 4   # the loader's hint: the row-sparse head (256 of 1024 rows)
-    ts, rec = [], None
-    for i in range(warmup + steps):
-        t0 = time.perf_counter()
-        rec = tr.step(dict(batch), i)
-        torch.cuda.synchronize()
-        if i >= warmup:
-            ts.append((time.perf_counter() - t0) * 1e3)
-    tr.join()
-    torch.cuda.synchronize()
+    tr = Trainer(student, method, step_conf("warmup_perc"), task_id=0 if method_name == "naive" else 1, n_batches_per_epoch=1000, pipeline_optimizer=True)
+    ts, _, rec = run_steps(tr, to_dev({k: v[:B] for k, v in mem.items()}, sparse_head=True), steps, warmup)
     parts = f"  (last step: CE {float(method.last_ce):.4f}, MSE {float(method.last_mse):.3e})" if method_name == "der" else ""
     return ts, rec["branch"], float(rec["loss"]), parts
 
 
 def recording_time(cfg, B, P, T, n=1000):
     student = VLPythiaForCausalLM(cfg, compute_dtype=torch.bfloat16, device=dev, seed=1234)
-    data = {k: v.to(dev) for k, v in _samples(cfg, n, P, T, 1238).items()}
+    data = to_dev(samples(cfg, n, P, T, torch.Generator().manual_seed(1238)))
 
     def record():
         parts = [student.answer_logits(data["patch_embeddings"][lo:lo + B], data["input_ids"][lo:lo + B], data["attention_mask"][lo:lo + B],
@@ -182,10 +137,7 @@ def main():
     assert torch.cuda.is_available(), "der_bench needs a GPU"
     if "--naive-only" in sys.argv[1:]:
         return naive_only()
-    # (``--head SHA``: for a tree that was copied to the GPU box without its .git)
-    head = sys.argv[sys.argv.index("--head") + 1] if "--head" in sys.argv[1:] else None
-    head = head or subprocess.run(["git", "rev-parse", "HEAD"], cwd=ROOT, capture_output=True, text=True).stdout.strip() or "no git checkout"
-    print(f"# python {' '.join(['tools/der_bench.py'] + sys.argv[1:])}; HEAD {head}; {datetime.datetime.now().isoformat(timespec='seconds')}")
+    print(header(__file__, sys.argv[1:]))
     print(f"# {torch.cuda.get_device_name(0)}; bf16 logits [rows, {V}], store [{N_MEM}, {A}, {V}] bf16; kernel time = the dispatch's own execution time, us, "
           f"median (min .. max) of {REPS}")
     print(f"{'rows':>5s} {'kernel':>11s} {'median us':>10s} {'min':>8s} {'max':>8s} {'MB':>8s} {'TB/s':>6s} {'vs ce_kd kernel':>16s}")
@@ -211,17 +163,8 @@ def main():
           f"{statistics.median(ts):.1f} ({min(ts):.1f} .. {max(ts):.1f}) ms, 3 passes after 1")
     torch.cuda.empty_cache()
     if "--parent-lib" in sys.argv[1:]:
-        parent = os.path.abspath(sys.argv[sys.argv.index("--parent-lib") + 1])
-        assert os.path.exists(parent), parent
-        print("# naive, the parent commit's library against this tree's, alternating, a fresh process each")
-        base = {k: v for k, v in os.environ.items() if k not in ("MAFED_HIP_LIB", "MAFED_HIP_LIB_LOOSE")}
-        for rnd in (1, 2, 3):
-            for who, env in (("parent library", dict(base, MAFED_HIP_LIB=parent, MAFED_HIP_LIB_LOOSE="1")), ("this tree's library", base)):
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--naive-only"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
-                if r.returncode != 0:
-                    print(f"## {who}, round {rnd}: the run ended with status {r.returncode}", flush=True)
-                    return 1
-                print(f"## {who}, round {rnd}\n{r.stdout.rstrip()}", flush=True)
+        return parent_lib_ab(__file__, sys.argv[sys.argv.index("--parent-lib") + 1],
+                             emit=lambda who, rnd, out: print(f"## {who}, round {rnd}\n{out.rstrip()}", flush=True))
     return 0
 
 

@@ -15,62 +15,24 @@ There is no speed gate: the table is reported as measured.
     python tools/gem_bench.py --parent-lib ../parent/mafed_amd/libmafed_hip.so [--head SHA] > profiles/gem_step.txt
     python tools/gem_bench.py --resources        # no GPU: registers, scratch and LDS of the kernels, from the hipcc gfx950 build
 """
-import datetime
 import os
-import re
 import statistics
-import subprocess
 import sys
-import tempfile
-import time
 import types
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from benchlib import header, parent_lib_ab, resources, run_steps, samples, step_conf, timed, to_dev  # noqa: E402
 
 REPS = 15
 dev = "cuda"
 
-
-def resources():
-    """VGPRs, SGPRs, scratch, LDS and occupancy of every kernel in gem.hip as hipcc reports them for gfx950."""
-    from mafed_amd import build
-    print("# hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage")
-    print(f"{'kernel':>36s} {'VGPRs':>6s} {'SGPRs':>6s} {'scratch B/lane':>15s} {'LDS B/block':>12s} {'waves/SIMD':>11s}")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run([build._hipcc()] + build.FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(build.CSRC, "gem.hip"), "-o",
-                            os.path.join(tmp, "o.o")], capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(r.stderr[-2000:])
-    field = lambda block, key: re.search(key + r": (\d+)", block).group(1)
-    for block in r.stderr.split("Function Name: ")[1:]:
-        name = subprocess.run(["c++filt", block.split()[0]], capture_output=True, text=True).stdout.strip() or block.split()[0]
-        name = re.sub(r"\(.*", "", name).replace("void ", "").replace("mafed::", "")
-        cols = [field(block, key) for key in (" VGPRs", "TotalSGPRs", r"ScratchSize \[bytes/lane\]", r"LDS Size \[bytes/block\]", r"Occupancy \[waves/SIMD\]")]
-        print(f"{name:>36s} {cols[0]:>6s} {cols[1]:>6s} {cols[2]:>15s} {cols[3]:>12s} {cols[4]:>11s}")
-
-
 if "--resources" in sys.argv[1:]:
-    resources()
+    resources(("gem.hip",), 36)
     sys.exit(0)
 
 import torch  # noqa: E402
 
 from mafed_amd import AGEM, GEM, Naive, Trainer, VLPythiaConfig, VLPythiaForCausalLM, ops  # noqa: E402
-
-
-def timed(fn, reps=REPS, warmup=3):
-    """[us per call] from device events around each call."""
-    out = []
-    for k in range(warmup + reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        if k >= warmup:
-            out.append(e0.elapsed_time(e1) * 1e3)
-    return out
 
 
 def kernel_table(n):
@@ -109,7 +71,7 @@ def kernel_table(n):
     print(f"{'pass':>34s} {'B/param':>8s} {'median us':>10s} {'min':>8s} {'max':>8s} {'MB':>8s} {'TB/s':>6s}   ratio to the sibling")
     rate = {}
     for name, bpp, sibling, fn in rows:
-        us = timed(fn)
+        us = timed(fn, REPS)
         med = statistics.median(us)
         rate[name] = n * bpp / med / 1e6
         beside = f"   {rate[name] / rate[sibling]:.2f} of {sibling}" if sibling else ""
@@ -122,14 +84,7 @@ def step_times(method_name, cfg, B, P, T, steps=12, warmup=4):
     gcpu = torch.Generator().manual_seed(1235)
     K = int(method_name[3:]) if method_name.startswith("gem") else 1
     n = 8 * B
-
-    def samples():
-        ids = torch.randint(1, cfg.vocab_size, (n, T), generator=gcpu)
-        labels = torch.full((n, T), -100, dtype=torch.int64)
-        labels[:, -4:] = ids[:, -4:]
-        feats = torch.randn(n, P, cfg.vision_hidden_size, generator=gcpu).to(torch.bfloat16)
-        return {"input_ids": ids, "attention_mask": torch.ones(n, T, dtype=torch.int64), "labels": labels, "patch_embeddings": feats}
-    first = samples()
+    first = samples(cfg, n, P, T, gcpu)
     opts = types.SimpleNamespace(tasks=[f"t{i}" for i in range(K + 1)], batch_size=B, seed=1236, pin_mem=False, accumulate_grad_batches=1)
     if method_name == "agem":
         method = AGEM(opts, memory_size=n, model_type="vlpythia")
@@ -137,24 +92,12 @@ def step_times(method_name, cfg, B, P, T, steps=12, warmup=4):
     elif method_name.startswith("gem"):
         method = GEM(opts, memory_size=n * K, model_type="vlpythia")
         for k in range(K):
-            method.update(first if k == 0 else samples(), model=student)
+            method.update(first if k == 0 else samples(cfg, n, P, T, gcpu), model=student)   # each task's memory draws on from the one generator
     else:
         method = Naive()
-    conf = types.SimpleNamespace(accumulate_grad_batches=1, replay_interval=1, grad_norm=2.0, learning_rate=5e-5, betas=(0.9, 0.98),
-                                 weight_decay=0.01, optim="adamw", warmup_perc=0.1)
-    tr = Trainer(student, method, conf, task_id=K if method_name != "naive" else 1, n_batches_per_epoch=1000, pipeline_optimizer=True)
-    sel = torch.arange(B)
-    batch = {k: v[sel].to(dev) for k, v in first.items()}
-    batch["max_label_rows"] = 4   # the loader's hint: the row-sparse head (256 of 1024 rows), as the memory batches carry it
-    ts, rec = [], None
-    for i in range(warmup + steps):
-        t0 = time.perf_counter()
-        rec = tr.step(dict(batch), i)
-        torch.cuda.synchronize()
-        if i >= warmup:
-            ts.append((time.perf_counter() - t0) * 1e3)
-    tr.join()
-    torch.cuda.synchronize()
+    tr = Trainer(student, method, step_conf("warmup_perc"), task_id=K if method_name != "naive" else 1, n_batches_per_epoch=1000, pipeline_optimizer=True)
+    batch = to_dev({k: v[:B] for k, v in first.items()}, sparse_head=True)   # the row-sparse head, as the memory batches carry it
+    ts, _, rec = run_steps(tr, batch, steps, warmup)
     parts = ""
     if method_name == "agem":
         parts = f"  (last step: dot {float(method.last_dot):.3e}, alpha {float(method.last_alpha):.3e}, projected {int(method.last_projected)})"
@@ -179,10 +122,7 @@ def main():
     if "--naive-only" in sys.argv[1:]:
         _step_row("naive", cfg, B, P, T)
         return 0
-    # (``--head SHA``: for a tree that was copied to the GPU box without its .git)
-    head = sys.argv[sys.argv.index("--head") + 1] if "--head" in sys.argv[1:] else None
-    head = head or subprocess.run(["git", "rev-parse", "HEAD"], cwd=ROOT, capture_output=True, text=True).stdout.strip() or "no git checkout"
-    print(f"# python {' '.join(['tools/gem_bench.py'] + sys.argv[1:])}; HEAD {head}; {datetime.datetime.now().isoformat(timespec='seconds')}")
+    print(header(__file__, sys.argv[1:]))
     print(f"# {torch.cuda.get_device_name(0)}; VLPythia-410M bf16 step, B = {B}, {P} + {T} tokens, row-sparse head, pipelined optimiser; wall ms per Trainer.step, "
           "median (min .. max) of 12 after 4")
     n_flat = 0
@@ -191,17 +131,8 @@ def main():
     print(f"# flat fp32 buffers of {n_flat} elements ({n_flat * 4 / 1e9:.2f} GB each); device-event time around each call, us, median (min .. max) of {REPS}")
     kernel_table(n_flat)
     if "--parent-lib" in sys.argv[1:]:
-        parent = os.path.abspath(sys.argv[sys.argv.index("--parent-lib") + 1])
-        assert os.path.exists(parent), parent
-        print("# naive, the parent commit's library against this tree's, alternating, a fresh process each")
-        env0 = {k: v for k, v in os.environ.items() if k not in ("MAFED_HIP_LIB", "MAFED_HIP_LIB_LOOSE")}
-        for rnd in (1, 2, 3):
-            for who, env in (("parent library", dict(env0, MAFED_HIP_LIB=parent, MAFED_HIP_LIB_LOOSE="1")), ("this tree's library", env0)):
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--naive-only"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
-                if r.returncode != 0:
-                    print(f"## {who}, round {rnd}: the run ended with status {r.returncode}", flush=True)
-                    return 1
-                print(f"{who + ', round %d' % rnd:>28s}:{r.stdout.strip().split(':', 1)[1]}", flush=True)
+        return parent_lib_ab(__file__, sys.argv[sys.argv.index("--parent-lib") + 1],
+                             emit=lambda who, rnd, out: print(f"{who + ', round %d' % rnd:>28s}:{out.strip().split(':', 1)[1]}", flush=True))
     return 0
 
 

@@ -16,12 +16,12 @@ forward, 1.5x backward) plus the spread between the repeats.  There is no speed 
 import os
 import statistics
 import sys
-import time
 import types
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
+from benchlib import run_steps, samples, step_conf  # noqa: E402
 from mafed_amd import CLMethod, Trainer, VLPythiaConfig, VLPythiaForCausalLM, ops  # noqa: E402
 from mafed_amd.methods import HBMReplayBuffer  # noqa: E402
 from mafed_amd.profiler import KernelProfile  # noqa: E402
@@ -67,15 +67,9 @@ def kernel_times(rows):
 
 def step_times(method_name, cfg, B, P, T, steps=12, warmup=4):
     student = VLPythiaForCausalLM(cfg, compute_dtype=torch.bfloat16, device=dev, seed=1234)
-    gcpu = torch.Generator().manual_seed(1235)
     n = 8 * B
-    ids = torch.randint(1, cfg.vocab_size, (n, T), generator=gcpu)
-    labels = torch.full((n, T), -100, dtype=torch.int64)
-    labels[:, -4:] = ids[:, -4:]
-    feats = torch.randn(n, P, cfg.vision_hidden_size, generator=gcpu).to(torch.bfloat16)
-    samples = {"input_ids": ids, "attention_mask": torch.ones(n, T, dtype=torch.int64), "labels": labels, "patch_embeddings": feats}
     mem = HBMReplayBuffer(B, torch.device(dev), seed=9)
-    mem.add(samples)
+    mem.add(samples(cfg, n, P, T, torch.Generator().manual_seed(1235)))
     opts = types.SimpleNamespace(tasks=["t0", "t1"], batch_size=B, seed=1236, pin_mem=False, accumulate_grad_batches=1)
     gen = torch.Generator(device=dev).manual_seed(1237)
     if method_name == "featdistill":
@@ -92,19 +86,9 @@ def step_times(method_name, cfg, B, P, T, steps=12, warmup=4):
     if getattr(method, "past_model", None) is not None:   # the student has moved away from the teacher
         method.past_model.flat_params.add_(torch.randn(method.past_model.flat_params.shape, generator=gen, device=dev) * 1e-3)
         method.past_model._shadow_dirty = True
-    conf = types.SimpleNamespace(accumulate_grad_batches=1, replay_interval=1, grad_norm=2.0, learning_rate=5e-5, betas=(0.9, 0.98),
-                                 weight_decay=0.01, optim="adamw", warmup_perc=0.1)
-    tr = Trainer(student, method, conf, task_id=1, n_batches_per_epoch=1000, pipeline_optimizer=True)
+    tr = Trainer(student, method, step_conf("warmup_perc"), task_id=1, n_batches_per_epoch=1000, pipeline_optimizer=True)
     batch = mem.sample()   # carries the loader's max_label_rows hint: the row-sparse head (256 of 1024 rows)
-    ts, rec = [], None
-    for i in range(warmup + steps):
-        t0 = time.perf_counter()
-        rec = tr.step(dict(batch), i)
-        torch.cuda.synchronize()
-        if i >= warmup:
-            ts.append((time.perf_counter() - t0) * 1e3)
-    tr.join()
-    torch.cuda.synchronize()
+    ts, _, rec = run_steps(tr, batch, steps, warmup)
     parts = ""
     if method_name == "lwf":
         parts = f"  (last step: CE {float(method.last_ce):.4f}, KD {float(method.last_kd):.3e})"

@@ -19,70 +19,24 @@ parameter) of the same run is marked.
     python tools/mas_bench.py --resources        # no GPU: registers and scratch of the kernels, from the hipcc gfx950 build
 """
 import os
-import re
 import statistics
-import subprocess
 import sys
-import tempfile
 import time
-import types
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from benchlib import rate_row, resources, run_steps, samples, step_conf, timed, to_dev  # noqa: E402
 
 REPS = 15
 FREE_RUNS, FREE_STEPS = 5, 8
 dev = "cuda"
 
-
-def resources():
-    """VGPRs, SGPRs, scratch and occupancy of every kernel in mas.hip, sqnorm.hip and si.hip as hipcc reports them for gfx950."""
-    from mafed_amd import build
-    print("# hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage")
-    print(f"{'kernel':>58s} {'VGPRs':>6s} {'SGPRs':>6s} {'scratch B/lane':>15s} {'waves/SIMD':>11s}")
-    for src in ("mas.hip", "sqnorm.hip", "si.hip"):
-        with tempfile.TemporaryDirectory() as tmp:
-            r = subprocess.run([build._hipcc()] + build.FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(build.CSRC, src), "-o",
-                                os.path.join(tmp, "o.o")], capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError(r.stderr[-2000:])
-        field = lambda block, key: re.search(key + r": (\d+)", block).group(1)
-        for block in r.stderr.split("Function Name: ")[1:]:
-            name = subprocess.run(["c++filt", block.split()[0]], capture_output=True, text=True).stdout.strip() or block.split()[0]
-            name = re.sub(r"\(.*", "", name).replace("void ", "").replace("mafed::", "")
-            cols = [field(block, key) for key in (" VGPRs", "TotalSGPRs", r"ScratchSize \[bytes/lane\]", r"Occupancy \[waves/SIMD\]")]
-            print(f"{src + ': ' + name:>58s} {cols[0]:>6s} {cols[1]:>6s} {cols[2]:>15s} {cols[3]:>11s}")
-
-
 if "--resources" in sys.argv[1:]:
-    resources()
+    resources(("mas.hip", "sqnorm.hip", "si.hip"), 58, lds=False)
     sys.exit(0)
 
 import torch  # noqa: E402
 
 from mafed_amd import EWC, MAS, SI, Naive, Trainer, VLPythiaConfig, VLPythiaForCausalLM, ops  # noqa: E402
-
-
-def timed(fn, reps=REPS, warmup=3):
-    """[us per call] from device events around each call."""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1) * 1e3)
-    return out
-
-
-def _row(name, nbytes, us, mark=""):
-    med = statistics.median(us)
-    print(f"{name:>36s} {med:10.1f} {min(us):8.1f} {max(us):8.1f} {nbytes / 1e6:8.1f} {nbytes / med / 1e6:6.2f}{mark}", flush=True)
-    return nbytes / med / 1e6
 
 
 def kernel_table(n):
@@ -108,9 +62,9 @@ def kernel_table(n):
     print(f"{'pass [bytes per parameter]':>36s} {'median us':>10s} {'min':>8s} {'max':>8s} {'MB':>8s} {'TB/s':>6s}")
     rate = {}
     for name, bpp, fn in rows:
-        us = timed(fn)
+        us = timed(fn, REPS)
         below = name == "mas_penalty" and n * bpp / statistics.median(us) / 1e6 < 0.9 * rate["ewc_penalty_bwd"]
-        rate[name] = _row(f"{name} [{bpp}]", n * bpp, us, "   <-- more than 10 % below ewc_penalty_bwd" if below else "")
+        rate[name] = rate_row(f"{name} [{bpp}]", n * bpp, us, "   <-- more than 10 % below ewc_penalty_bwd" if below else "")
     del g, p, anchor, omega, acc, sg, sp
     torch.cuda.empty_cache()
     V = 50304
@@ -126,55 +80,28 @@ def kernel_table(n):
                 (f"sqnorm_fwd {R} x {V}", labelled * V * 2, lambda: ops.sqnorm_fwd(z, lab)),
                 (f"ce_bwd {R} x {V}", (labelled + R) * V * 2, lambda: ops.ce_bwd(z, lab, lse, one, out=out)),
                 (f"sqnorm_bwd {R} x {V}", (labelled + R) * V * 2, lambda: ops.sqnorm_bwd(z, lab, one, out=out))):
-            _row(name, nbytes, timed(fn))
+            rate_row(name, nbytes, timed(fn, REPS))
         del z, out
 
 
 def _batch(cfg, B, P, T):
-    gcpu = torch.Generator().manual_seed(1235)
-    ids = torch.randint(1, cfg.vocab_size, (B, T), generator=gcpu)
-    labels = torch.full((B, T), -100, dtype=torch.int64)
-    labels[:, -4:] = ids[:, -4:]
-    feats = torch.randn(B, P, cfg.vision_hidden_size, generator=gcpu).to(torch.bfloat16)
-    batch = {"input_ids": ids, "attention_mask": torch.ones(B, T, dtype=torch.int64), "labels": labels, "patch_embeddings": feats}
-    return {k: v.to(dev) for k, v in batch.items()}
+    return to_dev(samples(cfg, B, P, T, torch.Generator().manual_seed(1235)))
 
 
 def step_times(method_name, cfg, B, P, T, steps=12, warmup=4):
     student = VLPythiaForCausalLM(cfg, compute_dtype=torch.bfloat16, device=dev, seed=1234)
-    batch = _batch(cfg, B, P, T)
-    dense = dict(batch)
-    batch["max_label_rows"] = 4   # the loader's hint: the row-sparse head (256 of 1024 rows)
-    conf = types.SimpleNamespace(accumulate_grad_batches=1, replay_interval=1, grad_norm=2.0, learning_rate=5e-5, betas=(0.9, 0.98),
-                                 weight_decay=0.01, optim="adamw", warmup_steps=0, total_steps=100000)   # no warm-up: the parameters move from step 1
-    method = {"naive": Naive, "ewc": EWC, "si task>=1": SI, "mas task>=1": MAS}[method_name](**({} if method_name == "naive" else {"reg_lambda": 1.0}))
+    dense = _batch(cfg, B, P, T)
+    batch = dict(dense, max_label_rows=4)   # the loader's hint: the row-sparse head (256 of 1024 rows)
+    method ={"naive": Naive, "ewc": EWC, "si task>=1": SI, "mas task>=1": MAS}[method_name](**({} if method_name == "naive" else {"reg_lambda": 1.0}))
     consolidated = method_name != "naive"
-    tr = Trainer(student, method, conf, task_id=1 if consolidated else 0, n_batches_per_epoch=1000, pipeline_optimizer=True)
+    tr = Trainer(student, method, step_conf("no_warmup"), task_id=1 if consolidated else 0, n_batches_per_epoch=1000, pipeline_optimizer=True)
     if consolidated:
         # one step so that the parameters have left their start (and SI has a path integral to consolidate), then the task boundary
         tr.step(dict(batch), 0)
         tr.join()
         method.update(student, dataloader=[dense])
         student.zero_grad()
-    ts, rec, i = [], None, 0
-    for _ in range(warmup + steps):
-        t0 = time.perf_counter()
-        rec = tr.step(dict(batch), i)
-        torch.cuda.synchronize()
-        if i >= warmup:
-            ts.append((time.perf_counter() - t0) * 1e3)
-        i += 1
-    free = []
-    for _ in range(FREE_RUNS):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(FREE_STEPS):
-            rec = tr.step(dict(batch), i)
-            i += 1
-        torch.cuda.synchronize()
-        free.append((time.perf_counter() - t0) * 1e3 / FREE_STEPS)
-    tr.join()
-    torch.cuda.synchronize()
+    ts, free, rec = run_steps(tr, batch, steps, warmup, free=(FREE_RUNS, FREE_STEPS))
     parts = f"  penalty {float(method.last_penalty):.3e}" if isinstance(method, (SI, MAS)) else ""
     return ts, free, float(rec["loss"]), float(rec["grad_norm"]), parts, student.flat_grads.numel()
 

@@ -19,62 +19,24 @@ There is no speed gate: the table is reported as measured.
     python tools/merge_bench.py --resources        # no GPU: registers, scratch and LDS of the kernels, from the hipcc gfx950 build
 """
 import os
-import re
 import statistics
-import subprocess
 import sys
-import tempfile
-import time
-import types
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from benchlib import parent_lib_ab, resources, run_steps, samples, step_conf, timed, to_dev  # noqa: E402
 
 REPS = 15
 FREE_RUNS, FREE_STEPS = 5, 8
 DENSITY = 0.2
 dev = "cuda"
 
-
-def resources():
-    """VGPRs, SGPRs, scratch, LDS and occupancy of every kernel in merge.hip as hipcc reports them for gfx950."""
-    from mafed_amd import build
-    print("# hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage")
-    print(f"{'kernel':>44s} {'VGPRs':>6s} {'SGPRs':>6s} {'scratch B/lane':>15s} {'LDS B/block':>12s} {'waves/SIMD':>11s}")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run([build._hipcc()] + build.FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(build.CSRC, "merge.hip"), "-o",
-                            os.path.join(tmp, "o.o")], capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(r.stderr[-2000:])
-    field = lambda block, key: re.search(key + r": (\d+)", block).group(1)
-    for block in r.stderr.split("Function Name: ")[1:]:
-        name = subprocess.run(["c++filt", block.split()[0]], capture_output=True, text=True).stdout.strip() or block.split()[0]
-        name = re.sub(r"\(.*", "", name).replace("void ", "").replace("mafed::", "")
-        cols = [field(block, key) for key in (" VGPRs", "TotalSGPRs", r"ScratchSize \[bytes/lane\]", r"LDS Size \[bytes/block\]", r"Occupancy \[waves/SIMD\]")]
-        print(f"{name:>44s} {cols[0]:>6s} {cols[1]:>6s} {cols[2]:>15s} {cols[3]:>12s} {cols[4]:>11s}")
-
-
 if "--resources" in sys.argv[1:]:
-    resources()
+    resources(("merge.hip",), 44)
     sys.exit(0)
 
 import torch  # noqa: E402
 
 from mafed_amd import Naive, TaskMerging, Trainer, VLPythiaConfig, VLPythiaForCausalLM, ops  # noqa: E402
-
-
-def timed(fn, reps=REPS, warmup=3):
-    """[us per call] from device events around each call."""
-    out = []
-    for k in range(warmup + reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        if k >= warmup:
-            out.append(e0.elapsed_time(e1) * 1e3)
-    return out
 
 
 def kernel_table(n, rows_seg):
@@ -116,7 +78,7 @@ def kernel_table(n, rows_seg):
     print(f"{'pass [bytes per parameter]':>48s} {'median us':>10s} {'min':>8s} {'max':>8s} {'MB':>8s} {'TB/s':>6s}   ratio to the sibling")
     rate = {}
     for name, bpp, elems, sibling, fn in rows:
-        us = timed(fn)
+        us = timed(fn, REPS)
         med, nbytes = statistics.median(us), elems * bpp
         rate[name] = nbytes / med / 1e6
         beside = f"   {rate[name] / rate[sibling]:.2f} of {sibling}" if sibling else ""
@@ -126,45 +88,14 @@ def kernel_table(n, rows_seg):
           f"{blocks} blocks per tensor at most", flush=True)
 
 
-def _batch(cfg, B, P, T):
-    gcpu = torch.Generator().manual_seed(1235)
-    ids = torch.randint(1, cfg.vocab_size, (B, T), generator=gcpu)
-    labels = torch.full((B, T), -100, dtype=torch.int64)
-    labels[:, -4:] = ids[:, -4:]
-    feats = torch.randn(B, P, cfg.vision_hidden_size, generator=gcpu).to(torch.bfloat16)
-    batch = {"input_ids": ids, "attention_mask": torch.ones(B, T, dtype=torch.int64), "labels": labels, "patch_embeddings": feats}
-    return {k: v.to(dev) for k, v in batch.items()}
-
-
 def step_times(method_name, cfg, B, P, T, steps=12, warmup=4):
     student = VLPythiaForCausalLM(cfg, compute_dtype=torch.bfloat16, device=dev, seed=1234)
-    batch = _batch(cfg, B, P, T)
-    batch["max_label_rows"] = 4   # the loader's hint: the row-sparse head (256 of 1024 rows)
-    conf = types.SimpleNamespace(accumulate_grad_batches=1, replay_interval=1, grad_norm=2.0, learning_rate=5e-5, betas=(0.9, 0.98),
-                                 weight_decay=0.01, optim="adamw", warmup_steps=0, total_steps=100000)
+    batch = to_dev(samples(cfg, B, P, T, torch.Generator().manual_seed(1235)), sparse_head=True)
     method = Naive() if method_name == "naive" else TaskMerging(rule="magmax")
     if method_name != "naive":
         method.begin(student)
-    tr = Trainer(student, method, conf, task_id=0, n_batches_per_epoch=1000, pipeline_optimizer=True)
-    ts, rec, i = [], None, 0
-    for _ in range(warmup + steps):
-        t0 = time.perf_counter()
-        rec = tr.step(dict(batch), i)
-        torch.cuda.synchronize()
-        if i >= warmup:
-            ts.append((time.perf_counter() - t0) * 1e3)
-        i += 1
-    free = []
-    for _ in range(FREE_RUNS):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(FREE_STEPS):
-            rec = tr.step(dict(batch), i)
-            i += 1
-        torch.cuda.synchronize()
-        free.append((time.perf_counter() - t0) * 1e3 / FREE_STEPS)
-    tr.join()
-    torch.cuda.synchronize()
+    tr = Trainer(student, method, step_conf("no_warmup"), task_id=0, n_batches_per_epoch=1000, pipeline_optimizer=True)
+    ts, free, rec = run_steps(tr, batch, steps, warmup, free=(FREE_RUNS, FREE_STEPS))
     rows_seg = [[o, m] for o, m, _ in student._offsets.values()]
     return ts, free, float(rec["loss"]), float(rec["grad_norm"]), student.flat_grads.numel(), rows_seg
 
@@ -192,17 +123,8 @@ def main():
     print(f"# flat buffers of {n_flat} elements ({n_flat * 4 / 1e9:.2f} GB per fp32 buffer); device-event time around each call, us, median (min .. max) of {REPS}")
     kernel_table(n_flat, rows_seg)
     if "--parent-lib" in sys.argv[1:]:
-        parent = os.path.abspath(sys.argv[sys.argv.index("--parent-lib") + 1])
-        assert os.path.exists(parent), parent
-        print("# naive, the parent commit's library against this tree's, alternating, a fresh process each")
-        env0 = {k: v for k, v in os.environ.items() if k not in ("MAFED_HIP_LIB", "MAFED_HIP_LIB_LOOSE")}
-        for rnd in (1, 2, 3):
-            for who, env in (("parent library", dict(env0, MAFED_HIP_LIB=parent, MAFED_HIP_LIB_LOOSE="1")), ("this tree's library", env0)):
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--naive-only"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
-                if r.returncode != 0:
-                    print(f"## {who}, round {rnd}: the run ended with status {r.returncode}", flush=True)
-                    return 1
-                print(f"{who + ', round %d' % rnd:>28s}:{r.stdout.strip().split(':', 1)[1]}", flush=True)
+        return parent_lib_ab(__file__, sys.argv[sys.argv.index("--parent-lib") + 1],
+                             emit=lambda who, rnd, out: print(f"{who + ', round %d' % rnd:>28s}:{out.strip().split(':', 1)[1]}", flush=True))
     return 0
 
 

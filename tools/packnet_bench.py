@@ -18,69 +18,23 @@ There is no speed gate: the table is reported as measured.  A per-step pass (mas
     python tools/packnet_bench.py --resources        # no GPU: registers and scratch of the kernels, from the hipcc gfx950 build
 """
 import os
-import re
 import statistics
-import subprocess
 import sys
-import tempfile
-import time
-import types
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from benchlib import rate_row, resources, run_steps, samples, step_conf, timed, to_dev  # noqa: E402
 
 REPS = 15
 FREE_RUNS, FREE_STEPS = 5, 8
 dev = "cuda"
 
-
-def resources():
-    """VGPRs, SGPRs, scratch, LDS and occupancy of every kernel in packnet.hip as hipcc reports them for gfx950."""
-    from mafed_amd import build
-    print("# hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage")
-    print(f"{'kernel':>44s} {'VGPRs':>6s} {'SGPRs':>6s} {'scratch B/lane':>15s} {'LDS B/block':>12s} {'waves/SIMD':>11s}")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run([build._hipcc()] + build.FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(build.CSRC, "packnet.hip"), "-o",
-                            os.path.join(tmp, "o.o")], capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(r.stderr[-2000:])
-    field = lambda block, key: re.search(key + r": (\d+)", block).group(1)
-    for block in r.stderr.split("Function Name: ")[1:]:
-        name = subprocess.run(["c++filt", block.split()[0]], capture_output=True, text=True).stdout.strip() or block.split()[0]
-        name = re.sub(r"\(.*", "", name).replace("void ", "").replace("mafed::", "")
-        cols = [field(block, key) for key in (" VGPRs", "TotalSGPRs", r"ScratchSize \[bytes/lane\]", r"LDS Size \[bytes/block\]", r"Occupancy \[waves/SIMD\]")]
-        print(f"{name:>44s} {cols[0]:>6s} {cols[1]:>6s} {cols[2]:>15s} {cols[3]:>12s} {cols[4]:>11s}")
-
-
 if "--resources" in sys.argv[1:]:
-    resources()
+    resources(("packnet.hip",), 44)
     sys.exit(0)
 
 import torch  # noqa: E402
 
 from mafed_amd import MAS, Naive, PackNet, Trainer, VLPythiaConfig, VLPythiaForCausalLM, ops  # noqa: E402
-
-
-def timed(fn, reps=REPS, warmup=3, before=None):
-    """[us per call] from device events around each call; ``before`` runs outside the events."""
-    out = []
-    for k in range(warmup + reps):
-        if before is not None:
-            before()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        if k >= warmup:
-            out.append(e0.elapsed_time(e1) * 1e3)
-    return out
-
-
-def _row(name, nbytes, us, mark=""):
-    med = statistics.median(us)
-    print(f"{name:>36s} {med:10.1f} {min(us):8.1f} {max(us):8.1f} {nbytes / 1e6:8.1f} {nbytes / med / 1e6:6.2f}{mark}", flush=True)
-    return nbytes / med / 1e6
 
 
 def kernel_table(n):
@@ -110,20 +64,10 @@ def kernel_table(n):
     print(f"{'pass [bytes per parameter]':>36s} {'median us':>10s} {'min':>8s} {'max':>8s} {'MB':>8s} {'TB/s':>6s}")
     rate = {}
     for name, bpp, fn in rows:
-        us = timed(fn)
+        us = timed(fn, REPS)
         per_step = name.startswith(("packnet_mask_grad", "packnet_hold (50", "packnet_hold (100"))
         below = per_step and n * bpp / statistics.median(us) / 1e6 < 0.8 * rate["mas_penalty"]
-        rate[name] = _row(f"{name} [{bpp:.3g}]", n * bpp, us, "   <-- below 0.8 of mas_penalty" if below else "")
-
-
-def _batch(cfg, B, P, T):
-    gcpu = torch.Generator().manual_seed(1235)
-    ids = torch.randint(1, cfg.vocab_size, (B, T), generator=gcpu)
-    labels = torch.full((B, T), -100, dtype=torch.int64)
-    labels[:, -4:] = ids[:, -4:]
-    feats = torch.randn(B, P, cfg.vision_hidden_size, generator=gcpu).to(torch.bfloat16)
-    batch = {"input_ids": ids, "attention_mask": torch.ones(B, T, dtype=torch.int64), "labels": labels, "patch_embeddings": feats}
-    return {k: v.to(dev) for k, v in batch.items()}
+        rate[name] = rate_row(f"{name} [{bpp:.3g}]", n * bpp, us, "   <-- below 0.8 of mas_penalty" if below else "")
 
 
 def prune_times(cfg, reps=7):
@@ -168,40 +112,19 @@ def prune_times(cfg, reps=7):
 
 def step_times(method_name, cfg, B, P, T, steps=12, warmup=4):
     student = VLPythiaForCausalLM(cfg, compute_dtype=torch.bfloat16, device=dev, seed=1234)
-    batch = _batch(cfg, B, P, T)
-    dense = dict(batch)
-    batch["max_label_rows"] = 4   # the loader's hint: the row-sparse head (256 of 1024 rows)
-    conf = types.SimpleNamespace(accumulate_grad_batches=1, replay_interval=1, grad_norm=2.0, learning_rate=5e-5, betas=(0.9, 0.98),
-                                 weight_decay=0.01, optim="adamw", warmup_steps=0, total_steps=100000)   # no warm-up: the parameters move from step 1
+    dense = to_dev(samples(cfg, B, P, T, torch.Generator().manual_seed(1235)))
+    batch = dict(dense, max_label_rows=4)   # the loader's hint: the row-sparse head (256 of 1024 rows)
     method = {"naive": lambda: Naive(), "packnet task 0": lambda: PackNet(), "packnet task>=1": lambda: PackNet(prune_fraction=0.5),
               "mas task>=1": lambda: MAS(reg_lambda=1.0)}[method_name]()
     later = method_name.endswith("task>=1")
-    tr = Trainer(student, method, conf, task_id=1 if later else 0, n_batches_per_epoch=1000, pipeline_optimizer=True)
+    tr = Trainer(student, method, step_conf("no_warmup"), task_id=1 if later else 0, n_batches_per_epoch=1000, pipeline_optimizer=True)
     if later:
         # one step so that the parameters have left their start, then the task boundary (PackNet: prune at 0.5 and consolidate)
         tr.step(dict(batch), 0)
         tr.join()
         method.update(student, dataloader=[dense])
         student.zero_grad()
-    ts, rec, i = [], None, 0
-    for _ in range(warmup + steps):
-        t0 = time.perf_counter()
-        rec = tr.step(dict(batch), i)
-        torch.cuda.synchronize()
-        if i >= warmup:
-            ts.append((time.perf_counter() - t0) * 1e3)
-        i += 1
-    free = []
-    for _ in range(FREE_RUNS):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(FREE_STEPS):
-            rec = tr.step(dict(batch), i)
-            i += 1
-        torch.cuda.synchronize()
-        free.append((time.perf_counter() - t0) * 1e3 / FREE_STEPS)
-    tr.join()
-    torch.cuda.synchronize()
+    ts, free, rec = run_steps(tr, batch, steps, warmup, free=(FREE_RUNS, FREE_STEPS))
     parts = ""
     if isinstance(method, PackNet) and method.owner is not None:
         parts = f"  trainable {float((method.owner == method.task_id).float().mean()):.3f} of the buffer"

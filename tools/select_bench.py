@@ -14,60 +14,24 @@ There is no speed gate: the table is reported as measured.
     python tools/select_bench.py --resources        # no GPU: registers, LDS and scratch of the kernels, from the hipcc gfx950 build
 """
 import os
-import re
 import statistics
-import subprocess
 import sys
-import tempfile
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from benchlib import resources, samples, timed, to_dev  # noqa: E402
 
 REPS, TORCH_PICKS, FORWARDS = 5, 50, 12
 SHAPES = [(20000, 1024, 1000), (100000, 1024, 1000), (100000, 2048, 1000)]
 dev = "cuda"
 
-
-def resources():
-    """VGPRs, SGPRs, scratch, LDS and occupancy of every kernel in select.hip as hipcc reports them for gfx950 (the scan's template
-    arguments: 16-byte loads, v in LDS, minimise, fold the running minimum; its LDS is dynamic, 16 cdiv(d, 4) + 64 bytes)."""
-    from mafed_amd import build
-    print("# hipcc --offload-arch=gfx950 -O3, -Rpass-analysis=kernel-resource-usage")
-    print(f"{'kernel':>56s} {'VGPRs':>6s} {'SGPRs':>6s} {'scratch B/lane':>15s} {'LDS B/block':>12s} {'waves/SIMD':>11s}")
-    with tempfile.TemporaryDirectory() as tmp:
-        r = subprocess.run([build._hipcc()] + build.FLAGS + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(build.CSRC, "select.hip"), "-o",
-                            os.path.join(tmp, "o.o")], capture_output=True, text=True)
-    if r.returncode != 0:
-        raise RuntimeError(r.stderr[-2000:])
-    field = lambda block, key: re.search(key + r": (\d+)", block).group(1)
-    for block in r.stderr.split("Function Name: ")[1:]:
-        name = subprocess.run(["c++filt", block.split()[0]], capture_output=True, text=True).stdout.strip() or block.split()[0]
-        name = re.sub(r"\(.*", "", name).replace("void ", "").replace("mafed::", "")
-        cols = [field(block, key) for key in (" VGPRs", "TotalSGPRs", r"ScratchSize \[bytes/lane\]", r"LDS Size \[bytes/block\]", r"Occupancy \[waves/SIMD\]")]
-        print(f"{name:>56s} {cols[0]:>6s} {cols[1]:>6s} {cols[2]:>15s} {cols[3]:>12s} {cols[4]:>11s}")
-
-
 if "--resources" in sys.argv[1:]:
-    resources()
+    # (the scan's template arguments: 16-byte loads, v in LDS, minimise, fold the running minimum; its LDS is dynamic, 16 cdiv(d, 4) + 64 bytes)
+    resources(("select.hip",), 56)
     sys.exit(0)
 
 import torch  # noqa: E402
 
 from mafed_amd import VLPythiaConfig, VLPythiaForCausalLM, ops  # noqa: E402
-
-
-def timed(fn, reps=REPS, warmup=2):
-    """[us per call] from device events around each call"""
-    out = []
-    for i in range(warmup + reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        if i >= warmup:
-            out.append(e0.elapsed_time(e1) * 1e3)
-    return out
 
 
 def torch_greedy(X, mean, mode, k):
@@ -100,12 +64,9 @@ def forward_us():
     cfg = VLPythiaConfig.preset("410m", num_vision_tokens=P)
     model = VLPythiaForCausalLM(cfg, compute_dtype=torch.bfloat16, device=dev, seed=1234)
     model.sync_shadow()
-    gcpu = torch.Generator().manual_seed(1235)
-    ids = torch.randint(1, cfg.vocab_size, (B, T), generator=gcpu).to(dev)
-    mask = torch.ones(B, T, dtype=torch.int64, device=dev)
-    feats = torch.randn(B, P, cfg.vision_hidden_size, generator=gcpu).to(torch.bfloat16).to(dev)
+    b = to_dev(samples(cfg, B, P, T, torch.Generator().manual_seed(1235)))
     out = torch.empty((2, B, cfg.hidden_size), dtype=torch.float32, device=dev)
-    us = timed(lambda: model.pooled_features(ids, mask, patch_embeddings=feats, out=out), reps=FORWARDS, warmup=3)
+    us = timed(lambda: model.pooled_features(b["input_ids"], b["attention_mask"], patch_embeddings=b["patch_embeddings"], out=out), FORWARDS)
     del model
     torch.cuda.empty_cache()
     return us
@@ -126,10 +87,10 @@ def main():
         X = torch.randn(n, d, generator=gen, device=dev)
         mean = ops.cka_stats(X, row_norms=False)[0][0]
         flat, clip2 = X.view(-1), torch.empty(2, device=dev)
-        clip = statistics.median(timed(lambda: ops.gradnorm_clip(flat, 2.0, clip2)))
+        clip = statistics.median(timed(lambda: ops.gradnorm_clip(flat, 2.0, clip2), REPS, warmup=2))
         nbytes = 4.0 * n * d
         for name, mode in (("herding", ops.SELECT_HERDING), ("kcenter", ops.SELECT_KCENTER)):
-            us = [t / k for t in timed(lambda: ops.select_greedy(X, mean, mode, k))]
+            us = [t / k for t in timed(lambda: ops.select_greedy(X, mean, mode, k), REPS, warmup=2)]
             med = statistics.median(us)
             tus = [t / TORCH_PICKS for t in timed(lambda: torch_greedy(X, mean, mode, TORCH_PICKS), reps=3, warmup=1)]
             same = torch_greedy(X, mean, mode, 8) == ops.select_greedy(X, mean, mode, 8)[0].tolist()

@@ -17,33 +17,16 @@ There is no speed gate: the table is reported as measured.  A pass more than 15 
 import os
 import statistics
 import sys
-import time
-import types
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
+from benchlib import run_steps, samples, step_conf, timed, to_dev  # noqa: E402
 from mafed_amd import EWC, SI, Naive, Trainer, VLPythiaConfig, VLPythiaForCausalLM, ops  # noqa: E402
 
 REPS = 15
 FREE_RUNS, FREE_STEPS = 5, 8
 dev = "cuda"
-
-
-def timed(fn, reps=REPS, warmup=3):
-    """[us per call] from device events around each call."""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        out.append(e0.elapsed_time(e1) * 1e3)
-    return out
 
 
 def kernel_table(n):
@@ -72,7 +55,7 @@ def kernel_table(n):
     print(f"{'pass':>26s} {'B/param':>8s} {'median us':>10s} {'min':>8s} {'max':>8s} {'MB':>8s} {'TB/s':>6s}")
     rate = {}
     for name, bpp, fn in rows:
-        us = timed(fn)
+        us = timed(fn, REPS)
         med = statistics.median(us)
         rate[name] = n * bpp / med / 1e6
         floor = 0.85 * min(rate.get("ewc_penalty_bwd", 0.0), rate.get("agem_project (violated)", 0.0))
@@ -82,16 +65,7 @@ def kernel_table(n):
 
 def step_times(method_name, cfg, B, P, T, steps=12, warmup=4):
     student = VLPythiaForCausalLM(cfg, compute_dtype=torch.bfloat16, device=dev, seed=1234)
-    gcpu = torch.Generator().manual_seed(1235)
-    ids = torch.randint(1, cfg.vocab_size, (B, T), generator=gcpu)
-    labels = torch.full((B, T), -100, dtype=torch.int64)
-    labels[:, -4:] = ids[:, -4:]
-    feats = torch.randn(B, P, cfg.vision_hidden_size, generator=gcpu).to(torch.bfloat16)
-    batch = {"input_ids": ids, "attention_mask": torch.ones(B, T, dtype=torch.int64), "labels": labels, "patch_embeddings": feats}
-    batch = {k: v.to(dev) for k, v in batch.items()}
-    batch["max_label_rows"] = 4   # the loader's hint: the row-sparse head (256 of 1024 rows)
-    conf = types.SimpleNamespace(accumulate_grad_batches=1, replay_interval=1, grad_norm=2.0, learning_rate=5e-5, betas=(0.9, 0.98),
-                                 weight_decay=0.01, optim="adamw", warmup_steps=0, total_steps=100000)   # no warm-up: the parameters move from step 1
+    batch = to_dev(samples(cfg, B, P, T, torch.Generator().manual_seed(1235)), sparse_head=True)
     consolidated = method_name in ("ewc", "si task>=1")
     if method_name == "naive":
         method = Naive()
@@ -99,34 +73,14 @@ def step_times(method_name, cfg, B, P, T, steps=12, warmup=4):
         method = EWC(reg_lambda=1.0)
     else:
         method = SI(reg_lambda=1.0)
-    tr = Trainer(student, method, conf, task_id=1 if consolidated else 0, n_batches_per_epoch=1000, pipeline_optimizer=True)
+    tr = Trainer(student, method, step_conf("no_warmup"), task_id=1 if consolidated else 0, n_batches_per_epoch=1000, pipeline_optimizer=True)
     if consolidated:
         # one step so that SI has a path integral to consolidate, then the task boundary
         tr.step(dict(batch), 0)
         tr.join()
         method.update(student, dataloader=[{k: v for k, v in batch.items() if k != "max_label_rows"}])
         student.zero_grad()
-    ts, rec, i = [], None, 0
-    for _ in range(warmup + steps):
-        t0 = time.perf_counter()
-        rec = tr.step(dict(batch), i)
-        torch.cuda.synchronize()
-        if i >= warmup:
-            ts.append((time.perf_counter() - t0) * 1e3)
-        i += 1
-    # free-running: FREE_RUNS blocks of FREE_STEPS steps with one synchronise behind each block -- what a training loop sees, and the
-    # form in which the pipelined optimiser runs under the next step's forward
-    free = []
-    for _ in range(FREE_RUNS):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(FREE_STEPS):
-            rec = tr.step(dict(batch), i)
-            i += 1
-        torch.cuda.synchronize()
-        free.append((time.perf_counter() - t0) * 1e3 / FREE_STEPS)
-    tr.join()
-    torch.cuda.synchronize()
+    ts, free, rec = run_steps(tr, batch, steps, warmup, free=(FREE_RUNS, FREE_STEPS))
     parts = f"  penalty {float(method.last_penalty):.3e}" if isinstance(method, SI) else ""
     return ts, free, float(rec["loss"]), float(rec["grad_norm"]), parts, student.flat_grads.numel()
 
